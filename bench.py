@@ -10,7 +10,7 @@ One "step" = one pass of the hot path over ONE enwik9-shaped 10^9-byte job (239 
           `value` ("scaling": "weak"): EVERY rank runs the N = 1 step on a 10^9-byte job of its own, resident in
           its HBM -- blocks are independent units, there is no data-path collective, nothing crosses PCIe inside
           the timed region -- so `value` = N x 10^9 B / wall time per step (max over ranks) and divides by N = 1's
-          like for like.  The same line carries `config4_host_gather` ("strong"), BASELINE.json config 4: ONE
+          like for like.  With --full the line carries `config4_host_gather` ("strong"), BASELINE.json config 4: ONE
           10^9-byte job, block b -> rank b % N (tsq_threads.cpp:71), every rank encodes the blocks it owns -> one
           RCCL all-gather of the u32 stream sizes -> every rank DMAs its frames to their final place in ONE
           container in host memory (a prefix sum, no gathering rank) -> barrier -> every rank walks the frames,
@@ -21,10 +21,16 @@ One "step" = one pass of the hot path over ONE enwik9-shaped 10^9-byte job (239 
 value = uncompressed bytes all ranks worked through / wall time per step (GB/s = 1e9 B/s), max over ranks.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events recorded inside the library on
-the launch stream; `peak` = 8 TB/s specification, `peak_measured` = a plain device copy kernel on this GPU)
-and, at N=1, `cpu_baseline` (the reference's own tsqEncode/tsqDecode compiled into oracle/_ref, or the oracle
-port, on the host cores: pinned threads, first touch by the owner, 1 warm + 5 timed passes, median and best,
-idealised and reference-shaped pipelines, 1-thread rate and parallel efficiency).
+the launch stream during the timed steps; `peak` = 8 TB/s specification).  A plain run does only that: set up,
+W warm-up steps, K timed steps, the line.  `--full` adds what takes runs of its own: `peak_measured` (a plain
+device copy kernel on this GPU), the timed container compared with the CPU oracle's, and at N=1 `throughput`,
+the other level, config 5's inputs, `host_gather` and `cpu_baseline` (the reference's own tsqEncode/tsqDecode
+compiled into oracle/_ref, or the oracle port, on the host cores: pinned threads, first touch by the owner,
+1 warm + 5 timed passes, median and best, idealised and reference-shaped pipelines, 1-thread rate and parallel
+efficiency); at N>1 `config4_host_gather`.
+
+`--dump-outputs DIR` writes what the last timed step returned (the container and the decompressed bytes) as
+float arrays under DIR, so that two builds can be compared output for output (dump_outputs below).
 """
 import argparse
 import json
@@ -38,6 +44,34 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 GUIDE_COPY_GBS = 6290.0        # same guide: what a float4 copy kernel measures on an MI355X (79 % of the specification)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: bytes drawn from each output (float32, 16 MiB per array)
+DUMP_CHUNK = 1 << 16           # --dump-outputs: every output byte is covered by the sums of these chunks
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """For each uint8 device tensor a caller of the timed path receives: `<name>_bytes.npy` (its length, float64),
+    `<name>_sample.npy` (the whole output if it has at most DUMP_SAMPLE bytes, else DUMP_SAMPLE bytes at sorted positions
+    drawn by a fixed seed from its length; float32) and `<name>_chunk_sums.npy` (the sum of every DUMP_CHUNK bytes, the
+    last chunk possibly short; float64, exact).  Same job and same outputs -> the same files."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        m = t.numel()
+        if m > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, m, DUMP_SAMPLE))
+            sample = t[torch.from_numpy(idx).to(t.device)]
+        else:
+            sample = t
+        full = m - m % DUMP_CHUNK
+        sums = [t[:full].view(-1, DUMP_CHUNK).sum(1)] if full else []
+        if m > full:
+            sums.append(t[full:].sum().reshape(1))
+        sums = torch.cat(sums).double() if sums else torch.zeros(0, dtype=torch.float64)
+        np.save(os.path.join(out_dir, f"{name}_bytes.npy"), np.array([m], dtype=np.float64))
+        np.save(os.path.join(out_dir, f"{name}_sample.npy"), sample.float().cpu().numpy())
+        np.save(os.path.join(out_dir, f"{name}_chunk_sums.npy"), sums.cpu().numpy())
 
 
 def pmc_traffic(kernel_substr: str, blocks: int, fingerprint: str):
@@ -300,9 +334,16 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the extra sections (the other level, config 5's inputs, the host-gather step)")
     ap.add_argument("--config5-size", type=int, default=1 << 30)
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = production, 1 = serial baselines, 5 = the previous round's production encoder, frozen in the A/B library)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the copy-probe peak, the oracle comparisons, and the "
+                         "sections the --no-* options above switch off (a plain run times the headline job only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (container, decompressed bytes) under DIR as .npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))               # `--gpus N` means N ranks, whoever starts the script
 
@@ -353,8 +394,9 @@ def main():
     codec = tsq.DeviceCodec(local_rank, ab=args.variant == 5)
     codec.set_variant(args.variant, args.variant if args.variant in (0, 1) else 0)
 
-    def single_gpu_job(seed, steps, warmup, check_oracle=False, n=n, nb=nb, ext=None, make=None):
-        """The N=1 step on this rank's own job.  -> (dt, comp_bytes, enc/dec kernel ms+launches, call ms, container == oracle's)"""
+    def single_gpu_job(seed, steps, warmup, check_oracle=False, n=n, nb=nb, ext=None, make=None, dump_dir=None):
+        """The N=1 step on this rank's own job.  -> (dt, comp_bytes, enc/dec kernel ms+launches, call ms, container == oracle's)
+        dump_dir: write the last timed step's outputs there (dump_outputs)."""
         ext = args.ext if ext is None else ext
         host = make(n, seed) if make else make_input(n, seed)
         src = torch.from_numpy(host).to(dev)
@@ -380,10 +422,14 @@ def main():
         total_out, status = codec.last_size_status()
         assert status == 0 and total_out == n, (status, total_out)
         assert torch.equal(back, src), "round trip mismatch"
+        timed_container = container.clone() if dump_dir else None    # the last timed step's, before the size read rewrites it
         codec.compress_async(src, ext, container)
         torch.cuda.synchronize()
         comp_bytes, status = codec.last_size_status()
         assert status == 0
+        if dump_dir:
+            dump_outputs(dump_dir, {"container": timed_container[:comp_bytes], "decompressed": back})
+            del timed_container
         oracle_equal = None
         if check_oracle:
             # ... and, outside the timed region, the timed job's container byte for byte against the CPU oracle (the checker)
@@ -398,9 +444,12 @@ def main():
 
     line = None
     if world == 1 and not force_sharded:
-        dt, comp_bytes, (enc_ms, enc_n, dec_ms, dec_n), (cmp_ms, cmp_n, dcm_ms, dcm_n), oracle_equal = single_gpu_job(1, args.steps, args.warmup, check_oracle=not args.no_oracle_check)
-        peak_best, peak_med = codec.measure_copy(4 << 30, 7)
-        probe_shape = codec.copy_probe_shape()
+        dt, comp_bytes, (enc_ms, enc_n, dec_ms, dec_n), (cmp_ms, cmp_n, dcm_ms, dcm_n), oracle_equal = single_gpu_job(
+            1, args.steps, args.warmup, check_oracle=args.full and not args.no_oracle_check, dump_dir=args.dump_outputs)
+        peak_best = peak_med = None
+        if args.full:
+            peak_best, peak_med = codec.measure_copy(4 << 30, 7)
+            probe_shape = codec.copy_probe_shape()
         alg, enc_e, dec_e, dom, enc_avg, dec_avg = roofline_entries(n, comp_bytes, enc_ms, enc_n, dec_ms, dec_n, peak_best)
         traffic, traffic_src = (None, "PMC summaries are collected for the default job only")
         fingerprint = tsq.source_fingerprint()
@@ -423,9 +472,11 @@ def main():
                          "algorithmic_bytes_per_launch": alg, "avg_launch_ms": round(dom[2] * 1e3, 4),
                          # the north star's decode criterion: compressed bytes READ per second by the decode kernel / HBM peak
                          "decode_read_only_frac": dec_e["read_only_frac"],
-                         "peak_measured": round(peak_best, 1), "peak_measured_median": round(peak_med, 1),
+                         "peak_measured": round(peak_best, 1) if peak_best else None,
+                         "peak_measured_median": round(peak_med, 1) if peak_med else None,
                          "frac_of_measured": round(dom[1] / peak_best, 6) if peak_best else None,
-                         "peak_measured_by": "copy_probe_kernel over 4 GiB, bytes read + written, best of 7; shape chosen by the probe: " + probe_shape,
+                         "peak_measured_by": ("copy_probe_kernel over 4 GiB, bytes read + written, best of 7; shape chosen by the probe: " + probe_shape)
+                                             if peak_best else "not measured (bench.py --full measures it)",
                          # the guide's own figure for the same kind of kernel (MI355X_MICROARCH.md: float4 copy, 6.29 TB/s = 79 % of the
                          # specification): this box's probe reaches a few per cent less, so the fraction against it is the stricter one
                          "peak_guide_copy": GUIDE_COPY_GBS, "frac_of_guide_copy": round(dom[1] / GUIDE_COPY_GBS, 6)},
@@ -436,7 +487,7 @@ def main():
             "encode_kernel_GBps": round(n / enc_avg / 1e9, 4) if enc_avg > 0 else 0.0,
             "decode_kernel_GBps": round(n / dec_avg / 1e9, 4) if dec_avg > 0 else 0.0,
         }
-        if not args.no_throughput:
+        if args.full and not args.no_throughput:
             # The headline job has fewer blocks (239) than the GPU has CUs (256): with one workgroup per block its kernel times are
             # per-block latencies.  The chip-filling figure beside it (device-resident kernel throughput): 4 GiB of the
             # same text = 1 024 blocks, same level, same HIP events, the timed container compared with the oracle's afterwards.
@@ -456,7 +507,7 @@ def main():
                 "algorithmic_bytes_per_launch": t_alg,
                 "roofline_encode": te_e, "roofline_decode": td_e,     # (N + C) / t against 8 TB/s and against the measured copy
             }
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             # ---- what a user of the reference sees beyond the published --no-ext row, same HIP events, every
             #      timed container compared with the oracle's outside the timed region.  Short runs (1 warm + 2 timed steps).
             def kernel_line(job_n, dtj, comp, kern, equal, steps_):
@@ -491,7 +542,7 @@ def main():
             #     back and decoded -- both PCIe legs and the host gather inside the step, so that the first point of the 1 -> 8 curve
             #     can be read against points that carry them (bench.py --gpus N runs exactly this per rank)
             line["host_gather"] = host_gather_step(tsq, sharding, codec, dev, n, args.ext, args.steps, not args.no_oracle_check)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # bounded sample, but never fewer blocks than 2 per host thread (block-parallel CPU code)
             line["cpu_baseline"] = cb = cpu_baseline(min(n, args.cpu_sample), args.ext)
             # the north star's criterion as a number: GPU decode over the reference's multithreaded CPU decode on this box's host cores
@@ -533,7 +584,7 @@ def main():
         #     region (a PCIe-inclusive rate is never `value`), the blocks of the N jobs are independent units with no data-path
         #     collective, and the figure divides by N = 1's like for like.  K steps, W warm-ups, barrier + device sync on both sides,
         #     MAX over ranks: the contract's timing exactly.
-        # (2) `config4_host_gather` ("strong"): BASELINE config 4 -- ONE job of `n` bytes, block b owned by rank b % N
+        # (2) `config4_host_gather` ("strong", --full only): BASELINE config 4 -- ONE job of `n` bytes, block b owned by rank b % N
         #     (tsq_threads.cpp:71), one all-gather of the u32 sizes (RCCL), every frame by DMA to its place in ONE container in host
         #     memory, barrier, owned frames back and decoded.  Both PCIe legs and the gather are inside ITS timed region.
         group_world = dist.get_world_size()
@@ -541,76 +592,93 @@ def main():
         dist.all_gather_object(idents, device_identity())
         distinct = len({d["uuid"] or (d["rank"], d["device"]) for d in idents})
 
-        # (2) first: it leaves nothing behind on the device
-        gsteps, gwarm = min(args.steps, 3), min(args.warmup, 1)
-        lay = sharding.ShardLayout(n, rank, world)
-        host = make_input(n, 1)                           # every rank generates the same job and keeps its blocks
-        d_shard = torch.from_numpy(lay.pack_input(host)).to(dev)
-        expect = torch.from_numpy(lay.expected_output(host)).to(dev)
-        del host
-        name = "tsq_bench_%s" % os.environ.get("MASTER_PORT", "0")
-        cap = tsq.container_bound(n)
-        hc = sharding.HostContainer(name, cap, create=True) if rank == 0 else None
-        dist.barrier()
-        if rank != 0:
-            hc = sharding.HostContainer(name, cap, create=False)
-        hc.register()
-        sc = sharding.ShardedCodec(lay, sharding.DeviceBlocks(codec, collective_device=red_dev), hc, args.ext)
-        sc.always_gather = force_sharded                  # (a world of one still runs the all-gather)
-        d_back = torch.empty(max(lay.shard_bytes, 1), dtype=torch.uint8, device=dev)
-        size_seen = [0]
+        # (2) first, with --full only: it leaves nothing behind on the device
+        config4 = None
+        if args.full:
+            gsteps, gwarm = min(args.steps, 3), min(args.warmup, 1)
+            lay = sharding.ShardLayout(n, rank, world)
+            host = make_input(n, 1)                           # every rank generates the same job and keeps its blocks
+            d_shard = torch.from_numpy(lay.pack_input(host)).to(dev)
+            expect = torch.from_numpy(lay.expected_output(host)).to(dev)
+            del host
+            name = "tsq_bench_%s" % os.environ.get("MASTER_PORT", "0")
+            cap = tsq.container_bound(n)
+            hc = sharding.HostContainer(name, cap, create=True) if rank == 0 else None
+            dist.barrier()
+            if rank != 0:
+                hc = sharding.HostContainer(name, cap, create=False)
+            hc.register()
+            sc = sharding.ShardedCodec(lay, sharding.DeviceBlocks(codec, collective_device=red_dev), hc, args.ext)
+            sc.always_gather = force_sharded                  # (a world of one still runs the all-gather)
+            d_back = torch.empty(max(lay.shard_bytes, 1), dtype=torch.uint8, device=dev)
+            size_seen = [0]
 
-        barrier_s = [0.0, 0.0]
+            barrier_s = [0.0, 0.0]
 
-        def step():
-            size_seen[0] = sc.compress(d_shard)
-            t0 = time.perf_counter()
-            dist.barrier()                                # every rank's frames are in the host container
-            t1 = time.perf_counter()
-            sc.decompress(size_seen[0], d_back)
-            t2 = time.perf_counter()
-            dist.barrier()                                # nobody overwrites the container while another still reads it
-            barrier_s[0] += t1 - t0
-            barrier_s[1] += time.perf_counter() - t2
+            def step():
+                size_seen[0] = sc.compress(d_shard)
+                t0 = time.perf_counter()
+                dist.barrier()                                # every rank's frames are in the host container
+                t1 = time.perf_counter()
+                sc.decompress(size_seen[0], d_back)
+                t2 = time.perf_counter()
+                dist.barrier()                                # nobody overwrites the container while another still reads it
+                barrier_s[0] += t1 - t0
+                barrier_s[1] += time.perf_counter() - t2
 
-        for _ in range(gwarm):
-            step()
-        codec.profile(True)
-        for k in sc.seconds:
-            sc.seconds[k] = 0.0
-        barrier_s[0] = barrier_s[1] = 0.0
-        gdt = timed_steps(step, gsteps, 0, world, torch.cuda.synchronize, red_dev)
-        g_enc_ms, g_enc_n, g_dec_ms, g_dec_n = codec.profile_read()
-        codec.profile(False)
-        # where this rank's step went (wall ms per step; rank 0's view): encode = launch + wait for the kernel, size_gather = the
-        # all-gather of u32 sizes, place_d2h = frames to the host container, fetch_h2d_decode = frame walk + frames back + decode
-        breakdown = {k: round(v / gsteps * 1e3, 3) for k, v in sc.seconds.items()}
-        breakdown["barrier_after_place"] = round(barrier_s[0] / gsteps * 1e3, 3)
-        breakdown["barrier_after_decode"] = round(barrier_s[1] / gsteps * 1e3, 3)
-        assert torch.equal(d_back[:lay.shard_bytes], expect), "round trip mismatch on rank %d" % rank
-        g_comp = size_seen[0]
-        # the host-gathered container is a well-formed .tsq file of the whole job
-        g_equal = None
-        if rank == 0:
-            total, frame_at, sizes, ext_bits, out_len = sharding.walk_frames(hc.array, g_comp)
-            assert total == n and len(sizes) == nb and int(frame_at[-1]) + 3 + int(sizes[-1]) == g_comp
-            if not args.no_oracle_check:
-                # ... and, outside the timed region, byte for byte the CPU oracle's container of the same job (the checker)
-                from oracle import pyoracle
-                want = pyoracle.Oracle().compress(make_input(n, 1), args.ext, threads=min(32, os.cpu_count() or 1))
-                g_equal = bool(len(want) == g_comp and bytes(hc.array[:g_comp]) == want)
-                assert g_equal, "the host-gathered container differs from the oracle's"
-        # the slowest rank's kernel times
-        gkt = torch.tensor([g_enc_ms / max(g_enc_n, 1), g_dec_ms / max(g_dec_n, 1)], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(gkt, op=dist.ReduceOp.MAX)
-        dist.barrier()
-        hc.close()
-        del d_shard, d_back, expect, sc
-        torch.cuda.empty_cache()
+            for _ in range(gwarm):
+                step()
+            codec.profile(True)
+            for k in sc.seconds:
+                sc.seconds[k] = 0.0
+            barrier_s[0] = barrier_s[1] = 0.0
+            gdt = timed_steps(step, gsteps, 0, world, torch.cuda.synchronize, red_dev)
+            g_enc_ms, g_enc_n, g_dec_ms, g_dec_n = codec.profile_read()
+            codec.profile(False)
+            # where this rank's step went (wall ms per step; rank 0's view): encode = launch + wait for the kernel, size_gather = the
+            # all-gather of u32 sizes, place_d2h = frames to the host container, fetch_h2d_decode = frame walk + frames back + decode
+            breakdown = {k: round(v / gsteps * 1e3, 3) for k, v in sc.seconds.items()}
+            breakdown["barrier_after_place"] = round(barrier_s[0] / gsteps * 1e3, 3)
+            breakdown["barrier_after_decode"] = round(barrier_s[1] / gsteps * 1e3, 3)
+            assert torch.equal(d_back[:lay.shard_bytes], expect), "round trip mismatch on rank %d" % rank
+            g_comp = size_seen[0]
+            # the host-gathered container is a well-formed .tsq file of the whole job
+            g_equal = None
+            if rank == 0:
+                total, frame_at, sizes, ext_bits, out_len = sharding.walk_frames(hc.array, g_comp)
+                assert total == n and len(sizes) == nb and int(frame_at[-1]) + 3 + int(sizes[-1]) == g_comp
+                if not args.no_oracle_check:
+                    # ... and, outside the timed region, byte for byte the CPU oracle's container of the same job (the checker)
+                    from oracle import pyoracle
+                    want = pyoracle.Oracle().compress(make_input(n, 1), args.ext, threads=min(32, os.cpu_count() or 1))
+                    g_equal = bool(len(want) == g_comp and bytes(hc.array[:g_comp]) == want)
+                    assert g_equal, "the host-gathered container differs from the oracle's"
+            # the slowest rank's kernel times
+            gkt = torch.tensor([g_enc_ms / max(g_enc_n, 1), g_dec_ms / max(g_dec_n, 1)], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(gkt, op=dist.ReduceOp.MAX)
+            dist.barrier()
+            if rank == 0:
+                config4 = {
+                    "what": f"BASELINE config 4: ONE {n} B job ({nb} blocks) block-sharded over {world} GPUs (block b -> rank b % {world}), one all-gather of "
+                            f"the u32 sizes per step, frames DMA'd to one container in host memory, barrier, owned frames back and decoded; both PCIe "
+                            f"legs inside the step, so this is never `value`",
+                    "scaling": "strong", "value": round(aggregate_value(n, gdt, gsteps), 4), "unit": "GB/s", "steps": gsteps, "warmup": gwarm,
+                    "ms_per_step": round(gdt / gsteps * 1e3, 3), "ratio": round(g_comp / n, 5), "container_equals_oracle": g_equal,
+                    "collective_backend": backend,
+                    "slowest_rank_kernel_ms": {"encode": round(float(gkt[0]), 4), "decode": round(float(gkt[1]), 4)},
+                    "rank0_step_breakdown_ms": breakdown,
+                    "note": "one workgroup per 4 MiB block: the encode time of a job of at most 256 blocks per GPU is the per-block latency at any N, "
+                            "so this curve is flat in encode by construction and carries two PCIe legs N = 1's device-resident step does not "
+                            "(DESIGN.md section 6); what shrinks with N is decode and the legs",
+                }
+            hc.close()
+            del d_shard, d_back, expect, sc
+            torch.cuda.empty_cache()
 
         # (1) the timed job of the line
         dt, comp_bytes, (enc_ms, enc_n, dec_ms, dec_n), _, oracle_equal = single_gpu_job(
-            1 + rank, args.steps, args.warmup, check_oracle=(rank == 0 and not args.no_oracle_check and not args.no_weak))
+            1 + rank, args.steps, args.warmup, check_oracle=(rank == 0 and args.full and not args.no_oracle_check and not args.no_weak),
+            dump_dir=args.dump_outputs if rank == 0 else None)
         kt = torch.tensor([enc_ms / max(enc_n, 1), dec_ms / max(dec_n, 1), float(comp_bytes)], dtype=torch.float64, device=red_dev)
         dist.all_reduce(kt, op=dist.ReduceOp.MAX)
         if rank == 0:
@@ -635,20 +703,9 @@ def main():
                              "frac": round(dom_gbs / HBM_PEAK_GBS, 6), "traffic": None, "traffic_source": "PMC summaries are collected at N = 1",
                              "algorithmic_bytes_per_launch": alg, "avg_launch_ms": round(dom_avg * 1e3, 4), "per": "GPU (slowest rank)"},
                 "slowest_rank_kernel_ms": {"encode": round(enc_avg * 1e3, 4), "decode": round(dec_avg * 1e3, 4)},
-                "config4_host_gather": {
-                    "what": f"BASELINE config 4: ONE {n} B job ({nb} blocks) block-sharded over {world} GPUs (block b -> rank b % {world}), one all-gather of "
-                            f"the u32 sizes per step, frames DMA'd to one container in host memory, barrier, owned frames back and decoded; both PCIe "
-                            f"legs inside the step, so this is never `value`",
-                    "scaling": "strong", "value": round(aggregate_value(n, gdt, gsteps), 4), "unit": "GB/s", "steps": gsteps, "warmup": gwarm,
-                    "ms_per_step": round(gdt / gsteps * 1e3, 3), "ratio": round(g_comp / n, 5), "container_equals_oracle": g_equal,
-                    "collective_backend": backend,
-                    "slowest_rank_kernel_ms": {"encode": round(float(gkt[0]), 4), "decode": round(float(gkt[1]), 4)},
-                    "rank0_step_breakdown_ms": breakdown,
-                    "note": "one workgroup per 4 MiB block: the encode time of a job of at most 256 blocks per GPU is the per-block latency at any N, "
-                            "so this curve is flat in encode by construction and carries two PCIe legs N = 1's device-resident step does not "
-                            "(DESIGN.md section 6); what shrinks with N is decode and the legs",
-                },
             }
+            if config4:
+                line["config4_host_gather"] = config4
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

@@ -2,6 +2,10 @@ import os
 import sys
 
 import pytest
+# torch brings its own HIP runtime, which the native library shares only when torch is loaded first (the library asks for
+# libamdhip64.so.7, torch's copy carries that soname; loaded the other way round, the process ends up with two HIP runtimes and
+# the library's sees no device).  CPU tests load the library without torch, so torch goes first for the whole session.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):

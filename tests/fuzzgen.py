@@ -2,7 +2,14 @@
 period-N runs, far offsets and block tails.  Shared by the oracle and GPU parity tests."""
 from __future__ import annotations
 
+import hashlib
+
 import numpy as np
+
+
+def stream_digest(b: bytes) -> int:
+    """64-bit BLAKE2b of a byte string (tests/golden/ref_streams.npz)."""
+    return int.from_bytes(hashlib.blake2b(b, digest_size=8).digest(), "little")
 
 
 def structured(rng: np.random.Generator, n: int) -> np.ndarray:
@@ -60,3 +67,25 @@ def structured(rng: np.random.Generator, n: int) -> np.ndarray:
     a = structured(rng, n // 2 + 1)
     b = structured(rng, n - n // 2 + 1)
     return np.concatenate([a, b])[:n]
+
+
+def oracle_vs_ref_small(n_cases: int):
+    """The cases of test_oracle_vs_ref.py::test_fuzz_small: (data, halo or None), seeded."""
+    rng = np.random.default_rng(12345)
+    for case in range(n_cases):
+        n = int(rng.integers(1, 3000)) if case % 10 else int(rng.integers(1, 40))
+        data = structured(rng, n).tobytes()
+        halo = rng.integers(0, 256, size=128, dtype=np.uint8).tobytes() if case % 3 else None
+        if halo is not None and case % 2:
+            halo = data[:128].ljust(128, b"\0")   # halo that continues the data: matches cross the end
+        yield data, halo
+
+
+def oracle_vs_ref_large():
+    """The cases of test_oracle_vs_ref.py::test_fuzz_large_blocks: (data, halo), seeded."""
+    rng = np.random.default_rng(99)
+    for case in range(6):
+        n = int(rng.integers(70000, 1 << 21)) if case else 1 << 22
+        data = structured(rng, n).tobytes()
+        halo = rng.integers(0, 256, size=128, dtype=np.uint8).tobytes()
+        yield data, halo

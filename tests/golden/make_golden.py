@@ -8,6 +8,8 @@ canonical conditions of SURVEY.md 8c.  Nothing here travels as reference source.
   <name>.in / .noext / .ext   small inputs and the reference's output streams
   manifest.json           sizes + FNV-1a64 of every fixture and of the larger known-answer
                           vectors (K3, K6) that are too big to commit
+  ref_streams.npz         length + digest (fuzzgen.stream_digest) of the reference's stream for every
+                          case of tests/test_oracle_vs_ref.py, and a digest of each case's input
 """
 import ast
 import json
@@ -23,6 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 
 from oracle.pyoracle import Oracle, Reference, build  # noqa: E402
+import fuzzgen  # noqa: E402
 import kat  # noqa: E402
 
 
@@ -76,7 +79,32 @@ def main() -> None:
             entry[tag] = {"bytes": len(out), "fnv": "%016x" % orc.fnv(out)}
         manifest[name] = entry
     json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
-    print("wrote", len(small), "fixtures +", "manifest.json")
+    write_ref_streams(ref)
+    print("wrote", len(small), "fixtures +", "manifest.json + ref_streams.npz")
+
+
+def write_ref_streams(ref) -> None:
+    """The reference's side of tests/test_oracle_vs_ref.py: for each group of cases, `<group>_len` and `<group>_digest`
+    [case, ext] of the reference's stream and `<group>_input` (digest of data + halo); every stream decodes back under the
+    reference."""
+    groups = {
+        "kat": [(bytes(kat.KATS[name][0]()), None) for name in sorted(kat.KATS)],
+        "small": list(fuzzgen.oracle_vs_ref_small(3000)),
+        "large": list(fuzzgen.oracle_vs_ref_large()),
+    }
+    arrays = {"kat_names": np.array(sorted(kat.KATS))}
+    for group, cases in groups.items():
+        lens = np.zeros((len(cases), 2), dtype=np.uint32)
+        digests = np.zeros((len(cases), 2), dtype=np.uint64)
+        inputs = np.zeros(len(cases), dtype=np.uint64)
+        for i, (data, halo) in enumerate(cases):
+            inputs[i] = fuzzgen.stream_digest(data + (halo or b""))
+            for ext in (0, 1):
+                out = ref.encode_block(data, ext, halo)
+                assert ref.decode_block(out, ext) == data, (group, i, ext)
+                lens[i, ext], digests[i, ext] = len(out), fuzzgen.stream_digest(out)
+        arrays.update({f"{group}_len": lens, f"{group}_digest": digests, f"{group}_input": inputs})
+    np.savez_compressed(os.path.join(HERE, "ref_streams.npz"), **arrays)
 
 
 if __name__ == "__main__":

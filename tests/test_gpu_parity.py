@@ -583,7 +583,7 @@ def test_bench_sharded_path_over_rccl_with_one_rank(tsq):
     """bench.py's N > 1 line -- process group on the nccl (= RCCL) backend, all-gather of the sizes on the GPU, one host container in
     /dev/shm registered with hipHostRegister, tsqa_sharded_place_async, tsqa_sharded_fetch_decode_async -- executed with a world of
     ONE rank (the box has one GPU); the host-gathered container is compared with the oracle's inside bench.py."""
-    r, line = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "300000000"],
+    r, line = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "300000000", "--full"],
                          dict(TSQ_BENCH_FORCE_SHARDED="1", TSQ_BENCH_BACKEND="nccl", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533",
                               RANK="0", LOCAL_RANK="0", WORLD_SIZE="1"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -599,7 +599,7 @@ def test_bench_gpus_2_typed_plainly_launches_two_ranks(tsq):
     with both ranks on the box's one GPU over gloo (TSQ_BENCH_SHARE_GPU / TSQ_BENCH_BACKEND: the dry run of a 1-GPU box).  The line's
     value is the weak-scaled one (two jobs), the config-4 section is the one job dealt b % 2 with its container equal to the
     oracle's (the flag used to be parsed and ignored)."""
-    r, line = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "150000000"],
+    r, line = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "150000000", "--full"],
                          dict(TSQ_BENCH_SHARE_GPU="1", TSQ_BENCH_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["process_group_world_size"] == 2 and len(line["devices"]) == 2

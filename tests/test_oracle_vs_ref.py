@@ -1,5 +1,7 @@
-"""Differential test: oracle/tsq_oracle.c vs the reference's own tsq_encode.cpp/tsq_decode.cpp
-(oracle/_ref/libtsq_ref.so).  Skipped where the reference build is absent.  CPU only."""
+"""Differential test: oracle/tsq_oracle.c vs the reference's own tsq_encode.cpp/tsq_decode.cpp.
+The reference's streams for these inputs are stored as length + digest in tests/golden/ref_streams.npz
+(tests/golden/make_golden.py, which also checked that every one decodes back under the reference), so the
+test needs no reference build.  CPU only."""
 import os
 
 import numpy as np
@@ -8,43 +10,49 @@ import pytest
 import fuzzgen
 import kat
 
+REF = np.load(os.path.join(kat.GOLDEN, "ref_streams.npz"))
+
+
+def assert_reference_stream(group, i, ext, stream):
+    """`stream` is byte for byte the reference's stream of case i of `group`."""
+    want = (int(REF[f"{group}_len"][i, ext]), int(REF[f"{group}_digest"][i, ext]))
+    assert (len(stream), fuzzgen.stream_digest(stream)) == want, (group, i, ext)
+
+
+def assert_input(group, i, data, halo):
+    assert fuzzgen.stream_digest(data + (halo or b"")) == int(REF[f"{group}_input"][i]), \
+        f"case {i} of {group}: not the input the stored reference streams were made from"
+
 
 @pytest.mark.parametrize("name", sorted(kat.KATS))
-def test_kat_bytes_equal_reference(oracle, reference, name):
+def test_kat_bytes_equal_reference(oracle, name):
+    i = list(REF["kat_names"]).index(name)
     data = bytes(kat.KATS[name][0]())
+    assert_input("kat", i, data, None)
     for ext in (0, 1):
         a = oracle.encode_block(data, ext)
-        b = reference.encode_block(data, ext)
-        assert a == b
-        assert reference.decode_block(a, ext) == data
+        assert_reference_stream("kat", i, ext, a)
+        back, st = oracle.decode_block(a, ext)
+        assert st == 0 and back == data
 
 
-def test_fuzz_small(oracle, reference):
+def test_fuzz_small(oracle):
     n_cases = int(os.environ.get("TSQ_FUZZ_CASES", "3000"))
-    rng = np.random.default_rng(12345)
-    for case in range(n_cases):
-        n = int(rng.integers(1, 3000)) if case % 10 else int(rng.integers(1, 40))
-        data = fuzzgen.structured(rng, n).tobytes()
-        halo = rng.integers(0, 256, size=128, dtype=np.uint8).tobytes() if case % 3 else None
-        if halo is not None and case % 2:
-            halo = data[:128].ljust(128, b"\0")   # halo that continues the data: matches cross the end
+    assert n_cases <= len(REF["small_len"]), f"reference streams are stored for {len(REF['small_len'])} cases"
+    for case, (data, halo) in enumerate(fuzzgen.oracle_vs_ref_small(n_cases)):
+        assert_input("small", case, data, halo)
         for ext in (0, 1):
             a = oracle.encode_block(data, ext, halo)
-            b = reference.encode_block(data, ext, halo)
-            assert a == b, (case, n, ext)
+            assert_reference_stream("small", case, ext, a)
             back, st = oracle.decode_block(a, ext)
-            assert st == 0 and back == data, (case, n, ext)
-            assert reference.decode_block(a, ext) == data
+            assert st == 0 and back == data, (case, len(data), ext)
 
 
-def test_fuzz_large_blocks(oracle, reference):
-    rng = np.random.default_rng(99)
-    for case in range(6):
-        n = int(rng.integers(70000, 1 << 21)) if case else 1 << 22
-        data = fuzzgen.structured(rng, n).tobytes()
-        halo = rng.integers(0, 256, size=128, dtype=np.uint8).tobytes()
+def test_fuzz_large_blocks(oracle):
+    for case, (data, halo) in enumerate(fuzzgen.oracle_vs_ref_large()):
+        assert_input("large", case, data, halo)
         for ext in (0, 1):
             a = oracle.encode_block(data, ext, halo)
-            assert a == reference.encode_block(data, ext, halo), (case, n, ext)
+            assert_reference_stream("large", case, ext, a)
             back, st = oracle.decode_block(a, ext)
             assert st == 0 and back == data

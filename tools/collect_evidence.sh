@@ -10,7 +10,7 @@ mkdir -p $OUT
 bash tools/profile_round.sh $TAG > $OUT/profile_round.log 2>&1
 # (bench.py takes roofline.traffic from the newest PMC summary under profiles/ that carries the running kernels' fingerprint: the one just made)
 cp $OUT/pmc_summary.json profiles/${TAG}_pmc_fetch_write.json
-(timeout 600 python bench.py --steps 10 --warmup 3 2>&1 | tail -1) > $OUT/bench.json
+(timeout 600 python bench.py --full --steps 10 --warmup 3 2>&1 | tail -1) > $OUT/bench.json
 python tools/phase_stats.py > $OUT/phase_stats.txt 2>&1
 (timeout 300 python tools/tile_trace.py 2>&1 | tail -60) > $OUT/tile_trace.txt
 python tools/traffic_experiment.py > $OUT/traffic_experiment.jsonl 2>/dev/null
@@ -45,8 +45,8 @@ for args in "--synthetic 1000000000 --reps 5 --no-ext" "--synthetic 1000000000 -
 tools/micro/lds_unaligned > $OUT/lds_access_costs.txt 2>&1
 # the N > 1 line on this 1-GPU box: `python bench.py --gpus N` typed plainly launches its N ranks itself; here they share GPU 0 over gloo (a dry run of the
 # code path, not a scaling measurement: N processes time-slice one GPU and one PCIe link)
-TSQ_BENCH_BACKEND=gloo TSQ_BENCH_SHARE_GPU=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 2>/dev/null | tail -1 > $OUT/bench_2ranks_1gpu.json
-TSQ_BENCH_BACKEND=gloo TSQ_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 8 --steps 2 --warmup 1 --size 2000000000 --ext 1 --kind mix 2>/dev/null | tail -1 > $OUT/bench_8ranks_1gpu.json
+TSQ_BENCH_BACKEND=gloo TSQ_BENCH_SHARE_GPU=1 timeout 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 2>/dev/null | tail -1 > $OUT/bench_2ranks_1gpu.json
+TSQ_BENCH_BACKEND=gloo TSQ_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus 8 --steps 2 --warmup 1 --size 2000000000 --ext 1 --kind mix 2>/dev/null | tail -1 > $OUT/bench_8ranks_1gpu.json
 (TSQ_AMD_DEBUG=1 timeout 200 tools/tsq_cli b --synthetic 1000000000 --reps 2 --no-ext 2>&1 | tail -45) > $OUT/cli_timeline.txt
 mkdir -p gpurun_out/x; bash tools/bottleneck.sh run > $OUT/bottleneck.txt 2>&1
 python tools/spin_counts.py > $OUT/spin_counts.txt 2>&1

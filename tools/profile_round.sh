@@ -9,8 +9,8 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 # (the extra bench sections -- ext1, config5, host_gather -- launch the same kernels at other sizes: left out of the profiled command)
-CMD="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
-PMC="python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+PMC="python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- $CMD > $OUT/stats_bench.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch --output-format csv -- $PMC > $OUT/fetch_bench.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write --output-format csv -- $PMC > $OUT/write_bench.log 2>&1
