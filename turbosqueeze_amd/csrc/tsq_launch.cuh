@@ -1,7 +1,7 @@
 // tsq_launch.cuh -- kernel selection and launch for the device context.
 //
 // The product library carries three kernel families: the staged encoder (tsq_enc_stage.cuh: fourteen working wavefronts per block, twelve in the lean layout; standard and lean
-// layouts, with and without extensions), the byte-lane decoder (tsq_dec_sym.cuh, tsq_dec_duo.cuh) and the serial correctness
+// layouts, with and without extensions), the byte-lane decoder (tsq_dec_sym.cuh, tsq_dec_duo.cuh; their phases in tsq_dec_common.cuh) and the serial correctness
 // baselines (tsq_serial.cuh, variant 1).  The previous round's production encoder (ab/tsq_enc_stage_r05.cuh, encoder variant 5) is
 // compiled only into the A/B library (`make ab`, -DTSQ_AB_VARIANTS), which tests/test_gpu_parity.py holds against the same oracle.
 #pragma once
