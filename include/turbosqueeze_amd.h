@@ -223,6 +223,46 @@ void tsqa_set_kernel_variant(tsqa_ctx *ctx, int encode_variant, int decode_varia
  * TSQA_ERR_STALL (default 2^24: seconds).  Tests set it to 1 to exercise the retry. */
 void tsqa_set_decode_wait_limit(tsqa_ctx *ctx, uint32_t polls);
 
+/*
+ * Range reads: bytes [offset, offset + length) of a container's uncompressed data, straight from the container in HBM.  Blocks
+ * are independent, so a read decodes only the blocks it touches, and each of them only up to the chunk that reaches the read's
+ * last byte there: its cost grows with how far the read reaches into its last block, not with the size of the container.
+ *
+ * tsqa_index_create: synchronous (on the context's own stream; the container's bytes must be in place).  Validates the container
+ *   (magic, block count, every frame, sizes that add up to the header's total) and keeps its frame table, on the device and a host
+ *   copy.  TSQA_ERR_FORMAT on a malformed container, and no index is made.  The index refers to the container: it must stay alive
+ *   and unchanged while the index is used.  An index belongs to the device of the context it was made on.
+ * tsqa_index_destroy: no read that uses the index may still be in flight.
+ */
+typedef struct tsqa_index tsqa_index;
+int      tsqa_index_create(tsqa_ctx *ctx, const void *d_container, size_t n, tsqa_index **out);
+void     tsqa_index_destroy(tsqa_index *idx);
+uint32_t tsqa_index_blocks(const tsqa_index *idx);   /* the container's block count (0 for NULL) */
+uint64_t tsqa_index_total(const tsqa_index *idx);    /* its uncompressed size (0 for NULL) */
+
+typedef struct tsqa_range { uint64_t offset, length, out_at; } tsqa_range;      /* bytes [offset, offset+length) -> d_out + out_at */
+typedef struct tsqa_range_item { uint32_t block, lo, hi, pad; uint64_t out_at; } tsqa_range_item;   /* block bytes [lo, hi) -> d_out + out_at */
+
+/* Host-only (no device): cut ranges into one item per block they touch, given the blocks' output starts out_start[0..n_blocks]
+ * (out_start[0] = 0, then the prefix sum of the blocks' lengths; a block may be shorter than TSQ_BLOCK_SZ anywhere).  Items come
+ * in range order; zero-length ranges give none.  *n_items = the item count.  TSQA_ERR_ARG, with nothing written to items, when a
+ * range ends past out_start[n_blocks], when out_at + length > out_cap, when the destinations of two ranges overlap, or when the
+ * items do not fit cap_items (*n_items then holds the count needed). */
+int tsqa_plan_ranges(const uint64_t *out_start, uint32_t n_blocks, const tsqa_range *ranges, uint32_t n_ranges,
+                     size_t out_cap, tsqa_range_item *items, uint32_t cap_items, uint32_t *n_items);
+
+/* Read the ranges (a host array) into d_out (out_cap bytes), on hip_stream (NULL = the context's own).  The ranges are planned
+ * (tsqa_plan_ranges) before anything is enqueued: argument errors are returned, and nothing is written.  *d_status (device int32)
+ * becomes nonzero (a TSQA_ERR_*) on a malformed stream.  The asynchronous form returns at once and may be called again on the
+ * same stream before the first has run.  tsqa_decompress_ranges waits and returns the status.
+ * Trust: a read reports TSQA_ERR_STREAM when a stream byte it consumed is malformed; damage that lies beyond the last chunk a read
+ * needs may go unreported.  A read of the whole range consumes every stream and agrees with tsqa_decompress_device.  Nothing
+ * outside the ranges' destinations is ever written. */
+int tsqa_decompress_ranges_async(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_range *ranges, uint32_t n_ranges,
+                                 void *d_out, size_t out_cap, int32_t *d_status, void *hip_stream);
+int tsqa_decompress_ranges(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_range *ranges, uint32_t n_ranges,
+                           void *d_out, size_t out_cap, void *hip_stream);
+
 /* =====================================================================================
  * (1) The reference API (turbosqueeze.h:441-674), C-callable subset
  * ================================================================================== */

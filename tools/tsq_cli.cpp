@@ -6,6 +6,10 @@
 //   tsq_cli b [file|--synthetic BYTES] [--no-ext] [--reps N]
 //                                           memory -> memory benchmark of the _MT API (host buffers, so
 //                                           PCIe transfers are INSIDE the timed region), wall clock, MB = 1e6 B.
+//   tsq_cli x <in.tsq> <offset> <length> <out>
+//                                           range read: the container goes to the device, an index is built
+//                                           (tsqa_index_create) and bytes [offset, offset + length) of its
+//                                           uncompressed data are read (tsqa_decompress_ranges) into <out>.
 // Unlike the reference's benchmark (clock() summed over threads, divided by 1e5) this reports
 // wall-clock MB/s.
 #include <chrono>
@@ -14,6 +18,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "turbosqueeze.h"
 
@@ -28,8 +34,46 @@ static double now_s()
 static int usage()
 {
     fprintf(stderr, "usage: tsq_cli c <in> <out> [--no-ext] | d <in> <out> | b [file | --synthetic BYTES] [--no-ext] [--reps N]\n"
-                    "       tsq_cli bf <in> <workdir> [--no-ext] [--reps N]   (file -> file -> file with warm contexts)\n");
+                    "       tsq_cli bf <in> <workdir> [--no-ext] [--reps N]   (file -> file -> file with warm contexts)\n"
+                    "       tsq_cli x <in.tsq> <offset> <length> <out>       (uncompressed bytes [offset, offset + length))\n");
     return 2;
+}
+
+// x: a range read straight from the container in device memory
+static int range_read(const std::string& in, uint64_t offset, uint64_t length, const std::string& out_path)
+{
+    FILE* f = fopen(in.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", in.c_str()); return 1; }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    std::vector<uint8_t> blob(sz > 0 ? (size_t)sz : 0);
+    const bool read_ok = fread(blob.data(), 1, blob.size(), f) == blob.size();
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "short read\n"); return 1; }
+    tsqa_ctx* ctx = nullptr;
+    if (tsqa_create(-1, &ctx) != TSQA_OK) { fprintf(stderr, "no usable MI355X (gfx950) device\n"); return 1; }
+    void *d_in = nullptr, *d_out = nullptr;
+    tsqa_index* idx = nullptr;
+    std::vector<uint8_t> got(length);
+    int rc = TSQA_OK;
+    if (hipMalloc(&d_in, blob.size() ? blob.size() : 1) != hipSuccess || hipMalloc(&d_out, length ? length : 1) != hipSuccess ||
+        hipMemcpy(d_in, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "device memory: %s\n", hipGetErrorString(hipGetLastError()));
+        rc = TSQA_ERR_HIP;
+    }
+    if (rc == TSQA_OK && (rc = tsqa_index_create(ctx, d_in, blob.size(), &idx)) == TSQA_OK) {
+        const tsqa_range r = {offset, length, 0};
+        rc = tsqa_decompress_ranges(ctx, idx, &r, 1, d_out, length, nullptr);
+    }
+    if (rc != TSQA_OK && rc != TSQA_ERR_HIP) fprintf(stderr, "range read failed (%d): %s\n", rc, tsqa_last_error(ctx));
+    if (rc == TSQA_OK && length && hipMemcpy(got.data(), d_out, length, hipMemcpyDeviceToHost) != hipSuccess) rc = TSQA_ERR_HIP;
+    tsqa_index_destroy(idx);
+    (void)hipFree(d_in); (void)hipFree(d_out);
+    tsqa_destroy(ctx);
+    if (rc != TSQA_OK) return 1;
+    FILE* o = fopen(out_path.c_str(), "wb");
+    if (!o || fwrite(got.data(), 1, got.size(), o) != got.size()) { fprintf(stderr, "cannot write %s\n", out_path.c_str()); if (o) fclose(o); return 1; }
+    fclose(o);
+    return 0;
 }
 
 int main(int argc, char** argv)
@@ -65,6 +109,10 @@ int main(int argc, char** argv)
         }
         fprintf(stderr, "%s: %s in %.3f s\n", mode == "c" ? "compress" : "decompress", ok ? "ok" : "FAILED", now_s() - t0);
         return ok ? 0 : 1;
+    }
+    if (mode == "x") {
+        if (pos.size() != 4) return usage();
+        return range_read(pos[0], strtoull(pos[1].c_str(), nullptr, 10), strtoull(pos[2].c_str(), nullptr, 10), pos[3]);
     }
     if (mode == "bf") {
         // file -> .tsq file -> file through the _MT API's file modes with the contexts allocated once (as sample/main.cpp:71-95 keeps

@@ -8,12 +8,16 @@ from .api import (  # noqa: F401
     BLOCK_SZ,
     OUTPUT_SZ,
     DeviceCodec,
+    Range,
+    RangeIndex,
+    RangeItem,
     TsqError,
     build_info,
     build_native,
     container_bound,
     lib,
     lib_path,
+    plan_ranges,
     source_fingerprint,
     tsq_compress_mt,
     tsq_decode,

@@ -155,12 +155,136 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_copy_probe_shape.argtypes = [vp]
     L.tsqa_measure_copy.restype = C.c_int
     L.tsqa_measure_copy.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.tsqa_index_create.restype = C.c_int
+    L.tsqa_index_create.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+    L.tsqa_index_destroy.restype = None
+    L.tsqa_index_destroy.argtypes = [vp]
+    L.tsqa_index_blocks.restype = C.c_uint32
+    L.tsqa_index_blocks.argtypes = [vp]
+    L.tsqa_index_total.restype = C.c_uint64
+    L.tsqa_index_total.argtypes = [vp]
+    L.tsqa_plan_ranges.restype = C.c_int
+    L.tsqa_plan_ranges.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_size_t, vp, C.c_uint32, u32p]
+    L.tsqa_decompress_ranges_async.restype = C.c_int
+    L.tsqa_decompress_ranges_async.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
+    L.tsqa_decompress_ranges.restype = C.c_int
+    L.tsqa_decompress_ranges.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
     L.tsqCompress.restype = None
     L.tsqCompress.argtypes = [vp, vp, C.c_bool, C.c_uint32]
     L.tsqDecompress.restype = None
     L.tsqDecompress.argtypes = [vp, vp]
     _libs[ab] = L
     return L
+
+
+class Range(C.Structure):
+    """tsqa_range: uncompressed bytes [offset, offset + length) -> d_out + out_at"""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
+
+
+class RangeItem(C.Structure):
+    """tsqa_range_item: bytes [lo, hi) of block `block` -> d_out + out_at"""
+    _fields_ = [("block", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("pad", C.c_uint32), ("out_at", C.c_uint64)]
+
+
+def _range_array(ranges):
+    """(offset, length, out_at) triples -> a ctypes tsqa_range array"""
+    arr = (Range * max(len(ranges), 1))()
+    for k, (off, ln, at) in enumerate(ranges):
+        arr[k] = Range(int(off), int(ln), int(at))
+    return arr
+
+
+def plan_ranges(out_start, ranges, out_cap: int, cap_items=None):
+    """tsqa_plan_ranges (host only): out_start = the blocks' output starts, then the total; ranges = (offset, length, out_at)
+    triples.  -> list of (block, lo, hi, out_at).  Raises TsqError(3) when the call is refused."""
+    import numpy as np
+    starts = np.ascontiguousarray(out_start, dtype=np.uint64)
+    rr = _range_array(ranges)
+    n = C.c_uint32(0)
+    if cap_items is None:
+        rc = lib().tsqa_plan_ranges(starts.ctypes.data, starts.size - 1, rr, len(ranges), out_cap, None, 0, C.byref(n))
+        if rc and n.value == 0:
+            raise TsqError(rc, "tsqa_plan_ranges refused the ranges")
+        cap_items = n.value
+    items = (RangeItem * max(cap_items, 1))()
+    rc = lib().tsqa_plan_ranges(starts.ctypes.data, starts.size - 1, rr, len(ranges), out_cap, items, cap_items, C.byref(n))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_ranges refused the ranges")
+    return [(items[k].block, items[k].lo, items[k].hi, items[k].out_at) for k in range(n.value)]
+
+
+class RangeIndex:
+    """The frame table of a device-resident .tsq container (tsqa_index_create), for reads of byte ranges of its uncompressed data.
+    Holds a reference to the container tensor, which must not change while the index is used."""
+
+    def __init__(self, codec: "DeviceCodec", blob):
+        self.codec, self.blob, self.L = codec, blob, codec.L
+        self.h = C.c_void_p()
+        # the index is made on the context's own stream: whatever the current stream still writes to the container comes first
+        codec.torch.cuda.current_stream(codec.device).synchronize()
+        rc = self.L.tsqa_index_create(codec.h, blob.data_ptr(), blob.numel(), C.byref(self.h))
+        if rc:
+            raise codec._err(rc)
+        self.n_blocks = int(self.L.tsqa_index_blocks(self.h))
+        self.total = int(self.L.tsqa_index_total(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.tsqa_index_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _out(self, out, n):
+        if out is None:
+            return self.codec.torch.empty(max(n, 1), dtype=self.codec.torch.uint8, device=self.codec.device)
+        if out.dtype != self.codec.torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise TsqError(3, "out must be a contiguous uint8 CUDA tensor")
+        return out
+
+    def read_into(self, ranges, out, sync: bool = True) -> None:
+        """The raw call: ranges = (offset, length, out_at) triples, bytes land at out[out_at:].  sync=False: on the current stream,
+        nothing waited for, the status in codec.status()."""
+        rr = _range_array(ranges)
+        if sync:
+            rc = self.L.tsqa_decompress_ranges(self.codec.h, self.h, rr, len(ranges), out.data_ptr(), out.numel(), self.codec._stream())
+        else:
+            rc = self.L.tsqa_decompress_ranges_async(self.codec.h, self.h, rr, len(ranges), out.data_ptr(), out.numel(),
+                                                     self.codec._status.data_ptr(), self.codec._stream())
+        if rc:
+            raise self.codec._err(rc)
+
+    def read(self, offset: int, length: int, out=None):
+        """Bytes [offset, offset + length) of the uncompressed data -> a uint8 CUDA tensor (out[:length] when out is given)."""
+        out = self._out(out, length)
+        self.read_into([(offset, length, 0)], out)
+        return out[:length]
+
+    def _packed(self, ranges, out):
+        at, triples = 0, []
+        for off, ln in ranges:
+            triples.append((off, ln, at))
+            at += int(ln)
+        out = self._out(out, at)
+        return triples, out, [out[a:a + int(ln)] for (_, ln, a) in triples]
+
+    def read_many(self, ranges, out=None):
+        """One call for many (offset, length) ranges, packed back to back.  -> (packed tensor, per-range views into it)."""
+        triples, out, views = self._packed(ranges, out)
+        self.read_into(triples, out)
+        return out[:sum(int(ln) for _, ln in ranges)], views
+
+    def read_many_async(self, ranges, out=None):
+        """read_many on the current torch stream, nothing waited for (like DeviceCodec.decompress_async): the status lands in
+        codec.status()."""
+        triples, out, views = self._packed(ranges, out)
+        self.read_into(triples, out, sync=False)
+        return out[:sum(int(ln) for _, ln in ranges)], views
 
 
 DONE_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_bool, C.c_void_p)
@@ -337,6 +461,10 @@ class DeviceCodec:
 
     def last_size_status(self):
         return int(self._size.item()), int(self._status.item())
+
+    def index(self, blob) -> RangeIndex:
+        """An index of the .tsq container `blob` (uint8 CUDA tensor) for range reads: index(blob).read(offset, length)."""
+        return RangeIndex(self, blob)
 
 
 # ---------------------------------------------------------------------------

@@ -15,10 +15,10 @@
 //       (c) every byte fetches its value from the stream buffer or the ring of previous output -- or, when its source lies in this
 //       same chunk, a pointer to it, (d) asynchronous pointer jumping resolves those pointers, (e) the bytes go to the ring: the
 //       chunk is composed IN the ring (77 KiB of LDS: 64 KiB of history + the chunk being built).
-//   P7  the chunk's bytes go from the ring to HBM with aligned 16-byte stores.
+//   P7  the chunk's bytes go from the ring to HBM with aligned 16-byte stores (a range read: only those inside its window).
 //
-// dec_sym_kernel (tsq_dec_sym.cuh) runs all of them on one workgroup per block; dec_duo_kernel (tsq_dec_duo.cuh) runs P0..P4 on
-// PARSE workgroups and P5, P7 on a COPY workgroup.  The kernels are schedules: they call the phases in their own order and keep
+// dec_sym_kernel (tsq_dec_sym.cuh) runs all of them on one workgroup per block (dec_range_kernel the same, inside a window);
+// dec_duo_kernel (tsq_dec_duo.cuh) runs P0..P4 on PARSE workgroups and P5, P7 on a COPY workgroup.  The kernels are schedules: they call the phases in their own order and keep
 // their waits, hand-overs and error exits to themselves.  The LDS layout is a template parameter L (SymLds, DuoCopyLds): every
 // layout names its regions sbuf, recw, ent, plist, wsum, misc and ring; P1..P4 also use j1 .. j16, gstart, glen, gout, pairs and sn.
 // misc[0] super nodes, [1] groups in chunk, [2] first group over the image budget, [3] group that completes the block, [4] error,
@@ -541,6 +541,20 @@ __device__ __forceinline__ void flush_image(const uint8_t* lds, uint8_t* out, co
     }
     const uint32_t tail_at = hb + (words << 4);
     if (t < im.len - tail_at) { uint32_t a = ra + (words << 4) + t; a -= a >= C::R ? C::R : 0u; out[im.op + tail_at + t] = ring[a]; }
+}
+
+// ---------------- P7 of a range read: only the image's bytes in the window [lo, hi) of the block are written, byte p to out[p - lo].
+// out - lo is the block's virtual base (oskew is taken from it), so the clipped image keeps its ring words on HBM words: aligned
+// 16-byte stores in the middle, single bytes at the edges (flush_image on the clipped image).
+template <class L>
+__device__ __forceinline__ void flush_window(const uint8_t* lds, uint8_t* out, const Image& im, uint32_t lo, uint32_t hi, uint32_t first_tid,
+                                             uint32_t n_threads)
+{
+    using C = SymCfg;
+    const uint32_t a = im.op > lo ? im.op : lo, b = im.op + im.len < hi ? im.op + im.len : hi;
+    if (a >= b) return;
+    uint32_t at = im.at + (a - im.op); at -= at >= C::R ? C::R : 0u;
+    flush_image<L>(lds, out, Image{a - lo, b - a, at}, first_tid, n_threads);
 }
 
 }  // namespace tsq

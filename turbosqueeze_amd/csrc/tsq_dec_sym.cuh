@@ -34,8 +34,19 @@ struct SymLds {
 };
 static_assert(SymLds::total <= 160 * 1024, "LDS budget");
 
-__global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
-                                                       uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
+// One item of a range read (tsqa_range_item): output bytes [lo, hi) of block `block` go to out + out_at (byte lo lands there).
+struct RangeItem {
+    uint32_t block, lo, hi, pad;
+    uint64_t out_at;
+};
+
+// The decoder of one block on one workgroup.  kWindow = false (dec_sym_kernel): block blockIdx.x, whole.  kWindow = true
+// (dec_range_kernel): item blockIdx.x -- only the bytes [lo, hi) of its block are written, and the chunk loop ends with the chunk
+// that reaches hi.  Every chunk that is decoded is validated as in the whole-block decode.  (The pointers carry no __restrict__ here:
+// the kernels' own parameters do, and restrict parameters of an inlined function would give dec_sym_kernel other code than before.)
+template <bool kWindow>
+__device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
+                                                 uint8_t* outbuf, int32_t* status)
 {
     using C = SymCfg;
     using L = SymLds;
@@ -51,18 +62,31 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
     if (tid == 0) misc[11] = (uint32_t)*status;
     __syncthreads();
     if (misc[11] != 0u) return;
-    const FrameInfo f = frames[blockIdx.x];
+    // window: the item's block and its bytes [lo, hi); the whole block otherwise
+    uint32_t blk = blockIdx.x, lo = 0, hi = 0;
+    uint64_t out_at = 0;
+    if constexpr (kWindow) {
+        const RangeItem it = items[blockIdx.x];
+        if (it.block >= n_frames) {
+            if (tid == 0) atomicMax(status, kErrStream);
+            return;
+        }
+        blk = it.block; lo = it.lo; hi = it.hi; out_at = it.out_at;
+    }
+    const FrameInfo f = frames[blk];
     // The descriptor may come straight from an untrusted container (tsqa_decode_blocks_async): a stream shorter than its 3-byte
     // header, longer than a block slot, or an output longer than a block is refused before anything is read through it.
-    if (f.stream_len < 3u || f.stream_len > kSlotSize || f.out_len > kBlockSize) {
+    if (f.stream_len < 3u || f.stream_len > kSlotSize || f.out_len > kBlockSize || (kWindow && (lo >= hi || hi > f.out_len))) {
         if (tid == 0) atomicMax(status, kErrStream);
         return;
     }
     const uint8_t* const in = container + f.stream_at;
-    uint8_t* const out = outbuf + f.out_at;
+    // window: `out` is where byte lo goes; byte p of the block goes to out + (p - lo)
+    uint8_t* const out = outbuf + (kWindow ? out_at : f.out_at);
     const uint32_t in_len = f.stream_len, size = f.out_len, ext = f.ext;
-    // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM
-    const uint32_t oskew = (uint32_t)((uintptr_t)out & 15u);
+    // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM (window: of
+    // the block's virtual base out - lo)
+    const uint32_t oskew = (uint32_t)(((uintptr_t)out - lo) & 15u);
 
 #ifdef TSQ_STATS
     const uint32_t lane = tid & 63u, wid = tid >> 6;
@@ -100,7 +124,10 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
         // ---------------- P4.  The upper half of the workgroup has no group to look after: it writes the PREVIOUS chunk's bytes to
         // HBM meanwhile (P7).  (measured in round 5: a build without this flush runs 4.558 against 4.553 ms, the flush beside P3's
         // chain instead 4.572 -- it hides completely)
-        if (tid >= C::T / 2) flush_image<L>(lds, out, prev, C::T / 2, C::T / 2);
+        if (tid >= C::T / 2) {
+            if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
+            else flush_image<L>(lds, out, prev, C::T / 2, C::T / 2);
+        }
         group_lanes<L>(lds, nsn, slim, op, size, ext);
         // the doubling tables are dead from here on (every lane is past its last look-up in them): the record words of P5, which lie
         // over them, are cleared now, under the barrier that is needed anyway
@@ -113,8 +140,10 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
             return;
         }
         const Image im = {op, e.next_op - op, ring_op};
+        // (window: the chunk that reaches hi is the last one decoded)
+        const bool more = !e.last && !(kWindow && e.next_op >= hi);
         // the next chunk's stream is on its way while this one is copied
-        if (!e.last) pre = prefetch_words(in, next_sp, in_len - next_sp);
+        if (more) pre = prefetch_words(in, next_sp, in_len - next_sp);
         TSQD_ACC(4);
 
         // ---------------- P5: symbols -> bytes
@@ -128,7 +157,7 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
         TSQD_ACC(6);
         // the NEXT chunk's stream goes to LDS now (P0 of chunk k + 1): the byte fetch that the barrier above closed was the last reader
         // of the stream buffer (the literal bytes), and the words were requested behind P4, a dozen thousand cycles ago
-        if (!e.last) { stage_words<L>(lds, in, next_sp, in_len - next_sp, pre); staged_ahead = true; }
+        if (more) { stage_words<L>(lds, in, next_sp, in_len - next_sp, pre); staged_ahead = true; }
 #ifdef TSQ_STATS
         const unsigned long long wj0_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -152,14 +181,28 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
         op = e.next_op;
         sp = next_sp;
         TSQD_ACC(8);
-        if (e.last) break;
+        if (!more) break;
     }
     __syncthreads();
-    flush_image<L>(lds, out, prev, 0, C::T);
+    if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
+    else flush_image<L>(lds, out, prev, 0, C::T);
 #ifdef TSQ_STATS
     if (blockIdx.x == 0 && tid == 0) for (int q = 0; q < 16; ++q) g_dec_stats[q] = st_[q];
     if (blockIdx.x == 0 && lane == 0) for (int q = 0; q < 3; ++q) g_dec_wave[wid * 3 + q] = wj_[q];
 #endif
+}
+
+__global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                       uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
+{
+    sym_decode_block<false>(container, frames, 0u, nullptr, outbuf, status);
+}
+
+// Range reads (tsqa_decompress_ranges_async): one workgroup per item; nothing outside [out_at, out_at + hi - lo) of `outbuf` is written.
+__global__ __launch_bounds__(1024) void dec_range_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames, uint32_t n_frames,
+                                                         const RangeItem* __restrict__ items, uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
+{
+    sym_decode_block<true>(container, frames, n_frames, items, outbuf, status);
 }
 
 }  // namespace tsq

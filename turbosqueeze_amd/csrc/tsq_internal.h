@@ -33,6 +33,14 @@ struct tsqa_ctx {
     const void* sharded_streams = nullptr;
     void* sharded_out = nullptr;
     void forget_sharded() { sharded_n_local = 0; sharded_streams = nullptr; sharded_out = nullptr; }
+    // range reads: two slots, used in turn, of items planned on the host (pinned) and their copy on the device.  A slot is reused
+    // once the read that used it has finished (items_done[k], recorded behind its kernel): two reads can be in flight.
+    tsqa_range_item* host_items[2] = {nullptr, nullptr};
+    tsqa_range_item* range_items[2] = {nullptr, nullptr};
+    size_t cap_items[2] = {0, 0};
+    hipEvent_t items_done[2] = {nullptr, nullptr};
+    bool items_pending[2] = {false, false};
+    int items_slot = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     uint32_t* duo_ring = nullptr;      // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     uint32_t* duo_flags = nullptr;     // and their progress counters
@@ -56,6 +64,7 @@ struct tsqa_ctx {
     int reserve(size_t n_blocks, bool want_tables, bool want_slots = true);
     int reserve_duo(size_t n_blocks);
     int reserve_host_frames(size_t n);
+    int reserve_range_items(size_t n, int* slot);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]
@@ -66,4 +75,16 @@ struct tsqa_ctx {
     int launch_decode_frames(const void* d_streams, const tsq::FrameInfo* d_frames, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant = -1);
     int launch_pack(size_t n, uint32_t ext, void* d_out, size_t out_cap, uint64_t* d_out_size, int32_t* status, hipStream_t s);
     int launch_decode(const void* d_container, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant = -1);
+};
+
+// A container's frame table, kept for range reads (tsqa_index_create).  The container itself is the caller's.
+struct tsqa_index {
+    int device = 0;
+    const uint8_t* container = nullptr;
+    size_t n = 0;
+    uint32_t n_blocks = 0;
+    uint64_t total = 0;
+    tsq::FrameInfo* frames = nullptr;          // n_blocks descriptors on the device (frame_walk_kernel)
+    std::vector<tsqa_frame> host_frames;       // their host copy
+    std::vector<uint64_t> out_start;           // n_blocks + 1: where each block's output starts, then the total
 };

@@ -138,4 +138,18 @@ inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const Fr
     return 0;
 }
 
+// Range reads: one workgroup per item (dec_range_kernel), at any item count.  The items are in device memory.
+inline int launch_range_kernel(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
+                               uint32_t n_items, uint8_t* out, int32_t* status, hipStream_t s)
+{
+    static std::atomic<uint64_t> attr_devices{0};
+    {
+        const void* const fns[1] = {reinterpret_cast<const void*>(dec_range_kernel)};
+        const uint32_t bytes[1] = {SymLds::total};
+        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
+    }
+    hipLaunchKernelGGL(dec_range_kernel, dim3(n_items), dim3(SymCfg::T), SymLds::total, s, container, frames, n_frames, items, out, status);
+    return 0;
+}
+
 }  // namespace tsq

@@ -12,6 +12,7 @@
 #include "tsq_serial.cuh"
 #include "tsq_launch.cuh"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -134,6 +135,11 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     (void)hipFree(c->duo_ring); (void)hipFree(c->duo_flags);
     if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
+    for (int k = 0; k < 2; ++k) {
+        (void)hipFree(c->range_items[k]);
+        if (c->host_items[k]) (void)hipHostFree(c->host_items[k]);
+        if (c->items_done[k]) (void)hipEventDestroy(c->items_done[k]);
+    }
     delete c;
 }
 
@@ -203,6 +209,27 @@ int tsqa_ctx::reserve_host_frames(size_t n)
         cap_host_frames = want;
     }
     host_frame_src.resize(cap_host_frames);
+    return TSQA_OK;
+}
+
+// Range-read items: the next of the two slots, once the read that used it last has finished, grown on demand.
+int tsqa_ctx::reserve_range_items(size_t n, int* slot)
+{
+    (void)hipSetDevice(device);
+    const int k = items_slot;
+    items_slot ^= 1;
+    if (items_pending[k]) { (void)hipEventSynchronize(items_done[k]); items_pending[k] = false; }
+    if (!items_done[k]) TSQ_HIP(this, hipEventCreateWithFlags(&items_done[k], hipEventDisableTiming));
+    if (n > cap_items[k]) {
+        if (host_items[k]) (void)hipHostFree(host_items[k]);
+        (void)hipFree(range_items[k]);
+        host_items[k] = nullptr; range_items[k] = nullptr; cap_items[k] = 0;
+        size_t want = 256; while (want < n) want *= 2;
+        TSQ_HIP(this, hipHostMalloc(reinterpret_cast<void**>(&host_items[k]), want * sizeof(tsqa_range_item), hipHostMallocDefault));
+        TSQ_HIP(this, hipMalloc(&range_items[k], want * sizeof(tsqa_range_item)));
+        cap_items[k] = want;
+    }
+    *slot = k;
     return TSQA_OK;
 }
 
@@ -645,6 +672,166 @@ extern "C" int tsqa_sharded_decode_again_async(tsqa_ctx* c, const void* d_stream
     (void)hipSetDevice(c->device);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     return c->launch_decode_frames(d_streams, c->frames, c->sharded_n_local, d_out, d_status, s, 4);
+}
+
+// ---- range reads: an index of a device-resident container, and reads of byte ranges of its uncompressed data ----
+
+extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n, tsqa_index** out)
+{
+    if (!out) return TSQA_ERR_ARG;
+    *out = nullptr;
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_container) { c->set_error("index_create: null container"); return TSQA_ERR_ARG; }
+    if (n < 16) { c->set_error("index_create: a container of %zu B has no header", n); return TSQA_ERR_FORMAT; }
+    (void)hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    uint8_t head[16];
+    TSQ_HIP(c, hipMemcpyAsync(head, d_container, 16, hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    uint32_t nb; uint64_t total;
+    memcpy(&nb, head + 4, 4); memcpy(&total, head + 8, 8);
+    // the reader's bounds (tsq_compat.hip): every frame takes at least 6 bytes, every block at most TSQ_BLOCK_SZ of output
+    if (memcmp(head, "TSQ1", 4) != 0) { c->set_error("index_create: bad magic"); return TSQA_ERR_FORMAT; }
+    if (nb == 0 || (size_t)nb > (n - 16) / 6) { c->set_error("index_create: bad block count %u", nb); return TSQA_ERR_FORMAT; }
+    if (total > (uint64_t)nb * kBlockSize) { c->set_error("index_create: total %llu larger than %u blocks", (unsigned long long)total, nb); return TSQA_ERR_FORMAT; }
+    tsqa_index* idx = new (std::nothrow) tsqa_index();
+    if (!idx) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
+    idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = total;
+    int rc = TSQA_OK;
+    int32_t st = 0;
+    try {
+        idx->host_frames.resize(nb);
+        idx->out_start.resize((size_t)nb + 1);
+    } catch (...) { rc = TSQA_ERR_ARG; c->set_error("index_create: out of host memory"); }
+    // the frame walk of a full decompress, into the index's own descriptors (the context's are left alone)
+    auto walk = [&]() -> int {
+        TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)nb * sizeof(FrameInfo)));
+        TSQ_HIP(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t), s));
+        hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, idx->container, (uint64_t)n, nb, total, idx->frames, c->d_size, c->d_status);
+        TSQ_HIP(c, hipGetLastError());
+        TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipMemcpyAsync(idx->host_frames.data(), idx->frames, (size_t)nb * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipStreamSynchronize(s));
+        return TSQA_OK;
+    };
+    if (rc == TSQA_OK) rc = walk();
+    if (rc == TSQA_OK && st != 0) { c->set_error("index_create: malformed container (status %d)", st); rc = TSQA_ERR_FORMAT; }
+    if (rc != TSQA_OK) { tsqa_index_destroy(idx); return rc; }
+    for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = idx->host_frames[b].out_at;
+    idx->out_start[nb] = total;
+    *out = idx;
+    return TSQA_OK;
+}
+
+extern "C" void tsqa_index_destroy(tsqa_index* idx)
+{
+    if (!idx) return;
+    (void)hipSetDevice(idx->device);
+    (void)hipFree(idx->frames);
+    delete idx;
+}
+
+extern "C" uint32_t tsqa_index_blocks(const tsqa_index* idx) { return idx ? idx->n_blocks : 0u; }
+extern "C" uint64_t tsqa_index_total(const tsqa_index* idx) { return idx ? idx->total : 0ull; }
+
+// tsqa_plan_ranges, with the reason for a refusal.  count_only: validate and count, write no item.
+static int plan_ranges(const uint64_t* out_start, uint32_t nb, const tsqa_range* r, uint32_t nr, size_t out_cap, tsqa_range_item* items,
+                       uint32_t cap_items, uint32_t* n_items, const char** why, bool count_only = false)
+{
+    *why = "";
+    if (!out_start || !n_items || (nr && !r) || nb == 0) { *why = "null pointer or no blocks"; return TSQA_ERR_ARG; }
+    if (out_start[0] != 0) { *why = "out_start[0] is not 0"; return TSQA_ERR_ARG; }
+    for (uint32_t b = 0; b < nb; ++b)
+        if (out_start[b + 1] < out_start[b] || out_start[b + 1] - out_start[b] > kBlockSize) { *why = "a block is longer than TSQ_BLOCK_SZ"; return TSQA_ERR_ARG; }
+    const uint64_t total = out_start[nb];
+    // the first block of a range: the last one that starts at or before its offset (blocks of length 0 are passed over)
+    auto first_block = [&](uint64_t at) -> uint32_t { return (uint32_t)(std::upper_bound(out_start, out_start + nb + 1, at) - out_start) - 1u; };
+    std::vector<std::pair<uint64_t, uint64_t>> dst;
+    uint64_t count = 0;
+    for (uint32_t k = 0; k < nr; ++k) {
+        const tsqa_range& x = r[k];
+        if (x.length == 0) continue;
+        if (x.length > total || x.offset > total - x.length) { *why = "a range ends past the total"; return TSQA_ERR_ARG; }
+        if (x.length > out_cap || x.out_at > out_cap - x.length) { *why = "a range does not fit the output"; return TSQA_ERR_ARG; }
+        dst.emplace_back(x.out_at, x.length);
+        const uint64_t end = x.offset + x.length;
+        for (uint32_t b = first_block(x.offset); b < nb && out_start[b] < end; ++b) count += out_start[b + 1] > out_start[b];
+    }
+    // two workgroups writing the same bytes would race: destinations may touch, not overlap
+    std::sort(dst.begin(), dst.end());
+    for (size_t k = 1; k < dst.size(); ++k)
+        if (dst[k - 1].first + dst[k - 1].second > dst[k].first) { *why = "the destinations of two ranges overlap"; return TSQA_ERR_ARG; }
+    if (count > 0xFFFFFFFFull) { *why = "more than 2^32 - 1 items"; return TSQA_ERR_ARG; }
+    *n_items = (uint32_t)count;
+    if (count_only) return TSQA_OK;
+    if (count > cap_items) { *why = "the items do not fit cap_items"; return TSQA_ERR_ARG; }
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < nr; ++k) {
+        const tsqa_range& x = r[k];
+        if (x.length == 0) continue;
+        const uint64_t end = x.offset + x.length;
+        for (uint32_t b = first_block(x.offset); b < nb && out_start[b] < end; ++b) {
+            const uint64_t a = x.offset > out_start[b] ? x.offset : out_start[b], e = end < out_start[b + 1] ? end : out_start[b + 1];
+            if (a >= e) continue;
+            items[m++] = tsqa_range_item{b, (uint32_t)(a - out_start[b]), (uint32_t)(e - out_start[b]), 0u, x.out_at + (a - x.offset)};
+        }
+    }
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_plan_ranges(const uint64_t* out_start, uint32_t n_blocks, const tsqa_range* ranges, uint32_t n_ranges, size_t out_cap,
+                                tsqa_range_item* items, uint32_t cap_items, uint32_t* n_items)
+{
+    const char* why;
+    if (!items && cap_items) return TSQA_ERR_ARG;
+    return plan_ranges(out_start, n_blocks, ranges, n_ranges, out_cap, items, cap_items, n_items, &why);
+}
+
+extern "C" int tsqa_decompress_ranges_async(tsqa_ctx* c, const tsqa_index* idx, const tsqa_range* ranges, uint32_t n_ranges, void* d_out,
+                                            size_t out_cap, int32_t* d_status, void* hip_stream)
+{
+    static_assert(sizeof(tsqa_range_item) == sizeof(RangeItem), "public range item = kernel range item");
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_out || !d_status || (n_ranges && !ranges)) { c->set_error("decompress_ranges: null pointer"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("decompress_ranges: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    const char* why;
+    uint32_t n_items = 0;
+    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, nullptr, 0, &n_items, &why, true)) {
+        c->set_error("decompress_ranges: %s", why);
+        return TSQA_ERR_ARG;
+    }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    (void)hipSetDevice(c->device);
+    int k = 0;
+    if (int rc = c->reserve_range_items(n_items ? n_items : 1, &k)) return rc;
+    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, c->host_items[k], (uint32_t)c->cap_items[k], &n_items, &why)) {
+        c->set_error("decompress_ranges: %s", why);
+        return TSQA_ERR_ARG;
+    }
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    if (n_items == 0) return TSQA_OK;
+    TSQ_HIP(c, hipMemcpyAsync(c->range_items[k], c->host_items[k], (size_t)n_items * sizeof(tsqa_range_item), hipMemcpyHostToDevice, s));
+    const int rc = launch_range_kernel(c, idx->container, idx->frames, idx->n_blocks, reinterpret_cast<const RangeItem*>(c->range_items[k]),
+                                       n_items, static_cast<uint8_t*>(d_out), d_status, s);
+    // (behind the kernel: neither copy of the items is touched again before the read that uses them has finished)
+    TSQ_HIP(c, hipEventRecord(c->items_done[k], s));
+    c->items_pending[k] = true;
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_ranges(tsqa_ctx* c, const tsqa_index* idx, const tsqa_range* ranges, uint32_t n_ranges, void* d_out,
+                                      size_t out_cap, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    int rc = tsqa_decompress_ranges_async(c, idx, ranges, n_ranges, d_out, out_cap, c->d_status, s);
+    if (rc) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "decompress_ranges");
 }
 
 // ---- the second roofline denominator: what a plain device copy reaches on this GPU ----
