@@ -15,6 +15,7 @@
 // (D2H + append + progress callbacks); decompression has its own drainer thread.
 #include "tsq_internal.h"
 #include "tsq_common.cuh"
+#include "tsq_format.h"
 
 #include "../../include/turbosqueeze.h"
 
@@ -632,10 +633,9 @@ private:
             return false;
         }
 
-        uint8_t header[16];                                          // tsq_threads.cpp:333-335,355-359
-        memcpy(header, "TSQ1", 4); memcpy(header + 4, &nb, 4);
-        uint64_t t64 = total; memcpy(header + 8, &t64, 8);
-        sink.write(header, 16);
+        uint8_t header[tsq::kHeaderSize];                            // tsq_threads.cpp:333-335,355-359
+        tsq::write_header(header, nb, total);
+        sink.write(header, sizeof(header));
 
         bool ok = true;
         std::deque<InFlight> fly;
@@ -752,21 +752,20 @@ private:
             if (verbose_ && j.infile) printf("Error opening input file: %s\n", reinterpret_cast<const char*>(j.in));   // tsq_threads.cpp:714-717
             return false;
         }
-        uint8_t header[16];
-        if (src.read_at(0, 16, header) != 16 || memcmp(header, "TSQ1", 4) != 0) {              // tsq_threads.cpp:732-752
+        uint8_t header[tsq::kHeaderSize];
+        uint32_t nb = 0; uint64_t total = 0;
+        const int h = src.read_at(0, sizeof(header), header) == sizeof(header) ? tsq::read_header(header, src.size, &nb, &total) : tsq::kHeaderBadMagic;
+        if (h == tsq::kHeaderBadMagic) {                                                       // tsq_threads.cpp:732-752
             if (verbose_) printf("Error: signature mismatch (expected TSQ1).\n");
             return false;
         }
-        uint32_t nb; uint64_t total;
-        memcpy(&nb, header + 4, 4); memcpy(&total, header + 8, 8);
-        if (nb == 0) {                                                                         // tsq_threads.cpp:759-768
+        if (h == tsq::kHeaderNoBlocks) {                                                       // tsq_threads.cpp:759-768
             if (verbose_) printf("Error: no blocks to decode in input file.\n");
             return false;
         }
-        // The header is not trusted with an allocation before it has been held against the container: a frame is at
-        // least 6 bytes, a block at most 4 MiB, and no stream expands more than 64x (eight 64-byte copies per 13-byte group).
-        if ((uint64_t)nb > (src.size - 16) / 6) return false;
-        if ((uint64_t)nb * kBlockSize < total || total / 64 > src.size) return false;
+        // The header is not trusted with an allocation before it has been held against the container (read_header's bounds), and
+        // no stream expands more than 64x (eight 64-byte copies per 13-byte group).
+        if (h != tsq::kHeaderOk || total / 64 > src.size) return false;
         Sink sink;
         if (j.outfile) { if (!sink.open_file_buffered(j.out_path.c_str(), (size_t)total + 128)) return false; }
         else if (!sink.open_mem((size_t)total + 128)) return false;                            // tsq_threads.cpp:795
@@ -792,8 +791,7 @@ private:
                 // a sibling workgroup of a several-workgroups-per-block decode did not get onto the GPU in time: the batch is still on
                 // the device -- once more with one workgroup per block
                 hipStream_t s = l.dev->stream;
-                bool good = hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s) == hipSuccess;
-                good = good && l.dev->launch_decode(l.d_in, f.n_blocks, l.d_out, l.dev->d_status, s, 4) == TSQA_OK;
+                bool good = l.dev->decode_again(l.d_in, l.dev->frames, f.n_blocks, l.d_out, l.dev->d_status, s) == TSQA_OK;
                 good = good && hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
                 good = good && hipStreamSynchronize(s) == hipSuccess;
                 mk.at("decompress: batch decoded again (stall)");
@@ -858,7 +856,7 @@ private:
             fly_cv.notify_all();
             if (drainer.joinable()) drainer.join();
         };
-        size_t at = 16;                       // container cursor: the frame walk is serial (tsq_threads.cpp:513-524)
+        size_t at = tsq::kHeaderSize;         // container cursor: the frame walk is serial (tsq_threads.cpp:513-524)
         uint64_t produced = 0;
         for (uint32_t b0 = 0, k = 0; b0 < nb && ok; ++k) {
             const size_t lane_i = k % lanes_.size();
@@ -871,24 +869,21 @@ private:
             // sized by what is left of the job, not by the configured batch (a one-block container must not reserve gigabytes)
             const uint32_t sched = k < sizes.size() ? sizes[k] : batch;
             const uint32_t want_blocks = nb - b0 < sched ? nb - b0 : sched;
-            size_t in_budget = (size_t)want_blocks * (3 + kSlotSize);
+            size_t in_budget = (size_t)want_blocks * (tsq::kFrameWordSize + kSlotSize);
             if (in_budget > src.size - at) in_budget = src.size - at;
             if (!l.reserve(in_budget + 16, (size_t)want_blocks * kBlockSize + 256, want_blocks, stage_in, stage_out)) { ok = false; break; }
             // walk whole frames until the batch is full; the frames of a batch are one contiguous slice of the container
             size_t cur = 0; uint32_t bn = 0; size_t out_bytes = 0;
             while (b0 + bn < nb && bn < want_blocks) {
-                uint8_t fh[6];
-                if (src.read_at(at + cur, 6, fh) != 6) break;
-                uint32_t frame = (uint32_t)fh[0] | ((uint32_t)fh[1] << 8) | ((uint32_t)fh[2] << 16);
-                uint32_t len = frame & 0x7FFFFFu;                                             // tsq_threads.cpp:513-517
-                if (len < 3 || len > kSlotSize) { ok = false; break; }                         // tsq_threads.cpp:526-531
-                if (at + cur + 3 + len > src.size) { ok = false; break; }
-                if (cur + 3 + len > l.in_cap) break;
-                uint32_t usize = (uint32_t)fh[3] | ((uint32_t)fh[4] << 8) | ((uint32_t)fh[5] << 16);
-                if (usize > kBlockSize || produced + out_bytes + usize > total) { ok = false; break; }
+                uint8_t fh[tsq::kMinFrameSize];
+                if (src.read_at(at + cur, sizeof(fh), fh) != sizeof(fh)) break;
                 FrameInfo& fi = l.h_frames[bn];
-                fi.stream_at = cur + 3; fi.out_at = out_bytes; fi.stream_len = len; fi.ext = frame >> 23; fi.out_len = usize; fi.pad = 0;
-                out_bytes += usize; cur += 3 + len; bn++;
+                if (!tsq::read_frame(fh, at + cur, src.size, &fi)) { ok = false; break; }      // tsq_threads.cpp:513-531
+                const size_t frame_bytes = tsq::kFrameWordSize + fi.stream_len;
+                if (cur + frame_bytes > l.in_cap) break;
+                if (produced + out_bytes + fi.out_len > total) { ok = false; break; }
+                fi.stream_at = cur + tsq::kFrameWordSize; fi.out_at = out_bytes;
+                out_bytes += fi.out_len; cur += frame_bytes; bn++;
             }
             if (!ok) break;
             if (bn == 0) { ok = false; break; }                        // truncated container
@@ -1087,8 +1082,8 @@ extern "C" void tsqDecode(uint8_t* inputBlock, uint8_t* outputBlock, uint32_t* o
                           uint32_t withExtensions)
 {
     if (outputSize) *outputSize = 0;
-    if (!inputBlock || !outputBlock || !outputSize || inputSize < 3 || inputSize > kSlotSize) return;
-    uint32_t usize = (uint32_t)inputBlock[0] | ((uint32_t)inputBlock[1] << 8) | ((uint32_t)inputBlock[2] << 16);
+    if (!inputBlock || !outputBlock || !outputSize || !tsq::stream_len_ok(inputSize)) return;
+    const uint32_t usize = (uint32_t)tsq::load_le(inputBlock, 3);
     if (usize > kBlockSize) return;                                    // tsq_decode.cpp:53,146
     BlockCodec& bc = block_codec();
     std::lock_guard<std::mutex> g(bc.m);
@@ -1107,8 +1102,7 @@ extern "C" void tsqDecode(uint8_t* inputBlock, uint8_t* outputBlock, uint32_t* o
     (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return;
     if (*l.h_status == tsq::kErrStall) {          // (a sibling workgroup did not get onto the GPU in time: once more on one workgroup)
-        (void)hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s);
-        if (l.dev->launch_decode(l.d_in, 1, l.d_out, l.dev->d_status, s, 4) != TSQA_OK) return;
+        if (l.dev->decode_again(l.d_in, l.dev->frames, 1, l.d_out, l.dev->d_status, s) != TSQA_OK) return;
         (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
         if (hipStreamSynchronize(s) != hipSuccess) return;
     }

@@ -1,10 +1,8 @@
-// tsq_container.cuh -- device-side .tsq container assembly and frame walk.
-//
-// Container (turbosqueeze.cpp:64-83, tsq_threads.cpp:218-239,333-335): 16-byte header
-// "TSQ1" | u32 n_blocks | u64 total, then per block a u24 frame (size | ext << 23) and the stream.
+// tsq_container.cuh -- device-side .tsq container assembly and frame walk (the format itself: tsq_format.h).
 #pragma once
 
 #include "tsq_common.cuh"
+#include "tsq_format.h"
 
 namespace tsq {
 
@@ -18,11 +16,11 @@ __global__ __launch_bounds__(256) void pack_scan_kernel(const uint32_t* __restri
     __shared__ uint64_t wave_sum[4];
     __shared__ uint64_t carry;
     const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
-    if (t == 0) carry = 16;
+    if (t == 0) carry = kHeaderSize;
     __syncthreads();
     for (uint32_t base = 0; base < n_blocks; base += 256) {
         uint32_t b = base + t;
-        uint64_t v = b < n_blocks ? 3ull + sizes[b] : 0ull;
+        uint64_t v = b < n_blocks ? kFrameWordSize + (uint64_t)sizes[b] : 0ull;
         uint64_t incl = v;                                   // inclusive wave scan
         for (uint32_t d = 1; d < 64; d <<= 1) {
             uint64_t up = __shfl_up(incl, d);
@@ -44,18 +42,8 @@ __global__ __launch_bounds__(256) void pack_scan_kernel(const uint32_t* __restri
         if (total > out_cap) atomicMax(status, kErrOverflow);
     }
     if (total > out_cap) return;
-    if (t < 16) {
-        uint8_t v;
-        if (t < 4) v = (uint8_t)"TSQ1"[t];
-        else if (t < 8) v = (uint8_t)(n_blocks >> (8 * (t - 4)));
-        else v = (uint8_t)(n_total >> (8 * (t - 8)));
-        container[t] = v;
-    }
-    for (uint32_t b = t; b < n_blocks; b += 256) {
-        uint32_t frame = sizes[b] | (ext ? 0x800000u : 0u);     // tsq_threads.cpp:218-219
-        uint8_t* p = container + frame_at[b];
-        p[0] = (uint8_t)frame; p[1] = (uint8_t)(frame >> 8); p[2] = (uint8_t)(frame >> 16);
-    }
+    if (t == 0) write_header(container, n_blocks, n_total);
+    for (uint32_t b = t; b < n_blocks; b += 256) write_frame(container + frame_at[b], sizes[b], ext);
 }
 
 // Copy each block stream from its slot to its place in the container.  Destination offsets are
@@ -98,31 +86,20 @@ __global__ __launch_bounds__(64) void frame_walk_kernel(const uint8_t* __restric
                                                         uint64_t* __restrict__ out_size, int32_t* __restrict__ status)
 {
     if (threadIdx.x != 0) return;
-    int32_t bad = 0;
-    uint64_t total = 0, at = 16, oat = 0;
-    if (n < 16 || container[0] != 'T' || container[1] != 'S' || container[2] != 'Q' || container[3] != '1') bad = kErrFormat;
-    if (!bad) {
-        uint32_t nb = ldu32(container + 4);
-        total = ldu64(container + 8);
-        if (nb != n_blocks || nb == 0) bad = kErrFormat;          // tsq_threads.cpp:759-768
-        if (total > out_cap) bad = kErrFormat;
-    }
+    uint32_t nb = 0;
+    uint64_t total = 0, at = kHeaderSize, oat = 0;
+    bool bad = read_header(container, n, &nb, &total) != kHeaderOk || nb != n_blocks || total > out_cap;
     for (uint32_t b = 0; b < n_blocks && !bad; ++b) {
-        if (at + 6 > n) { bad = kErrFormat; break; }
-        uint32_t frame = (uint32_t)container[at] | ((uint32_t)container[at + 1] << 8) | ((uint32_t)container[at + 2] << 16);
-        uint32_t len = frame & 0x7FFFFFu;                          // tsq_threads.cpp:513-517
-        if (len < 3 || len > kSlotSize || at + 3 + len > n) { bad = kErrFormat; break; }
-        uint32_t usize = (uint32_t)container[at + 3] | ((uint32_t)container[at + 4] << 8) | ((uint32_t)container[at + 5] << 16);
-        if (usize > kBlockSize || oat + usize > total) { bad = kErrFormat; break; }
         FrameInfo f;
-        f.stream_at = at + 3; f.out_at = oat; f.stream_len = len; f.ext = frame >> 23; f.out_len = usize; f.pad = 0;
+        if (at + kMinFrameSize > n || !read_frame(container + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
+        f.stream_at = at + kFrameWordSize; f.out_at = oat;
         frames[b] = f;
-        oat += usize;
-        at += 3 + len;
+        oat += f.out_len;
+        at += kFrameWordSize + f.stream_len;
     }
-    if (!bad && oat != total) bad = kErrFormat;
+    if (!bad && oat != total) bad = true;
     *out_size = bad ? 0 : total;
-    if (bad) atomicMax(status, bad);
+    if (bad) atomicMax(status, kErrFormat);
 }
 
 }  // namespace tsq

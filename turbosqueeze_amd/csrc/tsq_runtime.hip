@@ -9,6 +9,7 @@
 
 #include "tsq_common.cuh"
 #include "tsq_container.cuh"
+#include "tsq_format.h"
 #include "tsq_serial.cuh"
 #include "tsq_launch.cuh"
 
@@ -351,6 +352,12 @@ int tsqa_ctx::launch_decode(const void* d_container, uint32_t n_blocks, void* d_
     return launch_decode_frames(d_container, frames, n_blocks, d_out, status, s, variant);
 }
 
+int tsqa_ctx::decode_again(const void* d_streams, const FrameInfo* d_frames, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s)
+{
+    TSQ_HIP(this, hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    return launch_decode_frames(d_streams, d_frames, n_blocks, d_out, status, s, 4);
+}
+
 // ---- public device-resident entry points ----
 
 extern "C" int tsqa_compress_device_async(tsqa_ctx* c, const void* d_in, size_t n, void* d_out, size_t out_cap,
@@ -457,15 +464,15 @@ extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, v
     if (!d_in || n < 16) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     (void)hipSetDevice(c->device);
-    uint8_t head[16];
-    TSQ_HIP(c, hipMemcpyAsync(head, d_in, 16, hipMemcpyDeviceToHost, s));
+    uint8_t head[kHeaderSize];
+    TSQ_HIP(c, hipMemcpyAsync(head, d_in, kHeaderSize, hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
-    if (memcmp(head, "TSQ1", 4) != 0) { c->set_error("decompress: bad magic"); return TSQA_ERR_FORMAT; }   // tsq_threads.cpp:732-752
-    uint32_t nb; uint64_t total;
-    memcpy(&nb, head + 4, 4); memcpy(&total, head + 8, 8);
-    if (nb == 0) { c->set_error("decompress: n_blocks == 0"); return TSQA_ERR_FORMAT; }                     // tsq_threads.cpp:759-768
+    uint32_t nb = 0; uint64_t total = 0;
+    const int h = read_header(head, n, &nb, &total);
+    if (h == kHeaderBadMagic || h == kHeaderNoBlocks) { c->set_error("decompress: bad magic or no blocks"); return TSQA_ERR_FORMAT; }
     if (total > out_cap) { c->set_error("decompress: output capacity %zu < %llu", out_cap, (unsigned long long)total); return TSQA_ERR_ARG; }
-    if ((size_t)nb > n / 6) { c->set_error("decompress: n_blocks larger than the container"); return TSQA_ERR_FORMAT; }
+    // (an implausible header is refused with *out_size = 0, as the frame walk would refuse it)
+    if (h != kHeaderOk) { *out_size = 0; c->set_error("decompress: more blocks or bytes than a container of %zu B can hold", n); return TSQA_ERR_FORMAT; }
     int rc = tsqa_decompress_device_async(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s);
     if (rc) return rc;
     uint64_t sz = 0; int32_t st = 0;
@@ -497,11 +504,10 @@ extern "C" int tsqa_frames_to_host_async(tsqa_ctx* c, const void* d_slots, const
     (void)hipSetDevice(c->device);
     uint8_t* base = static_cast<uint8_t*>(host_container);
     for (uint32_t b = 0; b < n_blocks; ++b) {
-        if (sizes[b] < 3 || sizes[b] > kSlotSize) { c->set_error("frames_to_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_ARG; }
-        const uint32_t frame = sizes[b] | (ext ? 0x800000u : 0u);                     // tsq_threads.cpp:218-219
+        if (!stream_len_ok(sizes[b])) { c->set_error("frames_to_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_ARG; }
         uint8_t* p = base + frame_at[b];
-        p[0] = (uint8_t)frame; p[1] = (uint8_t)(frame >> 8); p[2] = (uint8_t)(frame >> 16);
-        TSQ_HIP(c, hipMemcpyAsync(p + 3, static_cast<const uint8_t*>(d_slots) + (size_t)b * kSlotSize, sizes[b], hipMemcpyDeviceToHost, s));
+        write_frame(p, sizes[b], ext);
+        TSQ_HIP(c, hipMemcpyAsync(p + kFrameWordSize, static_cast<const uint8_t*>(d_slots) + (size_t)b * kSlotSize, sizes[b], hipMemcpyDeviceToHost, s));
     }
     return TSQA_OK;
 }
@@ -515,8 +521,8 @@ extern "C" int tsqa_frames_from_host_async(tsqa_ctx* c, const void* host_contain
     (void)hipSetDevice(c->device);
     const uint8_t* base = static_cast<const uint8_t*>(host_container);
     for (uint32_t b = 0; b < n_blocks; ++b) {
-        if (sizes[b] < 3 || sizes[b] > kSlotSize) { c->set_error("frames_from_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_FORMAT; }
-        TSQ_HIP(c, hipMemcpyAsync(static_cast<uint8_t*>(d_streams) + (size_t)b * kSlotSize, base + frame_at[b] + 3, sizes[b], hipMemcpyHostToDevice, s));
+        if (!stream_len_ok(sizes[b])) { c->set_error("frames_from_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_FORMAT; }
+        TSQ_HIP(c, hipMemcpyAsync(static_cast<uint8_t*>(d_streams) + (size_t)b * kSlotSize, base + frame_at[b] + kFrameWordSize, sizes[b], hipMemcpyHostToDevice, s));
     }
     return TSQA_OK;
 }
@@ -527,13 +533,31 @@ extern "C" int tsqa_frames_from_host_async(tsqa_ctx* c, const void* host_contain
 extern "C" int tsqa_frame_offsets(const uint32_t* sizes, uint32_t n_blocks, uint64_t* frame_at, uint64_t* container_size)
 {
     if (!sizes || !frame_at || !container_size) return TSQA_ERR_ARG;
-    uint64_t at = 16;
+    uint64_t at = kHeaderSize;
     for (uint32_t b = 0; b < n_blocks; ++b) {
-        if (sizes[b] < 3 || sizes[b] > kSlotSize) return TSQA_ERR_ARG;
+        if (!stream_len_ok(sizes[b])) return TSQA_ERR_ARG;
         frame_at[b] = at;
-        at += 3ull + sizes[b];
+        at += kFrameWordSize + (uint64_t)sizes[b];
     }
     *container_size = at;
+    return TSQA_OK;
+}
+
+// The reader's walk over the nb frames of a container of `size` bytes in host memory whose header read_header has accepted:
+// visit(b, at, f) per frame (`at`: its frame word; f: read_frame's fields) returns false to end the walk, having set *why.
+// TSQA_ERR_FORMAT for a malformed or truncated frame and for block sizes that do not add up to the header's total.
+template <class Visit>
+static int walk_host_frames(const uint8_t* p, size_t size, uint32_t nb, uint64_t total, const char** why, Visit&& visit)
+{
+    uint64_t at = kHeaderSize, sum = 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+        FrameInfo f;
+        if (at + kMinFrameSize > size || !read_frame(p + at, at, size, &f)) { *why = "malformed or truncated frame"; return TSQA_ERR_FORMAT; }
+        if (!visit(b, at, f)) return TSQA_ERR_FORMAT;
+        sum += f.out_len;
+        at += kFrameWordSize + f.stream_len;
+    }
+    if (sum != total) { *why = "block sizes do not add up to the total"; return TSQA_ERR_FORMAT; }
     return TSQA_OK;
 }
 
@@ -542,23 +566,14 @@ extern "C" int tsqa_walk_frames(const void* container, size_t size, uint32_t cap
 {
     if (!container || !frame_at || !sizes || !ext || !out_len || !n_blocks || !total) return TSQA_ERR_ARG;
     const uint8_t* p = static_cast<const uint8_t*>(container);
-    if (size < 16 || memcmp(p, "TSQ1", 4) != 0) return TSQA_ERR_FORMAT;                    // tsq_threads.cpp:732-752
     uint32_t nb; uint64_t tot;
-    memcpy(&nb, p + 4, 4); memcpy(&tot, p + 8, 8);
-    if (nb == 0 || (size_t)nb > (size - 16) / 6 || nb > cap_blocks) return TSQA_ERR_FORMAT;  // tsq_threads.cpp:759-768
-    uint64_t at = 16, sum = 0;
-    for (uint32_t b = 0; b < nb; ++b) {
-        if (at + 6 > size) return TSQA_ERR_FORMAT;
-        const uint32_t frame = (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16);
-        const uint32_t len = frame & 0x7FFFFFu;                                             // tsq_threads.cpp:513-517
-        if (len < 3 || len > kSlotSize || at + 3 + len > size) return TSQA_ERR_FORMAT;
-        const uint32_t usize = (uint32_t)p[at + 3] | ((uint32_t)p[at + 4] << 8) | ((uint32_t)p[at + 5] << 16);
-        if (usize > kBlockSize) return TSQA_ERR_FORMAT;
-        frame_at[b] = at; sizes[b] = len; ext[b] = frame >> 23; out_len[b] = usize;
-        sum += usize;
-        at += 3ull + len;
-    }
-    if (sum != tot) return TSQA_ERR_FORMAT;
+    if (read_header(p, size, &nb, &tot) != kHeaderOk || nb > cap_blocks) return TSQA_ERR_FORMAT;
+    const char* why;
+    const int rc = walk_host_frames(p, size, nb, tot, &why, [&](uint32_t b, uint64_t at, const FrameInfo& f) {
+        frame_at[b] = at; sizes[b] = f.stream_len; ext[b] = f.ext; out_len[b] = f.out_len;
+        return true;
+    });
+    if (rc) return rc;
     *n_blocks = nb; *total = tot;
     return TSQA_OK;
 }
@@ -576,27 +591,23 @@ extern "C" int tsqa_sharded_place_async(tsqa_ctx* c, const void* d_slots, const 
     (void)hipSetDevice(c->device);
     uint8_t* base = static_cast<uint8_t*>(host_container);
     // every size and the capacity are checked before anything is written or enqueued (no partial container on an error)
-    uint64_t at = 16;
+    uint64_t at = kHeaderSize;
     for (uint32_t b = 0; b < n_blocks; ++b) {
         const uint32_t sz = all_sizes[b];
-        if (sz < 3 || sz > kSlotSize) { c->set_error("sharded_place: block %u has size %u", b, sz); return TSQA_ERR_ARG; }
-        at += 3ull + sz;
+        if (!stream_len_ok(sz)) { c->set_error("sharded_place: block %u has size %u", b, sz); return TSQA_ERR_ARG; }
+        at += kFrameWordSize + (uint64_t)sz;
     }
     if (at > host_cap) { c->set_error("sharded_place: the host container is too small (%llu > %zu)", (unsigned long long)at, host_cap); return TSQA_ERR_ARG; }
-    at = 16;
+    at = kHeaderSize;
     for (uint32_t b = 0; b < n_blocks; ++b) {
         const uint32_t sz = all_sizes[b];
         if (b % world == rank) {
-            const uint32_t frame = sz | (ext ? 0x800000u : 0u);                          // tsq_threads.cpp:218-219
-            uint8_t* p = base + at;
-            p[0] = (uint8_t)frame; p[1] = (uint8_t)(frame >> 8); p[2] = (uint8_t)(frame >> 16);
-            TSQ_HIP(c, hipMemcpyAsync(p + 3, static_cast<const uint8_t*>(d_slots) + (size_t)(b / world) * kSlotSize, sz, hipMemcpyDeviceToHost, s));
+            write_frame(base + at, sz, ext);
+            TSQ_HIP(c, hipMemcpyAsync(base + at + kFrameWordSize, static_cast<const uint8_t*>(d_slots) + (size_t)(b / world) * kSlotSize, sz, hipMemcpyDeviceToHost, s));
         }
-        at += 3ull + sz;
+        at += kFrameWordSize + (uint64_t)sz;
     }
-    if (rank == 0) {                                                                      // tsq_threads.cpp:333-335
-        memcpy(base, "TSQ1", 4); memcpy(base + 4, &n_blocks, 4); memcpy(base + 8, &n_total, 8);
-    }
+    if (rank == 0) write_header(base, n_blocks, n_total);                                 // tsq_threads.cpp:333-335
     *container_size = at;
     return TSQA_OK;
 }
@@ -612,38 +623,27 @@ extern "C" int tsqa_sharded_fetch_decode_async(tsqa_ctx* c, const void* host_con
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     (void)hipSetDevice(c->device);
     const uint8_t* p = static_cast<const uint8_t*>(host_container);
-    if (container_size < 16 || memcmp(p, "TSQ1", 4) != 0) { c->set_error("sharded_fetch_decode: bad magic"); return TSQA_ERR_FORMAT; }
+    c->forget_sharded();                                 // whatever happens below, an older call's descriptors are not to be decoded again
     uint32_t nb; uint64_t tot;
-    memcpy(&nb, p + 4, 4); memcpy(&tot, p + 8, 8);
-    if (nb == 0 || (size_t)nb > (container_size - 16) / 6) { c->set_error("sharded_fetch_decode: bad block count"); return TSQA_ERR_FORMAT; }
+    if (read_header(p, container_size, &nb, &tot) != kHeaderOk) { c->set_error("sharded_fetch_decode: bad header"); return TSQA_ERR_FORMAT; }
     const uint32_t n_local = nb > rank ? (nb - rank + world - 1) / world : 0;
     // The container is not trusted: the whole frame walk is validated -- against the container's own size and against what the caller's
     // buffers can hold -- before a single copy is enqueued (a container with more, shorter blocks than the job the buffers were sized
     // for must not overrun them).
     if ((uint64_t)n_local * kSlotSize > streams_cap) { c->set_error("sharded_fetch_decode: %u owned frames do not fit d_streams (%zu B)", n_local, streams_cap); return TSQA_ERR_FORMAT; }
-    c->forget_sharded();                                 // whatever happens below, an older call's descriptors are not to be decoded again
     if (int rc = c->reserve(n_local ? n_local : 1, false, false)) return rc;
     if (int rc = c->reserve_host_frames(n_local ? n_local : 1)) return rc;
-    uint64_t at = 16, sum = 0;
-    for (uint32_t b = 0; b < nb; ++b) {
-        if (at + 6 > container_size) { c->set_error("sharded_fetch_decode: truncated container"); return TSQA_ERR_FORMAT; }
-        const uint32_t frame = (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16);
-        const uint32_t len = frame & 0x7FFFFFu;
-        if (len < 3 || len > kSlotSize || at + 3 + len > container_size) { c->set_error("sharded_fetch_decode: bad frame %u", b); return TSQA_ERR_FORMAT; }
-        const uint32_t usize = (uint32_t)p[at + 3] | ((uint32_t)p[at + 4] << 8) | ((uint32_t)p[at + 5] << 16);
-        if (usize > kBlockSize) { c->set_error("sharded_fetch_decode: bad block size in frame %u", b); return TSQA_ERR_FORMAT; }
-        if (b % world == rank) {
-            const uint32_t k = b / world;
-            if ((uint64_t)k * kBlockSize + usize > out_cap) { c->set_error("sharded_fetch_decode: owned block %u does not fit d_out (%zu B)", k, out_cap); return TSQA_ERR_FORMAT; }
-            FrameInfo f;
-            f.stream_at = (uint64_t)k * kSlotSize; f.out_at = (uint64_t)k * kBlockSize; f.stream_len = len; f.ext = frame >> 23; f.out_len = usize; f.pad = 0;
-            c->host_frames[k] = f;
-            c->host_frame_src[k] = at + 3;
-        }
-        sum += usize;
-        at += 3ull + len;
-    }
-    if (sum != tot) { c->set_error("sharded_fetch_decode: block sizes do not add up"); return TSQA_ERR_FORMAT; }
+    const char* why;
+    const int rc = walk_host_frames(p, container_size, nb, tot, &why, [&](uint32_t b, uint64_t at, FrameInfo f) {
+        if (b % world != rank) return true;
+        const uint32_t k = b / world;
+        if ((uint64_t)k * kBlockSize + f.out_len > out_cap) { why = "an owned block does not fit d_out"; return false; }
+        f.stream_at = (uint64_t)k * kSlotSize; f.out_at = (uint64_t)k * kBlockSize;
+        c->host_frames[k] = f;
+        c->host_frame_src[k] = at + kFrameWordSize;
+        return true;
+    });
+    if (rc) { c->set_error("sharded_fetch_decode: %s", why); return rc; }
     *total = tot;
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     if (n_local == 0) return TSQA_OK;
@@ -670,8 +670,7 @@ extern "C" int tsqa_sharded_decode_again_async(tsqa_ctx* c, const void* d_stream
     if (d_streams != c->sharded_streams || d_out != c->sharded_out) { c->set_error("sharded_decode_again: not the buffers of the sharded decode being repeated"); return TSQA_ERR_ARG; }
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     (void)hipSetDevice(c->device);
-    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    return c->launch_decode_frames(d_streams, c->frames, c->sharded_n_local, d_out, d_status, s, 4);
+    return c->decode_again(d_streams, c->frames, c->sharded_n_local, d_out, d_status, s);
 }
 
 // ---- range reads: an index of a device-resident container, and reads of byte ranges of its uncompressed data ----
@@ -682,18 +681,14 @@ extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n,
     *out = nullptr;
     if (!c) return TSQA_ERR_ARG;
     if (!d_container) { c->set_error("index_create: null container"); return TSQA_ERR_ARG; }
-    if (n < 16) { c->set_error("index_create: a container of %zu B has no header", n); return TSQA_ERR_FORMAT; }
+    if (n < kHeaderSize) { c->set_error("index_create: a container of %zu B has no header", n); return TSQA_ERR_FORMAT; }
     (void)hipSetDevice(c->device);
     hipStream_t s = c->stream;
-    uint8_t head[16];
-    TSQ_HIP(c, hipMemcpyAsync(head, d_container, 16, hipMemcpyDeviceToHost, s));
+    uint8_t head[kHeaderSize];
+    TSQ_HIP(c, hipMemcpyAsync(head, d_container, kHeaderSize, hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     uint32_t nb; uint64_t total;
-    memcpy(&nb, head + 4, 4); memcpy(&total, head + 8, 8);
-    // the reader's bounds (tsq_compat.hip): every frame takes at least 6 bytes, every block at most TSQ_BLOCK_SZ of output
-    if (memcmp(head, "TSQ1", 4) != 0) { c->set_error("index_create: bad magic"); return TSQA_ERR_FORMAT; }
-    if (nb == 0 || (size_t)nb > (n - 16) / 6) { c->set_error("index_create: bad block count %u", nb); return TSQA_ERR_FORMAT; }
-    if (total > (uint64_t)nb * kBlockSize) { c->set_error("index_create: total %llu larger than %u blocks", (unsigned long long)total, nb); return TSQA_ERR_FORMAT; }
+    if (read_header(head, n, &nb, &total) != kHeaderOk) { c->set_error("index_create: bad header"); return TSQA_ERR_FORMAT; }
     tsqa_index* idx = new (std::nothrow) tsqa_index();
     if (!idx) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
     idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = total;
