@@ -263,6 +263,50 @@ int tsqa_decompress_ranges_async(tsqa_ctx *ctx, const tsqa_index *idx, const tsq
 int tsqa_decompress_ranges(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_range *ranges, uint32_t n_ranges,
                            void *d_out, size_t out_cap, void *hip_stream);
 
+/*
+ * Batches: many independent items in one call.  A batch is one input buffer and one output buffer in HBM plus a host array of
+ * items: item i reads bytes [in_at, in_at + in_len) of d_in (in_size bytes) and writes its result to [out_at, out_at + out_cap) of
+ * d_out (out_size bytes).  The blocks of all items run side by side, one workgroup each, in launches of at most 2 x CUs blocks, so
+ * a batch of small items fills the chip where one call per item holds one CU at a time.
+ */
+typedef struct tsqa_batch_item { uint64_t in_at, in_len, out_at, out_cap; } tsqa_batch_item;
+
+/* Host-only (no device): validate a batch and give each item's first block in the batch; first_block[n_items] = the batch's
+ * block count.  n_blocks == NULL: a compress batch (item i has ceil(in_len / TSQ_BLOCK_SZ) blocks); else a decompress batch with
+ * the stated block counts.  TSQA_ERR_ARG, with nothing written, for: no items; an item with in_len == 0; an input range past
+ * in_size or an output range past out_size; two output ranges that overlap (input ranges may); compress: out_cap < 16 + 6 * blocks;
+ * decompress: in_len < 16, a block count of 0 or above (in_len - 16) / 6. */
+int tsqa_plan_batch(const tsqa_batch_item *items, uint32_t n_items, size_t in_size, size_t out_size,
+                    const uint32_t *n_blocks, uint64_t *first_block);
+
+/* Compress every item.  Item i's container is byte for byte what tsqa_compress_device gives for its bytes alone: the encoder's
+ * look-ahead ends at the item's last byte and never sees the next item.  d_sizes[i] (device) = its container size; when that
+ * exceeds out_cap, *d_status (device) becomes TSQA_ERR_OVERFLOW and the frames that do not fit are not written.  Nothing is written
+ * outside the items' output ranges, and the other items are complete.  The batch is planned (tsqa_plan_batch) before anything is
+ * enqueued.  Encoder variants 0, 6 and 7; the others are refused (TSQA_ERR_ARG).  The asynchronous form returns at once and may be
+ * called again on the same stream before the first has run.  tsqa_compress_batch waits, fills sizes (host) and returns
+ * TSQA_ERR_OVERFLOW when an item did not fit: retry those items with more room. */
+int tsqa_compress_batch_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                              uint32_t ext, void *d_out, size_t out_size, uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
+int tsqa_compress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                        uint32_t ext, void *d_out, size_t out_size, uint64_t *sizes, void *hip_stream);
+
+/* Decompress every item (a container) into its output range.  The asynchronous form takes each container's block count (host
+ * array n_blocks) and validates each container as tsqa_decompress_device_async validates one: the header with that block count,
+ * total <= out_cap, every frame, frame lengths that add up to the total.  d_sizes[i] = the item's uncompressed size, 0 when it was
+ * refused; any refusal or malformed stream sets *d_status, and the decode then leaves at once: all or nothing.  TSQA_ERR_STALL as
+ * for tsqa_decompress_device_async (decode again with decode variant 4).
+ * tsqa_decompress_batch reads every header itself (one gather, one copy), leaves items with a refused header out (item_status:
+ * TSQA_ERR_FORMAT, or TSQA_ERR_ARG when the total exceeds out_cap), decodes the rest in one batch, retries once after
+ * TSQA_ERR_STALL on one workgroup per block, and when the batch reports a malformed container decodes the items one by one to find
+ * those at fault.  item_status (host, may be NULL) and sizes (host) per item; every healthy item is delivered; the return value is
+ * the largest item status.  Nothing is written outside the items' output ranges. */
+int tsqa_decompress_batch_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items,
+                                const uint32_t *n_blocks, uint32_t n_items, void *d_out, size_t out_size,
+                                uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
+int tsqa_decompress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                          void *d_out, size_t out_size, uint64_t *sizes, int32_t *item_status, void *hip_stream);
+
 /* =====================================================================================
  * (1) The reference API (turbosqueeze.h:441-674), C-callable subset
  * ================================================================================== */

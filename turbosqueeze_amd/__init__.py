@@ -7,16 +7,19 @@ if the shared library or a gfx950 device is missing, calls raise.
 from .api import (  # noqa: F401
     BLOCK_SZ,
     OUTPUT_SZ,
+    BatchItem,
     DeviceCodec,
     Range,
     RangeIndex,
     RangeItem,
     TsqError,
+    batch_bound,
     build_info,
     build_native,
     container_bound,
     lib,
     lib_path,
+    plan_batch,
     plan_ranges,
     source_fingerprint,
     tsq_compress_mt,

@@ -169,6 +169,16 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_ranges_async.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
     L.tsqa_decompress_ranges.restype = C.c_int
     L.tsqa_decompress_ranges.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
+    L.tsqa_plan_batch.restype = C.c_int
+    L.tsqa_plan_batch.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_size_t, vp, vp]
+    L.tsqa_compress_batch_async.restype = C.c_int
+    L.tsqa_compress_batch_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_compress_batch.restype = C.c_int
+    L.tsqa_compress_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp]
+    L.tsqa_decompress_batch_async.restype = C.c_int
+    L.tsqa_decompress_batch_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_decompress_batch.restype = C.c_int
+    L.tsqa_decompress_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqCompress.restype = None
     L.tsqCompress.argtypes = [vp, vp, C.c_bool, C.c_uint32]
     L.tsqDecompress.restype = None
@@ -285,6 +295,43 @@ class RangeIndex:
         triples, out, views = self._packed(ranges, out)
         self.read_into(triples, out, sync=False)
         return out[:sum(int(ln) for _, ln in ranges)], views
+
+
+class BatchItem(C.Structure):
+    """tsqa_batch_item: input bytes [in_at, in_at + in_len) -> output range [out_at, out_at + out_cap)"""
+    _fields_ = [("in_at", C.c_uint64), ("in_len", C.c_uint64), ("out_at", C.c_uint64), ("out_cap", C.c_uint64)]
+
+
+def _batch_array(items):
+    """(in_at, in_len, out_at, out_cap) quadruples -> a ctypes tsqa_batch_item array"""
+    arr = (BatchItem * max(len(items), 1))()
+    for k, (a, n, o, cap) in enumerate(items):
+        arr[k] = BatchItem(int(a), int(n), int(o), int(cap))
+    return arr
+
+
+def plan_batch(items, in_size: int, out_size: int, n_blocks=None):
+    """tsqa_plan_batch (host only): items = (in_at, in_len, out_at, out_cap); n_blocks None: a compress batch, else the stated block
+    count per container.  -> each item's first block in the batch, then the batch's block count.  Raises TsqError(3) when refused."""
+    import numpy as np
+    first = np.zeros(len(items) + 1, dtype=np.uint64)
+    nb = None if n_blocks is None else np.ascontiguousarray(n_blocks, dtype=np.uint32)
+    rc = lib().tsqa_plan_batch(_batch_array(items), len(items), in_size, out_size, None if nb is None else nb.ctypes.data, first.ctypes.data)
+    if rc:
+        raise TsqError(rc, "tsqa_plan_batch refused the batch")
+    return [int(x) for x in first]
+
+
+def batch_bound(n: int) -> int:
+    """Room that always holds the container of an n-byte item, much tighter than container_bound below a block: the header, then
+    per block its frame word and a stream of at most every byte a literal of its own (n + n/8 + n/2 + 11), and never more than
+    TSQ_OUTPUT_SZ."""
+    cap, left = 16, n
+    while left > 0:
+        k = min(left, BLOCK_SZ)
+        cap += 3 + min(OUTPUT_SZ, 11 + k + (k >> 3) + (k >> 1))
+        left -= k
+    return cap
 
 
 DONE_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_bool, C.c_void_p)
@@ -465,6 +512,100 @@ class DeviceCodec:
     def index(self, blob) -> RangeIndex:
         """An index of the .tsq container `blob` (uint8 CUDA tensor) for range reads: index(blob).read(offset, length)."""
         return RangeIndex(self, blob)
+
+    # ---- batches: many independent items in one call (tsqa_*_batch) ----
+    def _arena(self, tensors):
+        """-> (arena tensor, offset of each tensor in it).  Views of one storage are used in place (the arena is the whole storage);
+        separate allocations are packed into a new arena with one torch.cat, a device copy of every byte."""
+        torch = self.torch
+        if not tensors:
+            raise TsqError(3, "a batch needs at least one item")
+        for t in tensors:
+            if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or not t.is_contiguous() or t.device != self.device:
+                raise TsqError(3, "batch items must be contiguous 1-D uint8 tensors on the codec's device")
+        st = tensors[0].untyped_storage()
+        if all(t.untyped_storage().data_ptr() == st.data_ptr() for t in tensors):
+            arena = torch.empty(0, dtype=torch.uint8, device=self.device).set_(st, 0, (st.nbytes(),))
+            return arena, [t.data_ptr() - st.data_ptr() for t in tensors]
+        offs, at = [], 0
+        for t in tensors:
+            offs.append(at)
+            at += t.numel()
+        return torch.cat(tensors), offs
+
+    def _out_arena(self, out, need: int):
+        if out is None:
+            return self.torch.empty(max(need, 1), dtype=self.torch.uint8, device=self.device)
+        if out.dtype != self.torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < need:
+            raise TsqError(3, f"out must be a contiguous uint8 CUDA tensor of at least {need} bytes")
+        return out
+
+    def compress_batch(self, srcs, ext: int, out=None):
+        """Compress many 1-D uint8 CUDA tensors in one call.  Item i's container is what compress(srcs[i]) gives.  -> a list of views
+        into one output arena (`out`, or a new one of sum(batch_bound(n)) bytes), each trimmed to its container.  Views of one
+        storage are read in place; separate allocations are first packed with one torch.cat (a device copy)."""
+        arena, offs = self._arena(srcs)
+        items, at = [], 0
+        for o, t in zip(offs, srcs):
+            cap = batch_bound(t.numel())
+            items.append((o, t.numel(), at, cap))
+            at += cap
+        out = self._out_arena(out, at)
+        sizes = (C.c_uint64 * len(items))()
+        rc = self.L.tsqa_compress_batch(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), len(items), int(ext), out.data_ptr(),
+                                        out.numel(), sizes, self._stream())
+        if rc:
+            raise self._err(rc)
+        return [out[a:a + int(sizes[k])] for k, (_, _, a, _) in enumerate(items)]
+
+    def decompress_batch(self, blobs, out=None):
+        """Decompress many .tsq containers (1-D uint8 CUDA tensors) in one call.  -> a list of views into one output arena, each trimmed
+        to its item's size.  A refused item raises TsqError with .item_status (one TSQA_ERR_* or 0 per item) and .results (the views,
+        None where refused): every healthy item is still delivered."""
+        import numpy as np
+        arena, offs = self._arena(blobs)
+        # every header with one gather and one copy: the output room each item asks for (0 for a header the library will refuse)
+        lens = np.array([b.numel() for b in blobs], dtype=np.int64)
+        pos = self.torch.tensor(np.minimum(np.array(offs, dtype=np.int64)[:, None] + np.arange(16), arena.numel() - 1), device=self.device)
+        heads = arena[pos].cpu().numpy().astype(np.uint64)
+        word = lambda lo, n: sum(heads[:, lo + k] << np.uint64(8 * k) for k in range(n))
+        magic, nb, total = word(0, 4), word(4, 4), word(8, 8)
+        room = (np.maximum(lens, 16) - 16).astype(np.uint64) // np.uint64(6)
+        plausible = (lens >= 16) & (magic == 0x31515354) & (nb >= 1) & (nb <= room) & (total <= nb * np.uint64(BLOCK_SZ))
+        caps = np.where(plausible, total, 0).astype(np.int64)
+        items, at = [], 0
+        for o, n, cap in zip(offs, lens.tolist(), caps.tolist()):
+            items.append((o, n, at, cap))
+            at += cap
+        out = self._out_arena(out, at)
+        sizes = (C.c_uint64 * len(items))()
+        status = (C.c_int32 * len(items))()
+        rc = self.L.tsqa_decompress_batch(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), len(items), out.data_ptr(), out.numel(),
+                                          sizes, status, self._stream())
+        views = [out[a:a + int(sizes[k])] for k, (_, _, a, _) in enumerate(items)]
+        if rc:
+            e = self._err(rc)
+            e.item_status = [int(s) for s in status]
+            e.results = [v if s == 0 else None for v, s in zip(views, e.item_status)]
+            raise e
+        return views
+
+    def compress_batch_async(self, arena, items, ext: int, out, d_sizes) -> None:
+        """tsqa_compress_batch_async on the current stream, nothing waited for: items = (in_at, in_len, out_at, out_cap) offsets into the
+        uint8 CUDA tensors arena and out; container sizes land in d_sizes (an int64 CUDA tensor, one per item), the status in status()."""
+        rc = self.L.tsqa_compress_batch_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), len(items), int(ext), out.data_ptr(),
+                                              out.numel(), d_sizes.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def decompress_batch_async(self, arena, items, n_blocks, out, d_sizes) -> None:
+        """tsqa_decompress_batch_async on the current stream: as compress_batch_async, with each container's block count."""
+        import numpy as np
+        nb = np.ascontiguousarray(n_blocks, dtype=np.uint32)
+        rc = self.L.tsqa_decompress_batch_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), nb.ctypes.data, len(items),
+                                                out.data_ptr(), out.numel(), d_sizes.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
 
 
 # ---------------------------------------------------------------------------

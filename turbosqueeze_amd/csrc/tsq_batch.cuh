@@ -1,0 +1,106 @@
+// tsq_batch.cuh -- batches of independent items (tsqa_compress_batch*, tsqa_decompress_batch*): the container pack across encode
+// launches, the frame walk and the header gather.  The container format itself: tsq_format.h.
+#pragma once
+
+#include "tsq_common.cuh"
+#include "tsq_container.cuh"
+#include "tsq_format.h"
+
+namespace tsq {
+
+// One item of a batch as the kernels see it, planned on the host (tsqa_plan_batch): its input and output ranges, relative to the
+// batch's input and output, its first block in the batch and its block count.
+struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_t n_blocks, pad; };
+
+constexpr uint64_t kNoFrame = ~0ull;      // frame_at of a block whose frame does not fit its item: batch_pack_copy_kernel skips it
+
+// After an encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0): one lane per item with blocks in the launch,
+// items [i0, i0 + ni).  An item's frame offsets run on from where its previous launch left them (run_at[i]); its header goes out
+// with its first block, its size and the capacity check with its last.  A frame is written only if it ends inside the item's
+// capacity: frame_at[b - b0] is its offset in the output, or kNoFrame.
+__global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* __restrict__ items, uint32_t i0, uint32_t ni, uint64_t b0,
+                                                              uint32_t nb, const uint32_t* __restrict__ sizes, uint32_t ext,
+                                                              uint8_t* __restrict__ out, uint64_t* __restrict__ run_at,
+                                                              uint64_t* __restrict__ frame_at, uint64_t* __restrict__ d_sizes,
+                                                              int32_t* __restrict__ status)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= ni) return;
+    const uint32_t i = i0 + j;
+    const BatchItem it = items[i];
+    const uint64_t first = it.first_block, end = first + it.n_blocks, launch_end = b0 + nb;
+    uint8_t* const base = out + it.out_at;
+    // (the planner has left room for the header and a minimal frame per block: out_cap >= 16 + 6 * n_blocks)
+    if (first >= b0) write_header(base, it.n_blocks, it.in_len);
+    uint64_t at = first >= b0 ? kHeaderSize : run_at[i];
+    for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) {
+        const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
+        const uint64_t next = at + kFrameWordSize + sz;
+        if (next <= it.out_cap) { write_frame(base + at, sz, ext); frame_at[k] = it.out_at + at; }
+        else frame_at[k] = kNoFrame;
+        at = next;
+    }
+    run_at[i] = at;
+    if (end <= launch_end) {
+        d_sizes[i] = at;
+        if (at > it.out_cap) atomicMax(status, kErrOverflow);
+    }
+}
+
+// Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.
+// grid = (pieces, blocks of the launch).
+__global__ __launch_bounds__(256) void batch_pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,
+                                                              const uint64_t* __restrict__ frame_at, uint8_t* __restrict__ out)
+{
+    const uint32_t b = blockIdx.y;
+    const uint32_t size = sizes[b];
+    const uint32_t piece_at = blockIdx.x * kPackPiece;
+    const uint64_t at = frame_at[b];
+    if (piece_at >= size || at == kNoFrame) return;
+    pack_copy_piece(slots + (size_t)b * kSlotSize, size, out + at + kFrameWordSize, piece_at);
+}
+
+// One lane per item of a decompress batch: the item's container is walked and validated as frame_walk_kernel walks one (the
+// header, its block count against the caller's, its total against the item's capacity, every frame, lengths that add up to the
+// total).  Frame k of item i lands at frames[first_block_i + k], stream_at relative to the batch's input, out_at to its output.
+// A refused item gets d_sizes[i] = 0, *status kErrFormat, and descriptors with no stream, which every decoder refuses.
+__global__ __launch_bounds__(256) void batch_walk_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
+                                                         FrameInfo* __restrict__ frames, uint64_t* __restrict__ d_sizes,
+                                                         int32_t* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const BatchItem it = items[i];
+    const uint8_t* const c = in + it.in_at;
+    const uint64_t n = it.in_len;
+    FrameInfo* const fr = frames + it.first_block;
+    uint32_t nb = 0;
+    uint64_t total = 0, at = kHeaderSize, oat = 0;
+    bool bad = read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks || total > it.out_cap;
+    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
+        FrameInfo f;
+        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
+        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
+        fr[b] = f;
+        oat += f.out_len;
+        at += kFrameWordSize + f.stream_len;
+    }
+    if (!bad && oat != total) bad = true;
+    d_sizes[i] = bad ? 0 : total;
+    if (!bad) return;
+    for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
+    atomicMax(status, kErrFormat);
+}
+
+// The first 16 bytes of every item's container, zeros past a short one: the synchronous batch decompress reads every header with
+// one copy.  One thread per byte.
+__global__ __launch_bounds__(256) void batch_heads_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
+                                                          uint8_t* __restrict__ heads)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, i = t / kHeaderSize, k = t % kHeaderSize;
+    if (i >= n_items) return;
+    const BatchItem it = items[i];
+    heads[t] = k < it.in_len ? in[it.in_at + k] : (uint8_t)0;
+}
+
+}  // namespace tsq

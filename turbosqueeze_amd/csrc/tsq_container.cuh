@@ -48,18 +48,11 @@ __global__ __launch_bounds__(256) void pack_scan_kernel(const uint32_t* __restri
 
 // Copy each block stream from its slot to its place in the container.  Destination offsets are
 // arbitrary bytes, so each thread stores one destination-aligned 16-byte word assembled from an
-// unaligned 16-byte load; head and tail bytes go singly.  grid = (pieces, n_blocks).
+// unaligned 16-byte load; head and tail bytes go singly.  One workgroup moves the piece of the
+// stream's size bytes that starts at piece_at.
 constexpr uint32_t kPackPiece = 32768;
-__global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,
-                                                        const uint64_t* __restrict__ frame_at, uint8_t* __restrict__ container,
-                                                        const int32_t* __restrict__ status)
+__device__ __forceinline__ void pack_copy_piece(const uint8_t* src, uint32_t size, uint8_t* dst, uint32_t piece_at)
 {
-    const uint32_t b = blockIdx.y;
-    const uint32_t size = sizes[b];
-    const uint32_t piece_at = blockIdx.x * kPackPiece;
-    if (piece_at >= size || *status != 0) return;
-    const uint8_t* src = slots + (size_t)b * kSlotSize;
-    uint8_t* dst = container + frame_at[b] + 3;
     // Piece p moves the destination-aligned words [head + p*P, head + (p+1)*P); piece 0 also
     // moves the `head` bytes in front of the first aligned word.
     const uint32_t head = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u);
@@ -77,6 +70,18 @@ __global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t* __restric
     }
     // the last piece that reaches the end carries the tail bytes
     if (end == end_all) for (uint32_t k = begin + (words << 4) + threadIdx.x; k < end_all; k += 256) dst[k] = src[k];
+}
+
+// grid = (pieces, n_blocks)
+__global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,
+                                                        const uint64_t* __restrict__ frame_at, uint8_t* __restrict__ container,
+                                                        const int32_t* __restrict__ status)
+{
+    const uint32_t b = blockIdx.y;
+    const uint32_t size = sizes[b];
+    const uint32_t piece_at = blockIdx.x * kPackPiece;
+    if (piece_at >= size || *status != 0) return;
+    pack_copy_piece(slots + (size_t)b * kSlotSize, size, container + frame_at[b] + 3, piece_at);
 }
 
 // Serial frame walk of a container (tsq_threads.cpp:444-543: block k starts at 16 + sum(3+size_j)).

@@ -1991,14 +1991,20 @@ __device__ __forceinline__ void stage_account(uint32_t n, lds_u8_t* lds, uint32_
 //  vector register -- the kernel is 0.4 ms faster at 239 blocks: 88 40.5 ms, 80 41.0, 72 41.6, no cap 40.6.  Either way seven wave slots
 //  per SIMD: two workgroups share a CU with twelve wavefronts each at most; with 80 there are eight, and two workgroups of fourteen
 //  fit -- the lean layout is no faster for it, 36.2 GB/s both ways.)
-template <bool EXT, bool WINDOW>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(96))) void enc_stage_kernel(const uint8_t* __restrict__ in, uint64_t n_total, uint64_t readable, uint64_t stride,
-                                                        uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes,
-                                                        uint16_t* __restrict__ tables, int32_t* __restrict__ status)
+//
+// Where the block of a workgroup lies: how many bytes may be read from its first byte on (the encoder sees zeros beyond: the
+// look-ahead ends there), its length, the slot that holds its stream, its size and its position table, and its first byte.
+struct EncBlockAt { uint64_t avail; uint32_t n, slot; const uint8_t* src; };
+
+// One workgroup encodes one block.  The kernels below differ only in `locate() -> EncBlockAt`, called where the block is first
+// needed.
+template <bool EXT, bool WINDOW, class Locate>
+__device__ __attribute__((always_inline)) inline void enc_stage_run(uint8_t* stage_lds, Locate&& locate, uint8_t* __restrict__ slots,
+                                                                    uint32_t* __restrict__ sizes, uint16_t* __restrict__ tables,
+                                                                    int32_t* __restrict__ status)
 {
     using StageCfg = StageCfgT<WINDOW>;
-    extern __shared__ __attribute__((aligned(16))) uint8_t stage_lds[];
-    const uint32_t b = blockIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t lane = threadIdx.x & 63u;
     // Wave w of a workgroup runs on SIMD w % 4 (read back from HW_ID in the instrumented build).  WALK, the serial stage, gets a SIMD
     // almost to itself (NEAR, a light stage, shares it): the two other wavefronts of SIMD 0 leave right after the prologue.
     //   SIMD 0: WALK, NEAR      SIMD 1: ORBIT even, MATCH even, HASH, BUILDER     SIMD 2: ORBIT odd, MATCH odd, TWINS, EMIT     SIMD 3: ACCOUNT, COMMIT, IN, BUILDER 2
@@ -2015,13 +2021,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(96))) void enc
 #pragma unroll
     for (uint32_t w = 0; w < 16u; ++w) role = (threadIdx.x >> 6) == w ? (WINDOW ? role_map[w] : role_map_lean[w]) : role;
     role = uniform(role);
-    // block b of the launch lies at in + b * stride (stride = 4 MiB: one contiguous buffer; larger: a shard's blocks, each
-    // followed by its own look-ahead bytes); its length follows from the virtual total n_total = (blocks - 1) * 4 MiB + last
-    const uint64_t start = (uint64_t)b * stride;
-    const uint64_t avail = readable - start;
-    const uint64_t vstart = (uint64_t)b << kBlockBits;
-    const uint32_t n = n_total - vstart < kBlockSize ? (uint32_t)(n_total - vstart) : kBlockSize;
-    const uint8_t* src = in + start;
+    const EncBlockAt at = locate();
+    const uint32_t b = at.slot, n = at.n;
+    const uint64_t avail = at.avail;
+    const uint8_t* src = at.src;
     uint8_t* out = slots + (size_t)b * kSlotSize;
     uint16_t* table = tables + (size_t)b * kHashEntries;
 
@@ -2058,6 +2061,38 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(96))) void enc
     if (blockIdx.x == 0 && lane == 0) g_enc_spins[threadIdx.x >> 6] = reinterpret_cast<uint32_t*>(stage_lds + StageCfg::off_ctl)[48u + (threadIdx.x >> 6)];
     if (blockIdx.x == 0 && role == kRoleEmit && lane == 0) for (uint32_t q = 0; q < 4u; ++q) g_enc_spins[16u + q] = reinterpret_cast<uint32_t*>(stage_lds + StageCfg::off_ctl)[44u + q];   // (EMIT leaves last)
 #endif
+}
+
+template <bool EXT, bool WINDOW>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(96))) void enc_stage_kernel(const uint8_t* __restrict__ in, uint64_t n_total, uint64_t readable, uint64_t stride,
+                                                        uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes,
+                                                        uint16_t* __restrict__ tables, int32_t* __restrict__ status)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage_lds[];
+    // block b of the launch lies at in + b * stride (stride = 4 MiB: one contiguous buffer; larger: a shard's blocks, each
+    // followed by its own look-ahead bytes); its length follows from the virtual total n_total = (blocks - 1) * 4 MiB + last
+    enc_stage_run<EXT, WINDOW>(stage_lds, [&]() {
+        const uint32_t b = blockIdx.x;
+        const uint64_t start = (uint64_t)b * stride;
+        const uint64_t vstart = (uint64_t)b << kBlockBits;
+        return EncBlockAt{readable - start, n_total - vstart < kBlockSize ? (uint32_t)(n_total - vstart) : kBlockSize, b, in + start};
+    }, slots, sizes, tables, status);
+}
+
+// One block of a batch of independent items (tsqa_compress_batch_async): where it starts in the batch's input, the bytes of ITS
+// item from there on (the look-ahead never reaches the next item), its length and its slot in the launch.
+struct EncBatchBlock { uint64_t src_at, avail; uint32_t n, slot; };
+
+template <bool EXT, bool WINDOW>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(96))) void enc_batch_kernel(const uint8_t* __restrict__ in, const EncBatchBlock* __restrict__ blocks,
+                                                        uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes,
+                                                        uint16_t* __restrict__ tables, int32_t* __restrict__ status)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t stage_lds[];
+    enc_stage_run<EXT, WINDOW>(stage_lds, [&]() {
+        const EncBatchBlock d = blocks[blockIdx.x];
+        return EncBlockAt{d.avail, uniform(d.n), uniform(d.slot), in + d.src_at};
+    }, slots, sizes, tables, status);
 }
 
 }  // namespace tsq

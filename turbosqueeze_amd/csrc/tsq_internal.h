@@ -11,6 +11,18 @@
 
 namespace tsq { struct FrameInfo; }
 
+// Descriptors a call plans on the host for its kernels (range-read items, batch descriptors): two slots, used in turn, each a pinned
+// host buffer and its copy on the device.  A slot is reused once the call that used it has finished (done[k], recorded behind its
+// last kernel): two calls can be in flight.
+struct tsqa_uploads {
+    void* host[2] = {nullptr, nullptr};
+    void* dev[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    hipEvent_t done[2] = {nullptr, nullptr};
+    bool pending[2] = {false, false};
+    int next = 0;
+};
+
 struct tsqa_ctx {
     int device = 0;
     int n_cus = 0;
@@ -33,14 +45,13 @@ struct tsqa_ctx {
     const void* sharded_streams = nullptr;
     void* sharded_out = nullptr;
     void forget_sharded() { sharded_n_local = 0; sharded_streams = nullptr; sharded_out = nullptr; }
-    // range reads: two slots, used in turn, of items planned on the host (pinned) and their copy on the device.  A slot is reused
-    // once the read that used it has finished (items_done[k], recorded behind its kernel): two reads can be in flight.
-    tsqa_range_item* host_items[2] = {nullptr, nullptr};
-    tsqa_range_item* range_items[2] = {nullptr, nullptr};
-    size_t cap_items[2] = {0, 0};
-    hipEvent_t items_done[2] = {nullptr, nullptr};
-    bool items_pending[2] = {false, false};
-    int items_slot = 0;
+    tsqa_uploads range_up, batch_up;           // range-read items; batch descriptors
+    // batches: per item, the running frame offset of a compress batch across its launches, and the sizes and headers the
+    // synchronous forms read back
+    uint64_t* batch_at = nullptr;
+    uint64_t* batch_sizes = nullptr;
+    uint8_t* batch_heads = nullptr;
+    size_t cap_batch = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     uint32_t* duo_ring = nullptr;      // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     uint32_t* duo_flags = nullptr;     // and their progress counters
@@ -64,7 +75,9 @@ struct tsqa_ctx {
     int reserve(size_t n_blocks, bool want_tables, bool want_slots = true);
     int reserve_duo(size_t n_blocks);
     int reserve_host_frames(size_t n);
-    int reserve_range_items(size_t n, int* slot);
+    // the next slot of `u`, once the call that used it has finished, with room for `bytes`
+    int reserve_upload(tsqa_uploads& u, size_t bytes, int* slot);
+    int reserve_batch(size_t n_items);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]

@@ -91,6 +91,35 @@ inline int launch_encode_kernels(tsqa_ctx* c, const uint8_t* in, size_t n, size_
 }
 #undef TSQ_LAUNCH_ENC
 
+#define TSQ_LAUNCH_BATCH(KERNEL, THREADS, LDS)                                                                                      \
+    hipLaunchKernelGGL((KERNEL), dim3(nb), dim3(THREADS), (LDS), s, in, blocks, slots, sizes, c->tables, status)
+
+// Encode nb blocks of a batch (tsqa_compress_batch_async) from their descriptors: the staged encoder in the layout
+// launch_encode_kernels takes for nb blocks.  Encoder variants 0, 6 and 7 only.
+inline int launch_batch_encode_kernels(tsqa_ctx* c, const uint8_t* in, const EncBatchBlock* blocks, uint32_t nb, uint32_t ext,
+                                       uint8_t* slots, uint32_t* sizes, int32_t* status, hipStream_t s)
+{
+    static std::atomic<uint64_t> attr_devices{0};
+    {
+        const void* const fns[4] = {reinterpret_cast<const void*>(enc_batch_kernel<true, true>), reinterpret_cast<const void*>(enc_batch_kernel<false, true>),
+                                    reinterpret_cast<const void*>(enc_batch_kernel<true, false>), reinterpret_cast<const void*>(enc_batch_kernel<false, false>)};
+        const uint32_t bytes[4] = {StageCfgT<true>::total, StageCfgT<true>::total, StageCfgT<false>::total, StageCfgT<false>::total};
+        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
+    }
+    const int v = c->enc_variant;
+    if (v != 0 && v != 6 && v != 7) { c->set_error("kernel variant %d does not encode batches (0, 6 and 7 do)", v); return TSQA_ERR_ARG; }
+    const bool lean = v == 6 || (v == 0 && nb > (uint32_t)c->n_cus);
+    if (lean) {
+        if (ext) TSQ_LAUNCH_BATCH((enc_batch_kernel<true, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
+        else     TSQ_LAUNCH_BATCH((enc_batch_kernel<false, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
+    } else {
+        if (ext) TSQ_LAUNCH_BATCH((enc_batch_kernel<true, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
+        else     TSQ_LAUNCH_BATCH((enc_batch_kernel<false, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
+    }
+    return 0;
+}
+#undef TSQ_LAUNCH_BATCH
+
 inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_blocks, uint8_t* out,
                                  int32_t* status, hipStream_t s, int variant = -1)
 {

@@ -7,6 +7,7 @@
 // There is no host computation on the data path and no CPU fallback.
 #include "tsq_internal.h"
 
+#include "tsq_batch.cuh"
 #include "tsq_common.cuh"
 #include "tsq_container.cuh"
 #include "tsq_format.h"
@@ -136,11 +137,13 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     (void)hipFree(c->duo_ring); (void)hipFree(c->duo_flags);
     if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
-    for (int k = 0; k < 2; ++k) {
-        (void)hipFree(c->range_items[k]);
-        if (c->host_items[k]) (void)hipHostFree(c->host_items[k]);
-        if (c->items_done[k]) (void)hipEventDestroy(c->items_done[k]);
-    }
+    for (tsqa_uploads* u : {&c->range_up, &c->batch_up})
+        for (int k = 0; k < 2; ++k) {
+            (void)hipFree(u->dev[k]);
+            if (u->host[k]) (void)hipHostFree(u->host[k]);
+            if (u->done[k]) (void)hipEventDestroy(u->done[k]);
+        }
+    (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_heads);
     delete c;
 }
 
@@ -213,24 +216,40 @@ int tsqa_ctx::reserve_host_frames(size_t n)
     return TSQA_OK;
 }
 
-// Range-read items: the next of the two slots, once the read that used it last has finished, grown on demand.
-int tsqa_ctx::reserve_range_items(size_t n, int* slot)
+// Planned descriptors: the next of the two slots, once the call that used it last has finished, grown on demand.
+int tsqa_ctx::reserve_upload(tsqa_uploads& u, size_t bytes, int* slot)
 {
     (void)hipSetDevice(device);
-    const int k = items_slot;
-    items_slot ^= 1;
-    if (items_pending[k]) { (void)hipEventSynchronize(items_done[k]); items_pending[k] = false; }
-    if (!items_done[k]) TSQ_HIP(this, hipEventCreateWithFlags(&items_done[k], hipEventDisableTiming));
-    if (n > cap_items[k]) {
-        if (host_items[k]) (void)hipHostFree(host_items[k]);
-        (void)hipFree(range_items[k]);
-        host_items[k] = nullptr; range_items[k] = nullptr; cap_items[k] = 0;
-        size_t want = 256; while (want < n) want *= 2;
-        TSQ_HIP(this, hipHostMalloc(reinterpret_cast<void**>(&host_items[k]), want * sizeof(tsqa_range_item), hipHostMallocDefault));
-        TSQ_HIP(this, hipMalloc(&range_items[k], want * sizeof(tsqa_range_item)));
-        cap_items[k] = want;
+    const int k = u.next;
+    u.next ^= 1;
+    if (u.pending[k]) { (void)hipEventSynchronize(u.done[k]); u.pending[k] = false; }
+    if (!u.done[k]) TSQ_HIP(this, hipEventCreateWithFlags(&u.done[k], hipEventDisableTiming));
+    if (bytes > u.cap[k]) {
+        if (u.host[k]) (void)hipHostFree(u.host[k]);
+        (void)hipFree(u.dev[k]);
+        u.host[k] = nullptr; u.dev[k] = nullptr; u.cap[k] = 0;
+        size_t want = 4096; while (want < bytes) want *= 2;
+        TSQ_HIP(this, hipHostMalloc(&u.host[k], want, hipHostMallocDefault));
+        TSQ_HIP(this, hipMalloc(&u.dev[k], want));
+        u.cap[k] = want;
     }
     *slot = k;
+    return TSQA_OK;
+}
+
+// Per-item scratch of the batch entry points (tsq_internal.h), grown on demand.
+int tsqa_ctx::reserve_batch(size_t n_items)
+{
+    (void)hipSetDevice(device);
+    if (n_items <= cap_batch) return TSQA_OK;
+    (void)hipStreamSynchronize(stream);
+    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_heads);
+    batch_at = nullptr; batch_sizes = nullptr; batch_heads = nullptr; cap_batch = 0;
+    size_t want = 256; while (want < n_items) want *= 2;
+    TSQ_HIP(this, hipMalloc(&batch_at, want * sizeof(uint64_t)));
+    TSQ_HIP(this, hipMalloc(&batch_sizes, want * sizeof(uint64_t)));
+    TSQ_HIP(this, hipMalloc(&batch_heads, want * kHeaderSize));
+    cap_batch = want;
     return TSQA_OK;
 }
 
@@ -798,19 +817,20 @@ extern "C" int tsqa_decompress_ranges_async(tsqa_ctx* c, const tsqa_index* idx, 
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     (void)hipSetDevice(c->device);
     int k = 0;
-    if (int rc = c->reserve_range_items(n_items ? n_items : 1, &k)) return rc;
-    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, c->host_items[k], (uint32_t)c->cap_items[k], &n_items, &why)) {
+    if (int rc = c->reserve_upload(c->range_up, (size_t)(n_items ? n_items : 1) * sizeof(tsqa_range_item), &k)) return rc;
+    tsqa_range_item* const host_items = static_cast<tsqa_range_item*>(c->range_up.host[k]);
+    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, host_items, (uint32_t)(c->range_up.cap[k] / sizeof(tsqa_range_item)), &n_items, &why)) {
         c->set_error("decompress_ranges: %s", why);
         return TSQA_ERR_ARG;
     }
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     if (n_items == 0) return TSQA_OK;
-    TSQ_HIP(c, hipMemcpyAsync(c->range_items[k], c->host_items[k], (size_t)n_items * sizeof(tsqa_range_item), hipMemcpyHostToDevice, s));
-    const int rc = launch_range_kernel(c, idx->container, idx->frames, idx->n_blocks, reinterpret_cast<const RangeItem*>(c->range_items[k]),
+    TSQ_HIP(c, hipMemcpyAsync(c->range_up.dev[k], host_items, (size_t)n_items * sizeof(tsqa_range_item), hipMemcpyHostToDevice, s));
+    const int rc = launch_range_kernel(c, idx->container, idx->frames, idx->n_blocks, static_cast<const RangeItem*>(c->range_up.dev[k]),
                                        n_items, static_cast<uint8_t*>(d_out), d_status, s);
     // (behind the kernel: neither copy of the items is touched again before the read that uses them has finished)
-    TSQ_HIP(c, hipEventRecord(c->items_done[k], s));
-    c->items_pending[k] = true;
+    TSQ_HIP(c, hipEventRecord(c->range_up.done[k], s));
+    c->range_up.pending[k] = true;
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
@@ -827,6 +847,245 @@ extern "C" int tsqa_decompress_ranges(tsqa_ctx* c, const tsqa_index* idx, const 
     TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "decompress_ranges");
+}
+
+// ---- batches: many independent items at offsets in one input and one output buffer ----
+
+enum BatchPlan { kPlanCompress, kPlanDecompress, kPlanRangesOnly };
+
+// tsqa_plan_batch, with the reason for a refusal.  kPlanRangesOnly: the ranges and input lengths of a decompress batch whose block
+// counts are not known yet (first_block is not written).
+static int plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_size, size_t out_size, const uint32_t* n_blocks,
+                      uint64_t* first_block, const char** why, BatchPlan mode)
+{
+    *why = "";
+    if (!items || n_items == 0) { *why = "no items"; return TSQA_ERR_ARG; }
+    auto blocks_of = [&](uint32_t i) -> uint64_t {
+        return mode == kPlanCompress ? items[i].in_len / kBlockSize + (items[i].in_len % kBlockSize != 0) : mode == kPlanDecompress ? n_blocks[i] : 0;
+    };
+    std::vector<std::pair<uint64_t, uint64_t>> dst;
+    dst.reserve(n_items);
+    uint64_t blocks = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const tsqa_batch_item& x = items[i];
+        const uint64_t nb = blocks_of(i);
+        if (x.in_len == 0) { *why = "an item is empty"; return TSQA_ERR_ARG; }
+        if (x.in_len > in_size || x.in_at > in_size - x.in_len) { *why = "an input range ends past in_size"; return TSQA_ERR_ARG; }
+        if (x.out_cap > out_size || x.out_at > out_size - x.out_cap) { *why = "an output range ends past out_size"; return TSQA_ERR_ARG; }
+        if (mode == kPlanCompress && x.out_cap < kHeaderSize + kMinFrameSize * nb) { *why = "an output range holds less than 16 + 6 bytes per block"; return TSQA_ERR_ARG; }
+        if (mode != kPlanCompress && x.in_len < kHeaderSize) { *why = "an input range is shorter than a header"; return TSQA_ERR_ARG; }
+        if (mode == kPlanDecompress && (nb == 0 || nb > (x.in_len - kHeaderSize) / kMinFrameSize)) { *why = "a block count that the container cannot hold"; return TSQA_ERR_ARG; }
+        if (x.out_cap) dst.emplace_back(x.out_at, x.out_cap);
+        blocks += nb;
+    }
+    // two items writing the same bytes would race: output ranges may touch, not overlap (input ranges may)
+    std::sort(dst.begin(), dst.end());
+    for (size_t k = 1; k < dst.size(); ++k)
+        if (dst[k - 1].first + dst[k - 1].second > dst[k].first) { *why = "two output ranges overlap"; return TSQA_ERR_ARG; }
+    if (blocks > 0xFFFFFFFFull) { *why = "more than 2^32 - 1 blocks"; return TSQA_ERR_ARG; }
+    if (mode == kPlanRangesOnly) return TSQA_OK;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_items; ++i) { first_block[i] = at; at += blocks_of(i); }
+    first_block[n_items] = at;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_size, size_t out_size, const uint32_t* n_blocks,
+                               uint64_t* first_block)
+{
+    const char* why;
+    if (!first_block) return TSQA_ERR_ARG;
+    return plan_batch(items, n_items, in_size, out_size, n_blocks, first_block, &why, n_blocks ? kPlanDecompress : kPlanCompress);
+}
+
+extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                         uint32_t ext, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+{
+    static_assert(sizeof(tsqa_batch_item) == 32 && sizeof(BatchItem) == 48 && sizeof(EncBatchBlock) == 24, "descriptor layouts");
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_in || !d_out || !d_sizes || !d_status) { c->set_error("compress_batch: null pointer"); return TSQA_ERR_ARG; }
+    const int v = c->enc_variant;
+    if (v != 0 && v != 6 && v != 7) { c->set_error("compress_batch: encoder variant %d does not take batches (0, 6 and 7 do)", v); return TSQA_ERR_ARG; }
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanCompress)) { c->set_error("compress_batch: %s", why); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    (void)hipSetDevice(c->device);
+    const uint64_t n_blocks = first[n_items];
+    // A launch takes at most 2 x n_cus blocks, the lean layout's chip-filling count: the scratch -- a slot and a position table per
+    // block -- stays bounded whatever the batch holds.  Items may span launches.
+    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), bytes = item_bytes + n_blocks * sizeof(EncBatchBlock);
+    int k = 0;
+    if (int rc = c->reserve_upload(c->batch_up, bytes, &k)) return rc;
+    if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true)) return rc;
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    uint8_t* const host = static_cast<uint8_t*>(c->batch_up.host[k]);
+    BatchItem* const hi = reinterpret_cast<BatchItem*>(host);
+    EncBatchBlock* const hb = reinterpret_cast<EncBatchBlock*>(host + item_bytes);
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const tsqa_batch_item& x = items[i];
+        const uint32_t nb = (uint32_t)(first[i + 1] - first[i]);
+        hi[i] = BatchItem{x.in_at, x.in_len, x.out_at, x.out_cap, first[i], nb, 0u};
+        for (uint32_t j = 0; j < nb; ++j) {
+            const uint64_t b = first[i] + j, off = (uint64_t)j * kBlockSize, left = x.in_len - off;
+            hb[b] = EncBatchBlock{x.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
+        }
+    }
+    const BatchItem* const di = static_cast<const BatchItem*>(c->batch_up.dev[k]);
+    const EncBatchBlock* const db = reinterpret_cast<const EncBatchBlock*>(static_cast<const uint8_t*>(c->batch_up.dev[k]) + item_bytes);
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], host, bytes, hipMemcpyHostToDevice, s));
+    const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
+    int rc = TSQA_OK;
+    for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget) {
+        const uint32_t nb = (uint32_t)(n_blocks - b0 < budget ? n_blocks - b0 : budget);
+        // the items with blocks in this launch: from the one that holds block b0 to the last that starts before b0 + nb
+        const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
+        const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
+        const bool timed = c->prof_begin(0, s);
+        rc = launch_batch_encode_kernels(c, in, db + b0, nb, ext, c->slots, c->sizes, d_status, s);
+        if (rc) { if (timed) c->prof_used[0]--; break; }
+        if (timed) c->prof_end(0, s);
+        hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
+                           c->batch_at, c->frame_at, d_sizes, d_status);
+        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out);
+    }
+    // (behind the last kernel: neither copy of the descriptors is touched again before the batch that uses them has finished)
+    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
+    c->batch_up.pending[k] = true;
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items, uint32_t ext,
+                                   void* d_out, size_t out_size, uint64_t* sizes, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!sizes) { c->set_error("compress_batch: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    int rc = tsqa_compress_batch_async(c, d_in, in_size, items, n_items, ext, d_out, out_size, c->batch_sizes, c->d_status, s);
+    if (rc) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "compress_batch");
+}
+
+// (variant < 0: the context's decode variant; the synchronous form's retry after TSQA_ERR_STALL passes 4)
+static int decompress_batch_async_impl(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                       uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, hipStream_t s,
+                                       int variant)
+{
+    if (!d_in || !d_out || !d_sizes || !d_status || !n_blocks) { c->set_error("decompress_batch: null pointer"); return TSQA_ERR_ARG; }
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, kPlanDecompress)) { c->set_error("decompress_batch: %s", why); return TSQA_ERR_ARG; }
+    (void)hipSetDevice(c->device);
+    const uint32_t total_blocks = (uint32_t)first[n_items];
+    int k = 0;
+    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
+    if (int rc = c->reserve(total_blocks, false, false)) return rc;
+    c->forget_sharded();                                 // the frame walk below overwrites c->frames
+    BatchItem* const hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    for (uint32_t i = 0; i < n_items; ++i)
+        hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(batch_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in),
+                       static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->frames, d_sizes, d_status);
+    // one decode over every frame of the batch (launch_decode_kernels picks the decoder by the block count, as for one container)
+    const int rc = c->launch_decode_frames(d_in, c->frames, total_blocks, d_out, d_status, s, variant);
+    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
+    c->batch_up.pending[k] = true;
+    return rc;
+}
+
+extern "C" int tsqa_decompress_batch_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                           uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return decompress_batch_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, d_sizes, d_status, s, -1);
+}
+
+// The synchronous form's decode of a (sub-)batch: the status lands in *st, the items' sizes in sizes[]; after TSQA_ERR_STALL once
+// more with one workgroup per block.  The return value is a call error (nothing decoded) or TSQA_OK.
+static int decompress_batch_wait(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                 uint32_t n_items, void* d_out, size_t out_size, uint64_t* sizes, int32_t* st, hipStream_t s)
+{
+    for (int variant : {-1, 4}) {
+        if (int rc = decompress_batch_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, c->batch_sizes, c->d_status, s, variant)) return rc;
+        TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipMemcpyAsync(st, c->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipStreamSynchronize(s));
+        if (*st != kErrStall) break;
+    }
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                     void* d_out, size_t out_size, uint64_t* sizes, int32_t* item_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_in || !d_out || !sizes) { c->set_error("decompress_batch: null pointer"); return TSQA_ERR_ARG; }
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, nullptr, nullptr, &why, kPlanRangesOnly)) { c->set_error("decompress_batch: %s", why); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    (void)hipSetDevice(c->device);
+    std::vector<int32_t> own;
+    if (!item_status) { own.resize(n_items); item_status = own.data(); }
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    // every header with one gather kernel and one copy
+    int k = 0;
+    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
+    BatchItem* const hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, 0, 0, 0};
+    std::vector<uint8_t> heads((size_t)n_items * kHeaderSize);
+    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(batch_heads_kernel, dim3((uint32_t)(((uint64_t)n_items * kHeaderSize + 255u) / 256u)), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(d_in), static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->batch_heads);
+    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
+    c->batch_up.pending[k] = true;
+    TSQ_HIP(c, hipMemcpyAsync(heads.data(), c->batch_heads, heads.size(), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    // items whose header is refused are reported and left out of the launch
+    std::vector<tsqa_batch_item> ok_items;
+    std::vector<uint32_t> ok_blocks, ok_index;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        sizes[i] = 0;
+        uint32_t nb = 0; uint64_t total = 0;
+        if (read_header(&heads[(size_t)i * kHeaderSize], items[i].in_len, &nb, &total) != kHeaderOk) item_status[i] = TSQA_ERR_FORMAT;
+        else if (total > items[i].out_cap) item_status[i] = TSQA_ERR_ARG;            // (as tsqa_decompress_device refuses it)
+        else { item_status[i] = TSQA_OK; ok_items.push_back(items[i]); ok_blocks.push_back(nb); ok_index.push_back(i); }
+    }
+    if (!ok_items.empty()) {
+        const uint32_t m = (uint32_t)ok_items.size();
+        std::vector<uint64_t> got(m);
+        int32_t st = 0;
+        if (int rc = decompress_batch_wait(c, d_in, in_size, ok_items.data(), ok_blocks.data(), m, d_out, out_size, got.data(), &st, s)) return rc;
+        if (st == 0) {
+            for (uint32_t j = 0; j < m; ++j) sizes[ok_index[j]] = got[j];
+        } else {
+            // (the error path only) the items at fault are found by decoding each alone; every healthy item's bytes are delivered
+            for (uint32_t j = 0; j < m; ++j) {
+                uint64_t one = 0;
+                if (int rc = decompress_batch_wait(c, d_in, in_size, &ok_items[j], &ok_blocks[j], 1, d_out, out_size, &one, &st, s)) return rc;
+                item_status[ok_index[j]] = st;
+                sizes[ok_index[j]] = st ? 0 : one;
+            }
+        }
+    }
+    int32_t worst = TSQA_OK;
+    uint32_t refused = 0;
+    for (uint32_t i = 0; i < n_items; ++i) { worst = std::max(worst, item_status[i]); refused += item_status[i] != TSQA_OK; }
+    if (worst) c->set_error("decompress_batch: %u of %u items refused (worst status %d)", refused, n_items, worst);
+    return worst;
 }
 
 // ---- the second roofline denominator: what a plain device copy reaches on this GPU ----
