@@ -307,6 +307,54 @@ int tsqa_decompress_batch_async(tsqa_ctx *ctx, const void *d_in, size_t in_size,
 int tsqa_decompress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
                           void *d_out, size_t out_size, uint64_t *sizes, int32_t *item_status, void *hip_stream);
 
+/*
+ * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
+ * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
+ * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.
+ *
+ * tsqa_index_create_batch: synchronous, like tsqa_index_create, and at a constant number of launches, copies and waits whatever
+ *   n_items is (one header gather, one frame walk with a lane per item, one frame table).  items: the items of a decompress batch
+ *   (in_at, in_len locate container i in d_in; out_at, out_cap are not used).  Every container is validated as
+ *   tsqa_index_create validates one; a refused item gets TSQA_ERR_FORMAT in item_status (host, may be NULL) and the healthy items
+ *   are indexed.  The index is made whenever the arguments are valid (tsqa_plan_batch's checks of the input ranges: TSQA_ERR_ARG
+ *   and no index otherwise); the return value is the largest item status.  tsqa_index_blocks / tsqa_index_total of such an index:
+ *   the healthy items' blocks and the sum of their totals, and tsqa_decompress_ranges* on it reads the concatenation of the healthy
+ *   items' data in item order.  The same tsqa_index type: tsqa_index_destroy frees it.
+ */
+int      tsqa_index_create_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items,
+                                 uint32_t n_items, tsqa_index **out, int32_t *item_status);
+uint32_t tsqa_index_items(const tsqa_index *idx);                   /* 1 for an index made by tsqa_index_create (0 for NULL) */
+uint64_t tsqa_index_item_total(const tsqa_index *idx, uint32_t i);  /* item i's uncompressed size; 0 when refused */
+int      tsqa_index_item_status(const tsqa_index *idx, uint32_t i); /* TSQA_OK or TSQA_ERR_FORMAT (TSQA_ERR_ARG: no such item) */
+
+/* bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at */
+typedef struct tsqa_item_range { uint32_t item, pad; uint64_t offset, length, out_at; } tsqa_item_range;
+/* one decode: block `block`, its items [first, first + count) of the item array (ascending lo), decoded up to `hi` */
+typedef struct tsqa_block_group { uint32_t block, first, count, hi; } tsqa_block_group;
+
+/* Host-only (no device), like tsqa_plan_ranges: out_start[0..n_blocks] as there; item i owns the blocks
+ * [item_first_block[i], item_first_block[i + 1]) (n_items + 1 entries, from 0 to n_blocks; a refused item owns none).  The ranges
+ * are cut into one item per block they touch, the items are sorted by (block, lo), and every touched block gets one group.
+ * Sources may overlap freely (two ranges may read the same bytes); destinations may not.  Zero-length ranges give nothing.
+ * TSQA_ERR_ARG, with nothing written to items and groups, for: an item number >= n_items, a range of a refused item, a range
+ * past its item's total, out_at + length > out_cap, destinations that overlap, or arrays too small (*n_range_items and *n_groups
+ * then hold the counts needed). */
+int tsqa_plan_item_ranges(const uint64_t *out_start, uint32_t n_blocks, const uint64_t *item_first_block, uint32_t n_items,
+                          const tsqa_item_range *ranges, uint32_t n_ranges, size_t out_cap,
+                          tsqa_range_item *items, uint32_t cap_items, uint32_t *n_range_items,
+                          tsqa_block_group *groups, uint32_t cap_groups, uint32_t *n_groups);
+
+/* Read the ranges (a host array) into d_out: one workgroup per touched block decodes it once, up to the last byte any of its
+ * ranges needs, and writes every range's bytes as the chunks that hold them appear.  Planning, the status word, stream ordering
+ * and repeated calls on one stream: exactly as tsqa_decompress_ranges*.  The index may also be one made by tsqa_index_create
+ * (a batch of one item).
+ * Trust: as for range reads, damage beyond the last chunk a group needs may go unreported; when *d_status is nonzero the
+ * destinations' contents are undefined, and nothing outside them has been written. */
+int tsqa_decompress_item_ranges_async(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_item_range *ranges, uint32_t n_ranges,
+                                      void *d_out, size_t out_cap, int32_t *d_status, void *hip_stream);
+int tsqa_decompress_item_ranges(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_item_range *ranges, uint32_t n_ranges,
+                                void *d_out, size_t out_cap, void *hip_stream);
+
 /* =====================================================================================
  * (1) The reference API (turbosqueeze.h:441-674), C-callable subset
  * ================================================================================== */

@@ -7,8 +7,11 @@ if the shared library or a gfx950 device is missing, calls raise.
 from .api import (  # noqa: F401
     BLOCK_SZ,
     OUTPUT_SZ,
+    BatchIndex,
     BatchItem,
+    BlockGroup,
     DeviceCodec,
+    ItemRange,
     Range,
     RangeIndex,
     RangeItem,
@@ -20,6 +23,7 @@ from .api import (  # noqa: F401
     lib,
     lib_path,
     plan_batch,
+    plan_item_ranges,
     plan_ranges,
     source_fingerprint,
     tsq_compress_mt,

@@ -179,6 +179,20 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_batch_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_batch.restype = C.c_int
     L.tsqa_decompress_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_index_create_batch.restype = C.c_int
+    L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
+    L.tsqa_index_items.restype = C.c_uint32
+    L.tsqa_index_items.argtypes = [vp]
+    L.tsqa_index_item_total.restype = C.c_uint64
+    L.tsqa_index_item_total.argtypes = [vp, C.c_uint32]
+    L.tsqa_index_item_status.restype = C.c_int
+    L.tsqa_index_item_status.argtypes = [vp, C.c_uint32]
+    L.tsqa_plan_item_ranges.restype = C.c_int
+    L.tsqa_plan_item_ranges.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_size_t, vp, C.c_uint32, u32p, vp, C.c_uint32, u32p]
+    L.tsqa_decompress_item_ranges_async.restype = C.c_int
+    L.tsqa_decompress_item_ranges_async.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
+    L.tsqa_decompress_item_ranges.restype = C.c_int
+    L.tsqa_decompress_item_ranges.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
     L.tsqCompress.restype = None
     L.tsqCompress.argtypes = [vp, vp, C.c_bool, C.c_uint32]
     L.tsqDecompress.restype = None
@@ -332,6 +346,129 @@ def batch_bound(n: int) -> int:
         cap += 3 + min(OUTPUT_SZ, 11 + k + (k >> 3) + (k >> 1))
         left -= k
     return cap
+
+
+class ItemRange(C.Structure):
+    """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
+    _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
+
+
+class BlockGroup(C.Structure):
+    """tsqa_block_group: block `block` is decoded once, up to `hi`, for the range items [first, first + count)"""
+    _fields_ = [("block", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("hi", C.c_uint32)]
+
+
+def _item_range_array(ranges):
+    """(item, offset, length, out_at) quadruples -> a ctypes tsqa_item_range array"""
+    arr = (ItemRange * max(len(ranges), 1))()
+    for k, (item, off, ln, at) in enumerate(ranges):
+        arr[k] = ItemRange(int(item), 0, int(off), int(ln), int(at))
+    return arr
+
+
+def plan_item_ranges(out_start, item_first_block, ranges, out_cap: int, cap_items=None, cap_groups=None):
+    """tsqa_plan_item_ranges (host only): out_start as for plan_ranges; item_first_block = each item's first block, then the block
+    count; ranges = (item, offset, length, out_at).  -> (range items (block, lo, hi, out_at) sorted by (block, lo), groups
+    (block, first, count, hi), one per touched block).  Raises TsqError(3) when the call is refused; .needed then holds the counts
+    the library reported (None when it reported none)."""
+    import numpy as np
+    starts = np.ascontiguousarray(out_start, dtype=np.uint64)
+    first = np.ascontiguousarray(item_first_block, dtype=np.uint64)
+    rr = _item_range_array(ranges)
+    ni, ng = C.c_uint32(0xFFFFFFFF), C.c_uint32(0xFFFFFFFF)
+
+    def call(items, ci, groups, cg):
+        return lib().tsqa_plan_item_ranges(starts.ctypes.data, starts.size - 1, first.ctypes.data, first.size - 1, rr, len(ranges), out_cap,
+                                           items, ci, C.byref(ni), groups, cg, C.byref(ng))
+
+    def refuse(rc):
+        e = TsqError(rc, "tsqa_plan_item_ranges refused the ranges")
+        e.needed = None if ni.value == 0xFFFFFFFF else (ni.value, ng.value)
+        return e
+
+    if cap_items is None or cap_groups is None:
+        rc = call(None, 0, None, 0)
+        if rc and (ni.value == 0xFFFFFFFF or (ni.value == 0 and ng.value == 0)):
+            raise refuse(rc)
+        cap_items = ni.value if cap_items is None else cap_items
+        cap_groups = ng.value if cap_groups is None else cap_groups
+        ni.value = ng.value = 0xFFFFFFFF
+    items = (RangeItem * max(cap_items, 1))()
+    groups = (BlockGroup * max(cap_groups, 1))()
+    rc = call(items, cap_items, groups, cap_groups)
+    if rc:
+        raise refuse(rc)
+    return ([(items[k].block, items[k].lo, items[k].hi, items[k].out_at) for k in range(ni.value)],
+            [(groups[k].block, groups[k].first, groups[k].count, groups[k].hi) for k in range(ng.value)])
+
+
+class BatchIndex(RangeIndex):
+    """One index over a batch of .tsq containers in one arena (tsqa_index_create_batch), for reads addressed by item: a block that
+    several ranges of a call touch is decoded once.  Refused containers are reported per item (item_status) and cannot be read; the
+    inherited flat reads (read_into / read_many with offsets) address the concatenation of the healthy items' data.  Holds a
+    reference to the arena, which must not change while the index is used."""
+
+    def __init__(self, codec: "DeviceCodec", arena, spans):
+        self.codec, self.blob, self.L = codec, arena, codec.L
+        self.h = C.c_void_p()
+        codec.torch.cuda.current_stream(codec.device).synchronize()
+        status = (C.c_int32 * len(spans))()
+        rc = self.L.tsqa_index_create_batch(codec.h, arena.data_ptr(), arena.numel(), _batch_array([(a, n, 0, 0) for a, n in spans]),
+                                            len(spans), C.byref(self.h), status)
+        if not self.h:
+            raise codec._err(rc)
+        self.n_blocks = int(self.L.tsqa_index_blocks(self.h))
+        self.total = int(self.L.tsqa_index_total(self.h))
+        self.items = int(self.L.tsqa_index_items(self.h))
+        self.worst_status = rc
+
+    def item_total(self, i: int) -> int:
+        return int(self.L.tsqa_index_item_total(self.h, i))
+
+    def item_status(self, i: int) -> int:
+        return int(self.L.tsqa_index_item_status(self.h, i))
+
+    def read_items_into(self, ranges, out, sync: bool = True) -> None:
+        """The raw call: ranges = (item, offset, length, out_at), bytes land at out[out_at:].  sync=False: on the current stream,
+        nothing waited for, the status in codec.status()."""
+        rr = _item_range_array(ranges)
+        if sync:
+            rc = self.L.tsqa_decompress_item_ranges(self.codec.h, self.h, rr, len(ranges), out.data_ptr(), out.numel(), self.codec._stream())
+        else:
+            rc = self.L.tsqa_decompress_item_ranges_async(self.codec.h, self.h, rr, len(ranges), out.data_ptr(), out.numel(),
+                                                          self.codec._status.data_ptr(), self.codec._stream())
+        if rc:
+            raise self.codec._err(rc)
+
+    def read(self, item: int, offset: int, length: int, out=None):
+        """Bytes [offset, offset + length) of item `item`'s data -> a uint8 CUDA tensor (out[:length] when out is given)."""
+        out = self._out(out, length)
+        self.read_items_into([(item, offset, length, 0)], out)
+        return out[:length]
+
+    def _packed_items(self, ranges, out):
+        at, quads = 0, []
+        for item, off, ln in ranges:
+            quads.append((item, off, ln, at))
+            at += int(ln)
+        out = self._out(out, at)
+        return quads, out, at, [out[a:a + int(ln)] for (_, _, ln, a) in quads]
+
+    def read_many(self, ranges, out=None):
+        """One call for many (item, offset, length) ranges, packed back to back.  -> (packed tensor, per-range views into it)."""
+        quads, out, n, views = self._packed_items(ranges, out)
+        self.read_items_into(quads, out)
+        return out[:n], views
+
+    def read_many_async(self, ranges, out=None):
+        """read_many on the current torch stream, nothing waited for: the status lands in codec.status()."""
+        quads, out, n, views = self._packed_items(ranges, out)
+        self.read_items_into(quads, out, sync=False)
+        return out[:n], views
+
+    def read_flat_many(self, ranges, out=None):
+        """RangeIndex.read_many on the concatenation of the healthy items' data: (offset, length) ranges."""
+        return RangeIndex.read_many(self, ranges, out)
 
 
 DONE_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_bool, C.c_void_p)
@@ -512,6 +649,12 @@ class DeviceCodec:
     def index(self, blob) -> RangeIndex:
         """An index of the .tsq container `blob` (uint8 CUDA tensor) for range reads: index(blob).read(offset, length)."""
         return RangeIndex(self, blob)
+
+    def index_batch(self, blobs) -> "BatchIndex":
+        """One index over many .tsq containers (1-D uint8 CUDA tensors), made in one call: index_batch(blobs).read(item, offset,
+        length).  Views of one storage are indexed in place; separate allocations are first packed with one torch.cat."""
+        arena, offs = self._arena(blobs)
+        return BatchIndex(self, arena, [(o, b.numel()) for o, b in zip(offs, blobs)])
 
     # ---- batches: many independent items in one call (tsqa_*_batch) ----
     def _arena(self, tensors):

@@ -92,6 +92,38 @@ __global__ __launch_bounds__(256) void batch_walk_kernel(const uint8_t* __restri
     atomicMax(status, kErrFormat);
 }
 
+constexpr uint64_t kItemRefused = ~0ull;  // verdicts[i] of an item whose container batch_index_walk_kernel refuses
+
+// One lane per item of a batch index (tsqa_index_create_batch): batch_walk_kernel's walk with a verdict per item instead of one
+// for the batch, and no capacity.  n_blocks is the count the item's header states (0: the host has refused the header already);
+// frame k of item i lands at frames[first_block_i + k], stream_at relative to the batch's input, out_at = the item's out_at (its
+// start in the concatenation of the items' data) + the block's start in the item.  verdicts[i] = the item's total, or kItemRefused
+// (its descriptors are then not to be used).
+__global__ __launch_bounds__(256) void batch_index_walk_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
+                                                               FrameInfo* __restrict__ frames, uint64_t* __restrict__ verdicts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const BatchItem it = items[i];
+    const uint8_t* const c = in + it.in_at;
+    const uint64_t n = it.in_len;
+    FrameInfo* const fr = frames + it.first_block;
+    uint32_t nb = 0;
+    uint64_t total = 0, at = kHeaderSize, oat = 0;
+    bool bad = it.n_blocks == 0u || read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks;
+    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
+        FrameInfo f;
+        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
+        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
+        fr[b] = f;
+        oat += f.out_len;
+        at += kFrameWordSize + f.stream_len;
+    }
+    if (!bad && oat != total) bad = true;
+    verdicts[i] = bad ? kItemRefused : total;
+    if (bad) for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
+}
+
 // The first 16 bytes of every item's container, zeros past a short one: the synchronous batch decompress reads every header with
 // one copy.  One thread per byte.
 __global__ __launch_bounds__(256) void batch_heads_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,

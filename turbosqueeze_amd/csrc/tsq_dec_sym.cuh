@@ -40,21 +40,154 @@ struct RangeItem {
     uint64_t out_at;
 };
 
-// The decoder of one block on one workgroup.  kWindow = false (dec_sym_kernel): block blockIdx.x, whole.  kWindow = true
-// (dec_range_kernel): item blockIdx.x -- only the bytes [lo, hi) of its block are written, and the chunk loop ends with the chunk
-// that reaches hi.  Every chunk that is decoded is validated as in the whole-block decode.  (The pointers carry no __restrict__ here:
-// the kernels' own parameters do, and restrict parameters of an inlined function would give dec_sym_kernel other code than before.)
-template <bool kWindow>
-__device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
-                                                 uint8_t* outbuf, int32_t* status)
+// One decode of a record read (tsqa_block_group): block `block` is decoded once, up to its byte `hi`, for the items
+// [first, first + count) of the item array, which are sorted by lo.
+struct BlockGroup {
+    uint32_t block, first, count, hi;
+};
+
+enum DecMode : int { kDecWhole, kDecWindow, kDecGroup };
+
+// ---------------- P7 of a record read: the image's bytes go to every item of the group that they meet (byte p of the block to
+// out[it.out_at + p - it.lo]).  The items are sorted by lo, so those that meet the image are a run of the list that only moves
+// forward: the cursor `gc.cur` (one per wavefront, it advances lazily) is the first item that an image at or behind this one can still meet, and
+// the run ends with the first item that starts behind the image.  The items stay in HBM / L2; every wavefront reads the run 64
+// items at a time, one per lane.
+//
+// The work is dealt by destination bytes, not by items: each item's stretch is cut into the 16-byte words of HBM that it touches,
+// the words of a batch are numbered across its items (a prefix sum over the lanes), and pass j of the numbering -- 64 words, one
+// per lane -- belongs to wavefront j mod n.  A 12 KiB stretch of one long window and two hundred records of 64 bytes both keep
+// every lane of every wavefront busy.  The destinations have unrelated alignments, so no skew of the ring serves them: a lane
+// reads the two ALIGNED 16-byte ring words that hold its sixteen source bytes (an unaligned ds access costs 3.5x an aligned one,
+// tools/micro/lds_unaligned.hip), shifts them into place in registers and stores one aligned 16-byte word; the words at a stretch's
+// edges (all of a short record) go as aligned dwords where a dword is whole and as single bytes where it is not.  Nothing outside
+// [a, b) of an item is written.  Threads first_tid .. first_tid + n_threads - 1 take part (whole wavefronts); no barrier inside.
+//
+// Most chunks of a record read meet no item, and a long window meets the same item for hundreds of chunks: the cursor keeps the
+// lo of its item (no image that ends at or before it has anything to write: no memory is touched) and the batch of 64 items it
+// last read around the cursor (read again only when the cursor has left it).
+struct GroupCursor {
+    uint32_t cur = 0, cur_lo = 0;           // the first item that is still needed, and its lo (0: not known yet)
+    uint32_t held = 0xFFFFFFFFu;            // `it` holds item held + lane (held: a multiple of 64)
+    RangeItem it = {0u, 0u, 0u, 0u, 0ull};
+};
+
+template <class L>
+__device__ __forceinline__ void flush_group(const uint8_t* lds, uint8_t* out, const Image& im, const RangeItem* items, uint32_t count, GroupCursor& gc,
+                                            uint32_t first_tid, uint32_t n_threads)
 {
+    using C = SymCfg;
+    const uint32_t tid = threadIdx.x;
+    if (im.len == 0 || tid < first_tid || gc.cur >= count || gc.cur_lo >= im.op + im.len) return;
+    uint32_t& cur = gc.cur;
+    const uint8_t* const ring = lds + L::ring;
+    const uint32_t lane = tid & 63u, w = (tid - first_tid) >> 6, nw = n_threads >> 6;
+    const uint32_t im_end = im.op + im.len;
+    uint32_t pass0 = 0;                     // passes of the batches before this one
+    bool leading = true;                    // no item that is still needed has been seen yet: the cursor moves
+    // The batches lie on a grid of 64 items from the group's first, whatever the cursor: every wavefront that takes part numbers
+    // the words alike even where its cursor lags behind the others' (the items in front of the true cursor give no word).
+    for (uint32_t base = cur & ~63u; base < count; base += 64u) {
+        const uint32_t k = base + lane;
+        RangeItem it = {0u, 0xFFFFFFFFu, 0u, 0u, 0ull};                           // behind the list: an item that starts behind every image
+        if (base == gc.held) it = gc.it;
+        else if (k < count) it = items[k];
+        const bool in_run = it.lo < im_end;
+        if (leading) {
+            gc.held = base; gc.it = it;                                           // (the batch at the cursor's place, or the one it moves into)
+            const uint64_t done = __ballot(k < count && it.hi <= im.op);         // behind this image and every later one
+            const uint32_t n = ~done == 0ull ? 64u : (uint32_t)__builtin_ctzll(~done);
+            cur = base + n;                                                       // (the lanes in front of the old cursor are done, too)
+            leading = n == 64u;
+            // the cursor's item is lane n of this batch (behind the list: no item, and cur >= count ends every later call at once)
+            if (!leading) gc.cur_lo = (uint32_t)__builtin_amdgcn_readlane((int)it.lo, (int)n);
+        }
+        const uint32_t a = it.lo > im.op ? it.lo : im.op, b = it.hi < im_end ? it.hi : im_end;
+        const bool live = in_run && a < b;
+        const uint32_t len = live ? b - a : 0u;
+        const uint64_t addr = (uint64_t)(uintptr_t)out + it.out_at + (a - it.lo);  // where byte a goes
+        const uint32_t nwords = live ? (((uint32_t)addr & 15u) + len + 15u) >> 4 : 0u;
+        uint32_t ra = im.at + (a - im.op); ra -= ra >= C::R ? C::R : 0u;          // ring address of byte a
+        uint32_t incl = nwords;                                                   // inclusive prefix over the lanes
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t passes = (total + 63u) >> 6;
+        const uint32_t packed = len | (ra << 14);                                 // len <= OUTC < 2^14, ra < R < 2^17
+        for (uint32_t j = (w + nw - pass0 % nw) % nw; j < passes; j += nw) {
+            const uint32_t q = (j << 6) + lane;
+            // the word's item: the first lane whose inclusive count exceeds q (= the number of lanes whose count does not)
+            uint32_t t = 0;
+#pragma unroll
+            for (uint32_t step = 32u; step != 0u; step >>= 1) {
+                const uint32_t v = __shfl(incl, (int)(t + step - 1u));
+                t += v <= q ? step : 0u;
+            }
+            const bool act = q < total;
+            const int src = (int)(t & 63u);
+            const uint32_t excl_s = __shfl(incl - nwords, src), alo = __shfl((uint32_t)addr, src), ahi = __shfl((uint32_t)(addr >> 32), src),
+                           pk = __shfl(packed, src);
+            if (act) {      // (the shuffles above are the whole wavefront's; what follows is each lane's own)
+                const uint32_t kk = q - excl_s, slen = pk & 0x3FFFu, sra = pk >> 14, s = alo & 15u;
+                uint8_t* const word = reinterpret_cast<uint8_t*>((uintptr_t)((((uint64_t)ahi << 32) | alo) & ~15ull)) + ((size_t)kk << 4);
+                // bytes [e0, e1) of the word belong to the stretch; the word's byte 0 is the stretch's byte i0
+                const int32_t i0 = (int32_t)(kk << 4) - (int32_t)s;
+                const uint32_t e0 = kk == 0u ? s : 0u;
+                const uint32_t left = (uint32_t)((int32_t)slen - i0), e1 = left < 16u ? left : 16u;
+                int32_t r = (int32_t)sra + i0;
+                r += r < 0 ? (int32_t)C::R : 0; r -= r >= (int32_t)C::R ? (int32_t)C::R : 0;
+                const uint32_t r0 = (uint32_t)r & ~15u;
+                uint32_t r1 = r0 + 16u; r1 -= r1 >= C::R ? C::R : 0u;                  // (the ring's size is a multiple of 16)
+                const uint4 x = *reinterpret_cast<const uint4*>(ring + r0), y = *reinterpret_cast<const uint4*>(ring + r1);
+                const uint32_t v8[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                const uint32_t dsh = ((uint32_t)r >> 2) & 3u, bsh = ((uint32_t)r & 3u) << 3;
+                uint32_t u[5], o[4];
+#pragma unroll
+                for (uint32_t i = 0; i < 5u; ++i) u[i] = dsh == 0u ? v8[i] : dsh == 1u ? v8[i + 1] : dsh == 2u ? v8[i + 2] : v8[i + 3];
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) o[i] = (uint32_t)((((uint64_t)u[i + 1] << 32) | u[i]) >> bsh);
+                if (e0 == 0u && e1 == 16u) {
+                    *reinterpret_cast<uint4*>(word) = make_uint4(o[0], o[1], o[2], o[3]);
+                } else {
+#pragma unroll
+                    for (uint32_t i = 0; i < 4u; ++i) {
+                        if (e0 <= 4u * i && 4u * i + 4u <= e1) {
+                            *reinterpret_cast<uint32_t*>(word + 4u * i) = o[i];
+                        } else {
+#pragma unroll
+                            for (uint32_t c = 0; c < 4u; ++c)
+                                if (4u * i + c >= e0 && 4u * i + c < e1) word[4u * i + c] = (uint8_t)(o[i] >> (8u * c));
+                        }
+                    }
+                }
+            }
+        }
+        pass0 += passes;
+        if (__ballot(!in_run) != 0ull) break;                                     // the run ends in this batch
+    }
+}
+
+// The decoder of one block on one workgroup.  kDecWhole (dec_sym_kernel): block blockIdx.x, whole.  kDecWindow
+// (dec_range_kernel): item blockIdx.x -- only the bytes [lo, hi) of its block are written, and the chunk loop ends with the chunk
+// that reaches hi.  kDecGroup (dec_group_kernel): group blockIdx.x -- its block is decoded up to the group's hi, and every chunk's
+// bytes go to each of the group's items that they meet (flush_group).  Every chunk that is decoded is validated as in the
+// whole-block decode.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
+// inlined function would give dec_sym_kernel other code than before.)
+template <DecMode kMode>
+__device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
+                                                 uint8_t* outbuf, int32_t* status, const BlockGroup* groups = nullptr, uint32_t n_items = 0u)
+{
+    constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup;
     using C = SymCfg;
     using L = SymLds;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t* const gout = reinterpret_cast<const uint32_t*>(lds + L::gout);
     const uint32_t* const pairs = reinterpret_cast<const uint32_t*>(lds + L::pairs);
     uint32_t* const misc = reinterpret_cast<uint32_t*>(lds + L::misc);
-    // misc[0..5]: tsq_dec_common.cuh; [9], [10] instrumented builds only
+    // misc[0..5]: tsq_dec_common.cuh; [9], [10] instrumented builds only; [12] group: the upper wavefronts' cursor, for the last write-out
 
     const uint32_t tid = threadIdx.x;
     // Another block may have reported an error: leave, but all together (thread 0 reads the word, the workgroup branches on its copy
@@ -73,20 +206,33 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         }
         blk = it.block; lo = it.lo; hi = it.hi; out_at = it.out_at;
     }
+    // group: the items it serves, and how far each wavefront has come in them (flush_group)
+    [[maybe_unused]] const RangeItem* gitems = nullptr;
+    [[maybe_unused]] uint32_t gcount = 0;
+    [[maybe_unused]] GroupCursor gcur;
+    if constexpr (kGroup) {
+        const BlockGroup g = groups[blockIdx.x];
+        if (g.block >= n_frames || g.count == 0u || g.first > n_items || g.count > n_items - g.first) {
+            if (tid == 0) atomicMax(status, kErrStream);
+            return;
+        }
+        blk = g.block; hi = g.hi; gitems = items + g.first; gcount = g.count;
+    }
     const FrameInfo f = frames[blk];
     // The descriptor may come straight from an untrusted container (tsqa_decode_blocks_async): a stream shorter than its 3-byte
     // header, longer than a block slot, or an output longer than a block is refused before anything is read through it.
-    if (f.stream_len < 3u || f.stream_len > kSlotSize || f.out_len > kBlockSize || (kWindow && (lo >= hi || hi > f.out_len))) {
+    if (f.stream_len < 3u || f.stream_len > kSlotSize || f.out_len > kBlockSize || ((kWindow || kGroup) && (lo >= hi || hi > f.out_len))) {
         if (tid == 0) atomicMax(status, kErrStream);
         return;
     }
     const uint8_t* const in = container + f.stream_at;
     // window: `out` is where byte lo goes; byte p of the block goes to out + (p - lo)
-    uint8_t* const out = outbuf + (kWindow ? out_at : f.out_at);
+    // (group: every item has a destination of its own in outbuf; no skew of the ring can serve them all)
+    uint8_t* const out = kGroup ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
     const uint32_t in_len = f.stream_len, size = f.out_len, ext = f.ext;
     // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM (window: of
     // the block's virtual base out - lo)
-    const uint32_t oskew = (uint32_t)(((uintptr_t)out - lo) & 15u);
+    const uint32_t oskew = kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
 
 #ifdef TSQ_STATS
     const uint32_t lane = tid & 63u, wid = tid >> 6;
@@ -125,7 +271,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         // HBM meanwhile (P7).  (measured in round 5: a build without this flush runs 4.558 against 4.553 ms, the flush beside P3's
         // chain instead 4.572 -- it hides completely)
         if (tid >= C::T / 2) {
-            if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
+            if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, C::T / 2, C::T / 2);
+            else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
             else flush_image<L>(lds, out, prev, C::T / 2, C::T / 2);
         }
         group_lanes<L>(lds, nsn, slim, op, size, ext);
@@ -140,8 +287,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
             return;
         }
         const Image im = {op, e.next_op - op, ring_op};
-        // (window: the chunk that reaches hi is the last one decoded)
-        const bool more = !e.last && !(kWindow && e.next_op >= hi);
+        // (window, group: the chunk that reaches hi is the last one decoded)
+        const bool more = !e.last && !((kWindow || kGroup) && e.next_op >= hi);
         // the next chunk's stream is on its way while this one is copied
         if (more) pre = prefetch_words(in, next_sp, in_len - next_sp);
         TSQD_ACC(4);
@@ -183,8 +330,13 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         TSQD_ACC(8);
         if (!more) break;
     }
+    // (group: the lower wavefronts have written nothing out so far; they take the cursor of the upper ones instead of walking the
+    // item list from its start)
+    if constexpr (kGroup) { if (tid == C::T / 2) misc[12] = gcur.cur; }
     __syncthreads();
-    if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
+    if constexpr (kGroup) { if (tid < C::T / 2) gcur.cur = misc[12]; }
+    if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, 0, C::T);
+    else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
     else flush_image<L>(lds, out, prev, 0, C::T);
 #ifdef TSQ_STATS
     if (blockIdx.x == 0 && tid == 0) for (int q = 0; q < 16; ++q) g_dec_stats[q] = st_[q];
@@ -195,14 +347,23 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
 __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
                                                        uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
 {
-    sym_decode_block<false>(container, frames, 0u, nullptr, outbuf, status);
+    sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, status);
 }
 
 // Range reads (tsqa_decompress_ranges_async): one workgroup per item; nothing outside [out_at, out_at + hi - lo) of `outbuf` is written.
 __global__ __launch_bounds__(1024) void dec_range_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames, uint32_t n_frames,
                                                          const RangeItem* __restrict__ items, uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
 {
-    sym_decode_block<true>(container, frames, n_frames, items, outbuf, status);
+    sym_decode_block<kDecWindow>(container, frames, n_frames, items, outbuf, status);
+}
+
+// Record reads (tsqa_decompress_item_ranges_async): one workgroup per touched block, which serves all of the block's items;
+// nothing outside the items' destinations is written.
+__global__ __launch_bounds__(1024) void dec_group_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames, uint32_t n_frames,
+                                                         const RangeItem* __restrict__ items, uint32_t n_items, const BlockGroup* __restrict__ groups,
+                                                         uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
+{
+    sym_decode_block<kDecGroup>(container, frames, n_frames, items, outbuf, status, groups, n_items);
 }
 
 }  // namespace tsq

@@ -94,7 +94,9 @@ struct tsqa_ctx {
     int launch_decode(const void* d_container, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant = -1);
 };
 
-// A container's frame table, kept for range reads (tsqa_index_create).  The container itself is the caller's.
+// A container's frame table, kept for range reads (tsqa_index_create), or the frame table of a batch of containers in one buffer
+// (tsqa_index_create_batch): the healthy items' blocks one after the other, stream_at relative to the buffer.  The containers
+// themselves are the caller's.
 struct tsqa_index {
     int device = 0;
     const uint8_t* container = nullptr;
@@ -104,4 +106,7 @@ struct tsqa_index {
     tsq::FrameInfo* frames = nullptr;          // n_blocks descriptors on the device (frame_walk_kernel)
     std::vector<tsqa_frame> host_frames;       // their host copy
     std::vector<uint64_t> out_start;           // n_blocks + 1: where each block's output starts, then the total
+    // items (one for a single container): item i owns the blocks [item_first[i], item_first[i + 1]), none when it was refused
+    std::vector<uint64_t> item_first;          // n_items + 1
+    std::vector<int32_t> item_status;          // TSQA_OK or TSQA_ERR_FORMAT
 };

@@ -181,4 +181,18 @@ inline int launch_range_kernel(tsqa_ctx* c, const uint8_t* container, const Fram
     return 0;
 }
 
+// Record reads: one workgroup per group (dec_group_kernel), at any group count.  Items and groups are in device memory.
+inline int launch_group_kernel(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
+                               uint32_t n_items, const BlockGroup* groups, uint32_t n_groups, uint8_t* out, int32_t* status, hipStream_t s)
+{
+    static std::atomic<uint64_t> attr_devices{0};
+    {
+        const void* const fns[1] = {reinterpret_cast<const void*>(dec_group_kernel)};
+        const uint32_t bytes[1] = {SymLds::total};
+        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
+    }
+    hipLaunchKernelGGL(dec_group_kernel, dim3(n_groups), dim3(SymCfg::T), SymLds::total, s, container, frames, n_frames, items, n_items, groups, out, status);
+    return 0;
+}
+
 }  // namespace tsq

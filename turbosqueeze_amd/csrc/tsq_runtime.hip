@@ -733,6 +733,8 @@ extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n,
     if (rc != TSQA_OK) { tsqa_index_destroy(idx); return rc; }
     for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = idx->host_frames[b].out_at;
     idx->out_start[nb] = total;
+    try { idx->item_first = {0ull, (uint64_t)nb}; idx->item_status = {TSQA_OK}; }
+    catch (...) { c->set_error("index_create: out of host memory"); tsqa_index_destroy(idx); return TSQA_ERR_ARG; }
     *out = idx;
     return TSQA_OK;
 }
@@ -747,6 +749,16 @@ extern "C" void tsqa_index_destroy(tsqa_index* idx)
 
 extern "C" uint32_t tsqa_index_blocks(const tsqa_index* idx) { return idx ? idx->n_blocks : 0u; }
 extern "C" uint64_t tsqa_index_total(const tsqa_index* idx) { return idx ? idx->total : 0ull; }
+extern "C" uint32_t tsqa_index_items(const tsqa_index* idx) { return idx ? (uint32_t)idx->item_status.size() : 0u; }
+extern "C" uint64_t tsqa_index_item_total(const tsqa_index* idx, uint32_t i)
+{
+    if (!idx || i >= idx->item_status.size()) return 0ull;
+    return idx->out_start[idx->item_first[i + 1]] - idx->out_start[idx->item_first[i]];
+}
+extern "C" int tsqa_index_item_status(const tsqa_index* idx, uint32_t i)
+{
+    return idx && i < idx->item_status.size() ? idx->item_status[i] : TSQA_ERR_ARG;
+}
 
 // tsqa_plan_ranges, with the reason for a refusal.  count_only: validate and count, write no item.
 static int plan_ranges(const uint64_t* out_start, uint32_t nb, const tsqa_range* r, uint32_t nr, size_t out_cap, tsqa_range_item* items,
@@ -847,6 +859,123 @@ extern "C" int tsqa_decompress_ranges(tsqa_ctx* c, const tsqa_index* idx, const 
     TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "decompress_ranges");
+}
+
+// ---- record reads: ranges addressed by item, one decode per touched block ----
+
+// tsqa_plan_item_ranges, with the reason for a refusal: the ranges become ranges of the concatenation (plan_ranges cuts them at the
+// block edges and checks the destinations), the items are sorted by (block, lo), and each block's items become one group.
+static int plan_item_ranges(const uint64_t* out_start, uint32_t nb, const uint64_t* item_first, uint32_t n_items, const tsqa_item_range* r,
+                            uint32_t nr, size_t out_cap, std::vector<tsqa_range_item>& items, std::vector<tsqa_block_group>& groups,
+                            const char** why)
+{
+    *why = "";
+    items.clear(); groups.clear();
+    if (!out_start || !item_first || n_items == 0 || (nr && !r)) { *why = "null pointer or no items"; return TSQA_ERR_ARG; }
+    if (item_first[0] != 0 || item_first[n_items] != nb) { *why = "item_first does not run from 0 to n_blocks"; return TSQA_ERR_ARG; }
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_first[i + 1] < item_first[i]) { *why = "item_first decreases"; return TSQA_ERR_ARG; }
+    uint32_t n = 0;
+    if (nb && plan_ranges(out_start, nb, nullptr, 0, out_cap, nullptr, 0, &n, why, true)) return TSQA_ERR_ARG;     // the block starts themselves
+    std::vector<tsqa_range> flat;
+    flat.reserve(nr);
+    for (uint32_t k = 0; k < nr; ++k) {
+        const tsqa_item_range& x = r[k];
+        if (x.item >= n_items) { *why = "an item number past the index"; return TSQA_ERR_ARG; }
+        const uint64_t fb = item_first[x.item], fe = item_first[x.item + 1];
+        if (fb == fe) { *why = "a range of a refused item"; return TSQA_ERR_ARG; }
+        const uint64_t total = out_start[fe] - out_start[fb];
+        if (x.length > total || x.offset > total - x.length) { *why = "a range ends past its item's total"; return TSQA_ERR_ARG; }
+        if (x.length) flat.push_back(tsqa_range{out_start[fb] + x.offset, x.length, x.out_at});
+    }
+    if (flat.empty()) return TSQA_OK;
+    if (plan_ranges(out_start, nb, flat.data(), (uint32_t)flat.size(), out_cap, nullptr, 0, &n, why, true)) return TSQA_ERR_ARG;
+    items.resize(n);
+    if (plan_ranges(out_start, nb, flat.data(), (uint32_t)flat.size(), out_cap, items.data(), n, &n, why)) return TSQA_ERR_ARG;
+    std::stable_sort(items.begin(), items.end(), [](const tsqa_range_item& p, const tsqa_range_item& q) {
+        return p.block != q.block ? p.block < q.block : p.lo < q.lo;
+    });
+    for (uint32_t k = 0; k < n; ++k) {
+        if (groups.empty() || groups.back().block != items[k].block) groups.push_back(tsqa_block_group{items[k].block, k, 0u, 0u});
+        tsqa_block_group& g = groups.back();
+        g.count++;
+        g.hi = std::max(g.hi, items[k].hi);
+    }
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_plan_item_ranges(const uint64_t* out_start, uint32_t n_blocks, const uint64_t* item_first_block, uint32_t n_items,
+                                     const tsqa_item_range* ranges, uint32_t n_ranges, size_t out_cap, tsqa_range_item* items,
+                                     uint32_t cap_items, uint32_t* n_range_items, tsqa_block_group* groups, uint32_t cap_groups,
+                                     uint32_t* n_groups)
+{
+    const char* why;
+    if (!n_range_items || !n_groups || (!items && cap_items) || (!groups && cap_groups)) return TSQA_ERR_ARG;
+    std::vector<tsqa_range_item> vi;
+    std::vector<tsqa_block_group> vg;
+    try {
+        if (plan_item_ranges(out_start, n_blocks, item_first_block, n_items, ranges, n_ranges, out_cap, vi, vg, &why)) return TSQA_ERR_ARG;
+    } catch (...) { return TSQA_ERR_ARG; }
+    *n_range_items = (uint32_t)vi.size();
+    *n_groups = (uint32_t)vg.size();
+    if (vi.size() > cap_items || vg.size() > cap_groups) return TSQA_ERR_ARG;
+    std::copy(vi.begin(), vi.end(), items);
+    std::copy(vg.begin(), vg.end(), groups);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_item_ranges_async(tsqa_ctx* c, const tsqa_index* idx, const tsqa_item_range* ranges, uint32_t n_ranges,
+                                                 void* d_out, size_t out_cap, int32_t* d_status, void* hip_stream)
+{
+    static_assert(sizeof(tsqa_block_group) == sizeof(BlockGroup) && sizeof(tsqa_item_range) == 32, "public group = kernel group");
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_out || !d_status || (n_ranges && !ranges)) { c->set_error("decompress_item_ranges: null pointer"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("decompress_item_ranges: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    const char* why = "out of host memory";
+    std::vector<tsqa_range_item> vi;
+    std::vector<tsqa_block_group> vg;
+    int prc = TSQA_ERR_ARG;
+    try {
+        prc = plan_item_ranges(idx->out_start.data(), idx->n_blocks, idx->item_first.data(), (uint32_t)idx->item_status.size(), ranges, n_ranges,
+                               out_cap, vi, vg, &why);
+    } catch (...) {}
+    if (prc) { c->set_error("decompress_item_ranges: %s", why); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    (void)hipSetDevice(c->device);
+    const uint32_t n_items = (uint32_t)vi.size(), n_groups = (uint32_t)vg.size();
+    // one upload: the items, then (on a 16-byte boundary) the groups
+    const size_t groups_at = ((size_t)n_items * sizeof(tsqa_range_item) + 15u) & ~(size_t)15u, bytes = groups_at + (size_t)n_groups * sizeof(tsqa_block_group);
+    int k = 0;
+    if (int rc = c->reserve_upload(c->range_up, bytes ? bytes : 16, &k)) return rc;
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    if (n_groups == 0) return TSQA_OK;
+    uint8_t* const host = static_cast<uint8_t*>(c->range_up.host[k]);
+    memset(host, 0, bytes);
+    memcpy(host, vi.data(), (size_t)n_items * sizeof(tsqa_range_item));
+    memcpy(host + groups_at, vg.data(), (size_t)n_groups * sizeof(tsqa_block_group));
+    TSQ_HIP(c, hipMemcpyAsync(c->range_up.dev[k], host, bytes, hipMemcpyHostToDevice, s));
+    const uint8_t* const dev = static_cast<const uint8_t*>(c->range_up.dev[k]);
+    const int rc = launch_group_kernel(c, idx->container, idx->frames, idx->n_blocks, reinterpret_cast<const RangeItem*>(dev), n_items,
+                                       reinterpret_cast<const BlockGroup*>(dev + groups_at), n_groups, static_cast<uint8_t*>(d_out), d_status, s);
+    // (behind the kernel: neither copy of the descriptors is touched again before the read that uses them has finished)
+    TSQ_HIP(c, hipEventRecord(c->range_up.done[k], s));
+    c->range_up.pending[k] = true;
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_item_ranges(tsqa_ctx* c, const tsqa_index* idx, const tsqa_item_range* ranges, uint32_t n_ranges, void* d_out,
+                                           size_t out_cap, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    int rc = tsqa_decompress_item_ranges_async(c, idx, ranges, n_ranges, d_out, out_cap, c->d_status, s);
+    if (rc) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "decompress_item_ranges");
 }
 
 // ---- batches: many independent items at offsets in one input and one output buffer ----
@@ -1086,6 +1215,127 @@ extern "C" int tsqa_decompress_batch(tsqa_ctx* c, const void* d_in, size_t in_si
     for (uint32_t i = 0; i < n_items; ++i) { worst = std::max(worst, item_status[i]); refused += item_status[i] != TSQA_OK; }
     if (worst) c->set_error("decompress_batch: %u of %u items refused (worst status %d)", refused, n_items, worst);
     return worst;
+}
+
+// ---- an index over a batch of containers (record reads: tsqa_decompress_item_ranges*) ----
+
+// tsqa_index_create_batch behind its argument checks.  The index under construction is the caller's (*made) from the moment it
+// exists: whatever ends this function early, an exception of a host allocation included, the caller destroys it.
+static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                              tsqa_index** out, int32_t* item_status, tsqa_index** made)
+{
+    // the batch planner's checks of the input ranges (the output ranges of the items are not used)
+    std::vector<tsqa_batch_item> plain;
+    if (items && n_items) {
+        plain.assign(items, items + n_items);
+        for (tsqa_batch_item& x : plain) { x.out_at = 0; x.out_cap = 0; }
+    }
+    const char* why;
+    if (plan_batch(plain.empty() ? nullptr : plain.data(), n_items, in_size, 0, nullptr, nullptr, &why, kPlanRangesOnly)) {
+        c->set_error("index_create_batch: %s", why);
+        return TSQA_ERR_ARG;
+    }
+    hipStream_t s = c->stream;
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    // every header with one gather kernel and one copy (as tsqa_decompress_batch reads them)
+    int k = 0;
+    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
+    BatchItem* hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, 0, 0, 0, 0, 0};
+    std::vector<uint8_t> heads((size_t)n_items * kHeaderSize);
+    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(batch_heads_kernel, dim3((uint32_t)(((uint64_t)n_items * kHeaderSize + 255u) / 256u)), dim3(256), 0, s, in,
+                       static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->batch_heads);
+    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
+    c->batch_up.pending[k] = true;
+    TSQ_HIP(c, hipMemcpyAsync(heads.data(), c->batch_heads, heads.size(), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    // the block counts the headers state (0: refused here), each item's first block, and its start in the concatenation of the data
+    std::vector<uint32_t> nbs(n_items);
+    std::vector<uint64_t> first((size_t)n_items + 1), verdicts(n_items);
+    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
+    hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    uint64_t blocks = 0, cat = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        uint32_t nb = 0; uint64_t total = 0;
+        if (read_header(&heads[(size_t)i * kHeaderSize], items[i].in_len, &nb, &total) != kHeaderOk) { nb = 0; total = 0; }
+        nbs[i] = nb; first[i] = blocks;
+        hi[i] = BatchItem{items[i].in_at, items[i].in_len, cat, 0, blocks, nb, 0u};
+        blocks += nb; cat += total;
+    }
+    first[n_items] = blocks;
+    if (blocks > 0xFFFFFFFFull) { c->set_error("index_create_batch: more than 2^32 - 1 blocks"); return TSQA_ERR_ARG; }
+    tsqa_index* idx = new (std::nothrow) tsqa_index();
+    if (!idx) { c->set_error("index_create_batch: out of host memory"); return TSQA_ERR_ARG; }
+    *made = idx;
+    idx->device = c->device; idx->container = in; idx->n = in_size;
+    std::vector<tsqa_frame> walked(blocks);
+    // one frame walk over all items, one lane each, into the index's own descriptors; verdicts and descriptors come back together
+    auto walk = [&]() -> int {
+        TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)(blocks ? blocks : 1) * sizeof(FrameInfo)));
+        TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(batch_index_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, in, static_cast<const BatchItem*>(c->batch_up.dev[k]),
+                           n_items, idx->frames, c->batch_sizes);
+        TSQ_HIP(c, hipGetLastError());
+        TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
+        c->batch_up.pending[k] = true;
+        TSQ_HIP(c, hipMemcpyAsync(verdicts.data(), c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (blocks) TSQ_HIP(c, hipMemcpyAsync(walked.data(), idx->frames, (size_t)blocks * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipStreamSynchronize(s));
+        return TSQA_OK;
+    };
+    if (int rc = walk()) return rc;
+    // the healthy items' blocks, one after the other.  (An item whose header passed and whose frames did not leaves a gap in the
+    // table the walk wrote: the table is closed up here and goes to the device once more.  Rare, and still a constant number of copies.)
+    idx->item_first.resize((size_t)n_items + 1);
+    idx->item_status.resize(n_items);
+    bool gaps = false;
+    uint64_t total = 0;
+    int32_t worst = TSQA_OK;
+    uint32_t refused = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const bool ok = verdicts[i] != kItemRefused;
+        idx->item_first[i] = idx->host_frames.size();
+        idx->item_status[i] = ok ? TSQA_OK : TSQA_ERR_FORMAT;
+        if (item_status) item_status[i] = idx->item_status[i];
+        if (!ok) { gaps |= nbs[i] != 0u; refused++; worst = TSQA_ERR_FORMAT; continue; }
+        for (uint64_t b = first[i]; b < first[i + 1]; ++b) {
+            tsqa_frame f = walked[b];
+            f.out_at = total;
+            idx->out_start.push_back(total);
+            idx->host_frames.push_back(f);
+            total += f.out_len;
+        }
+    }
+    idx->item_first[n_items] = idx->host_frames.size();
+    idx->out_start.push_back(total);
+    idx->n_blocks = (uint32_t)idx->host_frames.size();
+    idx->total = total;
+    if (gaps && idx->n_blocks) {
+        const hipError_t e = hipMemcpy(idx->frames, idx->host_frames.data(), (size_t)idx->n_blocks * sizeof(FrameInfo), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { c->set_error("index_create_batch: hipMemcpy failed: %s", hipGetErrorString(e)); return TSQA_ERR_HIP; }
+    }
+    if (worst) c->set_error("index_create_batch: %u of %u items refused", refused, n_items);
+    *out = idx;
+    return worst;
+}
+
+extern "C" int tsqa_index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                       tsqa_index** out, int32_t* item_status)
+{
+    if (!out) return TSQA_ERR_ARG;
+    *out = nullptr;
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_in) { c->set_error("index_create_batch: null pointer"); return TSQA_ERR_ARG; }
+    tsqa_index* made = nullptr;
+    int rc;
+    // (the block counts come from the containers' own headers: the host tables may be refused by the allocator)
+    try { rc = index_create_batch(c, d_in, in_size, items, n_items, out, item_status, &made); }
+    catch (...) { c->set_error("index_create_batch: out of host memory"); rc = TSQA_ERR_ARG; *out = nullptr; }
+    if (!*out) tsqa_index_destroy(made);
+    return rc;
 }
 
 // ---- the second roofline denominator: what a plain device copy reaches on this GPU ----
