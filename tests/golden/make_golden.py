@@ -10,6 +10,9 @@ canonical conditions of SURVEY.md 8c.  Nothing here travels as reference source.
                           vectors (K3, K6) that are too big to commit
   ref_streams.npz         length + digest (fuzzgen.stream_digest) of the reference's stream for every
                           case of tests/test_oracle_vs_ref.py, and a digest of each case's input
+  conformance_streams.json   digests (fuzzgen.stream_digest) of every case of the decoder conformance catalogue
+                          (tests/streamgen.py) and, per valid case, that the reference's decoder gave the builder's bytes
+                          (`make_golden.py conformance` writes this file alone)
 """
 import ast
 import json
@@ -80,7 +83,8 @@ def main() -> None:
         manifest[name] = entry
     json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1, sort_keys=True)
     write_ref_streams(ref)
-    print("wrote", len(small), "fixtures +", "manifest.json + ref_streams.npz")
+    write_conformance_streams(ref)
+    print("wrote", len(small), "fixtures +", "manifest.json + ref_streams.npz + conformance_streams.json")
 
 
 def write_ref_streams(ref) -> None:
@@ -107,5 +111,27 @@ def write_ref_streams(ref) -> None:
     np.savez_compressed(os.path.join(HERE, "ref_streams.npz"), **arrays)
 
 
+def write_conformance_streams(ref) -> None:
+    """name -> {ext, stream, plain, reference_agrees}: digests and names only.  A valid case is written only when the reference's
+    decoder returns the builder's plain bytes for it (the reference decides what a valid stream is); an invalid twin has no plain
+    and no verdict (the reference's decoder validates nothing and is not run on it)."""
+    import streamgen
+    hexd = lambda b: "%016x" % fuzzgen.stream_digest(b)
+    out = {}
+    for name, (ext, stream, plain) in streamgen.CATALOGUE.valid.items():
+        agrees = ref.decode_block(stream, ext) == plain
+        assert agrees, f"{name}: the reference decoder does not give the builder's bytes"
+        out[name] = {"ext": ext, "stream": hexd(stream), "plain": hexd(plain), "reference_agrees": agrees}
+    for name, (ext, stream) in streamgen.CATALOGUE.invalid.items():
+        out[name] = {"ext": ext, "stream": hexd(stream), "plain": None, "reference_agrees": None}
+    with open(os.path.join(HERE, "conformance_streams.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["conformance"]:
+        build()
+        write_conformance_streams(Reference())
+    else:
+        main()

@@ -8,9 +8,12 @@ import numpy as np
 import pytest
 
 import fuzzgen
+import streamgen
 import kat
 
 pytestmark = pytest.mark.gpu
+
+ERR_STREAM = 5                                        # TSQA_ERR_STREAM, as in test_gpu_range.py
 
 GOLDEN = kat.GOLDEN
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
@@ -294,14 +297,18 @@ def test_container_errors(codec, tsq, oracle):
     for blob in (bad_magic, zero_blocks, truncated, big_frame):
         with pytest.raises(tsq.TsqError):
             codec.decompress(to_dev(np.frombuffer(blob, dtype=np.uint8)), out_cap=400000)
-    # corrupt an offset inside the stream: must be flagged, not crash
+    # corrupt an offset inside the stream: the device agrees with the model and the oracle on this exact blob
     arr = np.frombuffer(good, dtype=np.uint8).copy()
     arr[40:60] = 0xFF
-    try:
-        out = codec.decompress(to_dev(arr), out_cap=400000)
-        assert out.numel() == 300000          # decoded to *something* of the right size, or raised
-    except tsq.TsqError:
-        pass
+    ln = int.from_bytes(bytes(arr[16:19]), "little") & 0x7FFFFF
+    want = streamgen.model_decode(bytes(arr[19:19 + ln]), 0)
+    assert oracle.decompress(arr) == want and len(arr) == 19 + ln          # (one block: None where both reject it)
+    if want is None:
+        with pytest.raises(tsq.TsqError) as e:
+            codec.decompress(to_dev(arr), out_cap=400000)
+        assert e.value.code == ERR_STREAM
+    else:
+        assert to_bytes(codec.decompress(to_dev(arr), out_cap=400000)) == want
     assert to_bytes(codec.decompress(to_dev(np.frombuffer(good, dtype=np.uint8)))) == bytes(tsq.synth.text(300000, 2))
 
 
