@@ -20,6 +20,17 @@ HALO = 128
 
 _u8p = C.POINTER(C.c_uint8)
 
+# tsq_oracle.h: tsqo_trace_rec, TSQO_OUT_*, TSQO_TF_*, TSQO_FL_*, TSQO_MUT_*
+TRACE_DTYPE = np.dtype([(f, "<u4") for f in ("i", "pos", "origin_at_offset", "origin_at_test", "offset", "k_raw", "k", "outcome",
+                                             "flags", "flush")])
+OUT_LITERAL, OUT_MATCH, OUT_BREAK_WORD, OUT_BREAK_OFFSET, OUT_BREAK_SHORT, OUT_BREAK_TAIL, OUT_END, OUT_BREAK_OFFSET_LATE = range(8)
+TF_WORD_EQUAL, TF_CHAIN_PROBE = 1, 2
+FL_FORCED, FL_BEFORE_MATCH = 1, 2
+NO_K = 0xFFFFFFFF
+MUTANTS = ("none", "offset_bound_plus", "offset_bound_minus", "lo_gt", "room_whole", "room_dropped", "chain_n4", "chain_n6",
+           "flush_at_32", "offset_after_flush", "nib17_plus", "nib32_plus", "nib32_minus", "nib48_plus", "nib48_minus", "nib64_plus",
+           "nib64_minus", "cap48", "no_chain_insert", "insert_pos0", "second_recent", "skip_prev_tile", "trim_spill")
+
 
 def build(force: bool = False) -> None:
     """Compile the checker (gcc) and, if /root/reference is here, oracle/_ref."""
@@ -59,6 +70,9 @@ class Oracle:
         L.tsqo_decompress.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.c_int]
         L.tsqo_fnv1a64.restype = C.c_uint64
         L.tsqo_fnv1a64.argtypes = [_u8p, C.c_size_t]
+        L.tsqo_encode_block_traced.restype = C.c_uint32
+        L.tsqo_encode_block_traced.argtypes = [_u8p, C.c_uint32, _u8p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                               C.POINTER(C.c_uint64)]
         self.L = L
         self._table = np.zeros(HASH_ENTRIES, dtype=np.uint16)
 
@@ -80,6 +94,20 @@ class Oracle:
         out = np.empty(self.L.tsqo_bound(n) + 32, dtype=np.uint8)
         sz = self.L.tsqo_encode_block(_ptr(buf), n, _ptr(out), int(ext), self._table.ctypes.data)
         return out[:sz].tobytes()
+
+    def encode_block_traced(self, data, ext: int, halo=None, mutant: int = 0, trace: bool = True):
+        """The instrumented form of encode_block (tsqo_encode_block_traced): -> (stream, trace records or None).
+        `mutant` selects one deliberate single-rule error (MUTANTS); a mutant's stream need not be valid."""
+        n = len(data)
+        assert n <= BLOCK_SZ and 0 <= mutant < len(MUTANTS)
+        buf = self._with_halo(data, halo)
+        out = np.zeros(self.L.tsqo_bound(n) + 256, dtype=np.uint8)
+        rec = np.zeros(n + 2 if trace else 0, dtype=TRACE_DTYPE)
+        count = C.c_uint64(0)
+        sz = self.L.tsqo_encode_block_traced(_ptr(buf), n, _ptr(out), int(ext), self._table.ctypes.data, int(mutant),
+                                             rec.ctypes.data if trace else None, rec.size, C.byref(count))
+        assert not trace or count.value <= rec.size
+        return out[:sz].tobytes(), (rec[: count.value] if trace else None)
 
     def decode_block(self, stream, ext: int):
         s = np.frombuffer(bytes(stream), dtype=np.uint8)

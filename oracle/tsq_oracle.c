@@ -32,6 +32,15 @@ uint32_t tsqo_bound(uint32_t n)
  * Encoder
  * ---------------------------------------------------------------------- */
 
+/*
+ * One body, three instances.  encode_body() is always inlined into its callers with `traced` and
+ * `mut` as compile-time constants where the caller passes constants: tsqo_encode_block passes
+ * (0, TSQO_MUT_NONE) and the compiler drops every trace and mutant branch from its loops;
+ * tsqo_encode_block_traced passes its run-time arguments.  There is no second copy to drift.
+ */
+#define TSQO_INLINE static inline __attribute__((always_inline))
+#define MUT(m) (mut == (uint32_t)(m))
+
 /* Output cursor and symbol bookkeeping (tsq_encode.cpp:57-61). */
 typedef struct {
     uint8_t *out;
@@ -44,9 +53,13 @@ typedef struct {
                           are still "zero-filled" (canonical condition) without a memset */
 } emitter;
 
+/* What the mutants that model a stale candidate need beside the 16-bit table: per bucket the last
+ * two insertions and the last insertion of an earlier 64-position tile, as position + 1 (0 = none). */
+typedef struct { uint32_t *last, *prev, *older; } mut_tables;
+
 /* Allocate the next output byte as a control/size byte.  If nothing has been stored there yet
  * it holds the zero of the zero-filled buffer; otherwise it keeps the literal spill. */
-static inline uint32_t alloc_byte(emitter *e)
+TSQO_INLINE uint32_t alloc_byte(emitter *e)
 {
     uint32_t at = e->j++;
     if (at >= e->hw) { e->out[at] = 0; e->hw = at + 1; }
@@ -60,8 +73,8 @@ static inline uint32_t alloc_byte(emitter *e)
  * 113-115, 157-159).  `origin_if_pair_closes` becomes the pair origin when
  * this symbol completes a pair.
  */
-static inline void account_symbol(emitter *e, uint32_t is_literal, uint32_t nibble,
-                                  uint32_t origin_if_pair_closes)
+TSQO_INLINE void account_symbol(emitter *e, uint32_t is_literal, uint32_t nibble,
+                                uint32_t origin_if_pair_closes)
 {
     e->nsym++;
     e->out[e->ctl_at] = (uint8_t)((e->out[e->ctl_at] << 1) | is_literal);
@@ -76,12 +89,14 @@ static inline void account_symbol(emitter *e, uint32_t is_literal, uint32_t nibb
  * via tsq_common.h:44-50); the spill is what later shows up in never-written
  * control/size bytes.
  */
-static inline uint32_t emit_literals(emitter *e, const uint8_t *in, uint32_t from, uint32_t to)
+TSQO_INLINE uint32_t emit_literals(emitter *e, const uint8_t *in, uint32_t from, uint32_t to,
+                                   const uint32_t mut)
 {
     while (to - from > 0) {
         uint32_t len = to - from > 16 ? 16 : to - from;
-        memcpy(e->out + e->j, in + from, 16);
-        if (e->j + 16 > e->hw) e->hw = e->j + 16;
+        uint32_t store = MUT(TSQO_MUT_TRIM_SPILL) ? len : 16u;
+        memcpy(e->out + e->j, in + from, store);
+        if (e->j + store > e->hw) e->hw = e->j + store;
         from += len;
         e->j += len;
         account_symbol(e, 1u, len - 1u, from);
@@ -95,25 +110,41 @@ static inline uint32_t emit_literals(emitter *e, const uint8_t *in, uint32_t fro
  * most recent position per 17-bit hash; the candidate is the unique position
  * congruent to that value in [i-65536, i-1].
  */
-static inline uint32_t probe_and_insert(uint16_t *table, const uint8_t *in, uint32_t i,
-                                        uint32_t *word)
+TSQO_INLINE uint32_t probe_and_insert(uint16_t *table, const uint8_t *in, uint32_t i,
+                                      uint32_t *word, const uint32_t mut, const int insert,
+                                      mut_tables *mt)
 {
     uint32_t w = ld32(in + i);
     uint32_t h = (w ^ (w >> 12)) & (TSQO_HASH_ENTRIES - 1u);
     uint32_t lo = table[h];
-    uint32_t pos = (i & 0xFFFF0000u) + lo;
-    if (lo >= (i & 0xFFFFu)) pos -= 65536u;
-    table[h] = (uint16_t)i;
+    uint32_t pos;
+    if (MUT(TSQO_MUT_SECOND_RECENT) && mt->last[h] && i - (mt->last[h] - 1u) <= 256u)
+        lo = mt->prev[h] ? (uint16_t)(mt->prev[h] - 1u) : 0u;
+    if (MUT(TSQO_MUT_SKIP_PREV_TILE) && mt->last[h] && ((mt->last[h] - 1u) >> 6) + 1u == (i >> 6))
+        lo = mt->older[h] ? (uint16_t)(mt->older[h] - 1u) : 0u;
+    pos = (i & 0xFFFF0000u) + lo;
+    if (MUT(TSQO_MUT_LO_GT) ? lo > (i & 0xFFFFu) : lo >= (i & 0xFFFFu)) pos -= 65536u;
+    if (insert) {
+        table[h] = (uint16_t)i;
+        if (MUT(TSQO_MUT_SECOND_RECENT) || MUT(TSQO_MUT_SKIP_PREV_TILE)) {
+            if (mt->last[h] && ((mt->last[h] - 1u) >> 6) != (i >> 6)) mt->older[h] = mt->last[h];
+            mt->prev[h] = mt->last[h];
+            mt->last[h] = i + 1u;
+        }
+    }
     *word = w;
     return pos;
 }
 
 /* offset in [4, 0xFFFE] (tsq_encode.cpp:100,145: (offset-4) < 0xFFFB unsigned). */
-static inline int offset_ok(uint32_t offset) { return (offset - 4u) < 0xFFFBu; }
+TSQO_INLINE int offset_ok(uint32_t offset, const uint32_t mut)
+{
+    return (offset - 4u) < (MUT(TSQO_MUT_OFFSET_BOUND_PLUS) ? 0xFFFCu : MUT(TSQO_MUT_OFFSET_BOUND_MINUS) ? 0xFFFAu : 0xFFFBu);
+}
 
 /* Common prefix of in+a and in+b in bytes, capped at `cap` (16 no-ext:
  * tsq_encode.cpp:126-137; 64 ext: tsq_encode.cpp:276-290). */
-static inline uint32_t common_prefix(const uint8_t *in, uint32_t a, uint32_t b, uint32_t cap)
+TSQO_INLINE uint32_t common_prefix(const uint8_t *in, uint32_t a, uint32_t b, uint32_t cap)
 {
     uint32_t k = ctz64_or_64(ld64(in + a) ^ ld64(in + b)) >> 3;
     if (k == 8) {
@@ -128,24 +159,43 @@ static inline uint32_t common_prefix(const uint8_t *in, uint32_t a, uint32_t b, 
 }
 
 /* Match length -> size nibble (tsq_encode.cpp:44-45). */
-static inline uint32_t length_nibble(uint32_t k)
+TSQO_INLINE uint32_t length_nibble(uint32_t k, const uint32_t mut)
 {
-    if (k >= 64) return 2;
-    if (k >= 48) return 1;
-    if (k >= 32) return 0;
-    if (k >= 17) return 15;
-    return k - 1;      /* 4..16 -> 3..15 */
+    if (k >= (MUT(TSQO_MUT_NIB64_PLUS) ? 65u : MUT(TSQO_MUT_NIB64_MINUS) ? 63u : 64u)) return 2;
+    if (k >= (MUT(TSQO_MUT_NIB48_PLUS) ? 49u : MUT(TSQO_MUT_NIB48_MINUS) ? 47u : 48u)) return 1;
+    if (k >= (MUT(TSQO_MUT_NIB32_PLUS) ? 33u : MUT(TSQO_MUT_NIB32_MINUS) ? 31u : 32u)) return 0;
+    /* (17 one less is no mutant: 16 -> k - 1 = 15, the same nibble) */
+    if (k >= (MUT(TSQO_MUT_NIB17_PLUS) ? 18u : 17u)) return 15;
+    return MUT(TSQO_MUT_NIB17_PLUS) ? (k - 1u) & 15u : k - 1;      /* 4..16 -> 3..15 */
 }
 
 /* Bytes consumed by a match with that nibble (tsq_encode.cpp:154,307). */
-static inline uint32_t nibble_span(uint32_t m) { return m < 3 ? (m + 2u) << 4 : m + 1u; }
+TSQO_INLINE uint32_t nibble_span(uint32_t m) { return m < 3 ? (m + 2u) << 4 : m + 1u; }
 
-uint32_t tsqo_encode_block(const uint8_t *in, uint32_t n, uint8_t *out,
-                           uint32_t ext, uint16_t *table)
+/* trace writer: records beyond the caller's capacity are counted, not written */
+typedef struct { tsqo_trace_rec *rec; uint64_t cap, count; tsqo_trace_rec scratch; } tracer;
+
+TSQO_INLINE tsqo_trace_rec *trace_probe(tracer *t, uint32_t i, uint32_t pos, uint32_t origin, uint32_t offset,
+                                        uint32_t word_eq, uint32_t in_chain)
 {
-    const uint32_t cap = ext ? 64u : 16u;
+    tsqo_trace_rec *r = t->count < t->cap ? &t->rec[t->count] : &t->scratch;
+    t->count++;
+    r->i = i; r->pos = pos; r->origin_at_offset = origin; r->origin_at_test = origin; r->offset = offset;
+    r->k_raw = 0xFFFFFFFFu; r->k = 0xFFFFFFFFu; r->outcome = TSQO_OUT_LITERAL;
+    r->flags = (word_eq ? TSQO_TF_WORD_EQUAL : 0u) | (in_chain ? TSQO_TF_CHAIN_PROBE : 0u);
+    r->flush = 0;
+    return r;
+}
+
+TSQO_INLINE uint32_t encode_body(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t ext, uint16_t *table,
+                                 const int traced, const uint32_t mut, tracer *tr, mut_tables *mt)
+{
+    const uint32_t cap = ext ? (MUT(TSQO_MUT_CAP48) ? 48u : 64u) : 16u;
+    const uint32_t flush_at = MUT(TSQO_MUT_FLUSH_AT_32) ? 32u : 31u;
+    const uint32_t chain_tail = MUT(TSQO_MUT_CHAIN_N4) ? 4u : MUT(TSQO_MUT_CHAIN_N6) ? 6u : 5u;
     emitter e;
     uint32_t i = 0, pending, pos, word, offset;
+    tsqo_trace_rec *r = NULL;
 
     memset(table, 0, TSQO_HASH_ENTRIES * sizeof(uint16_t));  /* tsq_context.cpp:77-80 */
     /* canonical zero-filled output, realised lazily through emitter.hw */
@@ -153,42 +203,57 @@ uint32_t tsqo_encode_block(const uint8_t *in, uint32_t n, uint8_t *out,
     out[3] = 0; out[4] = 0;
     e.out = out; e.ctl_at = 3; e.sz_at = 4; e.j = 5; e.nsym = 0; e.origin = 0; e.hw = 5;
 
+    if (MUT(TSQO_MUT_INSERT_POS0)) { uint32_t w0; (void)probe_and_insert(table, in, 0, &w0, mut, 1, mt); }
+
     do {
         pending = i;   /* first not-yet-emitted input byte (last_i) */
 
         /* scan for the next match start; position 0 is never probed (tsq_encode.cpp:70-100) */
         do {
             i++;
-            pos = probe_and_insert(table, in, i, &word);
+            pos = probe_and_insert(table, in, i, &word, mut, 1, mt);
             offset = e.origin - pos;   /* taken before any forced flush below */
-            if (i - pending > 31)
-                pending = emit_literals(&e, in, pending, i);
-        } while (i < n && !(word == ld32(in + pos) && offset_ok(offset)));
+            if (traced) r = trace_probe(tr, i, pos, e.origin, offset, word == ld32(in + pos), 0);
+            if (i - pending > flush_at) {
+                pending = emit_literals(&e, in, pending, i, mut);
+                if (traced) { r->flush |= TSQO_FL_FORCED; r->origin_at_test = e.origin; }
+                if (MUT(TSQO_MUT_OFFSET_AFTER_FLUSH)) offset = e.origin - pos;
+            }
+        } while (i < n && !(word == ld32(in + pos) && offset_ok(offset, mut)));
 
-        pending = emit_literals(&e, in, pending, i);   /* tsq_encode.cpp:103-118 */
-        if (!(i < n)) break;
+        if (traced && i > pending) r->flush |= TSQO_FL_BEFORE_MATCH | ((i - pending) << 8);
+        pending = emit_literals(&e, in, pending, i, mut);   /* tsq_encode.cpp:103-118 */
+        if (!(i < n)) { if (traced) r->outcome = TSQO_OUT_END; break; }
 
         /* chain of back-to-back matches (tsq_encode.cpp:123-170) */
         do {
             uint32_t k = common_prefix(in, i, pos, cap);
             uint32_t room = e.origin - pos;
             uint32_t m;
+            if (traced) { r->k_raw = k; r->origin_at_test = e.origin; }
             /* the source must end before the pair origin the decoder copies relative to */
-            if (k > room) k = room - 1u;
-            if (k < 4) break;
+            if (k > room && !MUT(TSQO_MUT_ROOM_DROPPED)) k = MUT(TSQO_MUT_ROOM_WHOLE) ? room : room - 1u;
+            if (traced) r->k = k;
+            if (k < 4) { if (traced) r->outcome = TSQO_OUT_BREAK_SHORT; break; }
             offset = e.origin - pos;
-            if (!offset_ok(offset)) break;
+            if (!offset_ok(offset, mut)) { if (traced) r->outcome = TSQO_OUT_BREAK_OFFSET_LATE; break; }
 
-            m = length_nibble(k);
+            m = length_nibble(k, mut);
+            if (traced) { r->outcome = TSQO_OUT_MATCH; r->flags |= m << 8; }
             out[e.j++] = (uint8_t)offset;
             out[e.j++] = (uint8_t)(offset >> 8);
             if (e.j > e.hw) e.hw = e.j;
             i += nibble_span(m);
             account_symbol(&e, 0u, m, i);
 
-            pos = probe_and_insert(table, in, i, &word);
+            pos = probe_and_insert(table, in, i, &word, mut, !MUT(TSQO_MUT_NO_CHAIN_INSERT), mt);
             offset = e.origin - pos;
-        } while (i < n - 5u && word == ld32(in + pos) && offset_ok(offset));
+            if (traced) {
+                r = trace_probe(tr, i, pos, e.origin, offset, word == ld32(in + pos), 1);
+                r->outcome = !(i < n - chain_tail) ? TSQO_OUT_BREAK_TAIL : word != ld32(in + pos) ? TSQO_OUT_BREAK_WORD
+                           : !offset_ok(offset, mut) ? TSQO_OUT_BREAK_OFFSET : TSQO_OUT_LITERAL /* overwritten by the next round */;
+            }
+        } while (i < n - chain_tail && word == ld32(in + pos) && offset_ok(offset, mut));
     } while (i < n);
 
     /* pad the last group: literal control bits; an odd final nibble moves to the
@@ -202,6 +267,30 @@ uint32_t tsqo_encode_block(const uint8_t *in, uint32_t n, uint8_t *out,
         }
     }
     return e.j;
+}
+
+uint32_t tsqo_encode_block(const uint8_t *in, uint32_t n, uint8_t *out,
+                           uint32_t ext, uint16_t *table)
+{
+    return encode_body(in, n, out, ext, table, 0, TSQO_MUT_NONE, NULL, NULL);
+}
+
+uint32_t tsqo_encode_block_traced(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t ext, uint16_t *table,
+                                  uint32_t mutant, tsqo_trace_rec *trace, uint64_t trace_cap, uint64_t *trace_count)
+{
+    tracer tr = { trace, trace ? trace_cap : 0, 0, { 0 } };
+    mut_tables mt = { NULL, NULL, NULL };
+    uint32_t sz;
+    if (mutant >= TSQO_MUT_COUNT) return 0;
+    if (mutant == TSQO_MUT_SECOND_RECENT || mutant == TSQO_MUT_SKIP_PREV_TILE) {
+        mt.last = (uint32_t *)calloc(3u * TSQO_HASH_ENTRIES, sizeof(uint32_t));
+        if (!mt.last) return 0;
+        mt.prev = mt.last + TSQO_HASH_ENTRIES; mt.older = mt.prev + TSQO_HASH_ENTRIES;
+    }
+    sz = encode_body(in, n, out, ext, table, 1, mutant, &tr, &mt);
+    free(mt.last);
+    if (trace_count) *trace_count = tr.count;
+    return sz;
 }
 
 /* -------------------------------------------------------------------------

@@ -47,6 +47,67 @@ uint32_t tsqo_encode_block(const uint8_t *in, uint32_t n, uint8_t *out,
                            uint32_t ext, uint16_t *table);
 
 /*
+ * The same encoder, instrumented and mutable (tsq_oracle.c compiles ONE body into both entry points:
+ * tsqo_encode_block carries no trace or mutant test in its loops).  tests/encgen.py turns the trace
+ * into a census of the encoder's rules and the mutants into a kill matrix.
+ *
+ * Trace: one record per probed position, in the scan loop and in the chain loop.
+ */
+typedef struct {
+    uint32_t i;                 /* probed position */
+    uint32_t pos;               /* the candidate the table gave */
+    uint32_t origin_at_offset;  /* pair origin when `offset` was computed (before a forced flush) */
+    uint32_t origin_at_test;    /* pair origin when the match was tested / its length clamped */
+    uint32_t offset;            /* origin_at_offset - pos (the value the acceptance test saw) */
+    uint32_t k_raw;             /* raw common prefix, 0xFFFFFFFF where none was computed */
+    uint32_t k;                 /* after the room clamp */
+    uint32_t outcome;           /* TSQO_OUT_* */
+    uint32_t flags;             /* TSQO_TF_*; the match's nibble in bits 8..11 */
+    uint32_t flush;             /* TSQO_FL_*; the bytes flushed before a match in bits 8.. */
+} tsqo_trace_rec;
+
+enum {
+    TSQO_OUT_LITERAL = 0,           /* scan probe refused: the byte stays pending */
+    TSQO_OUT_MATCH = 1,
+    TSQO_OUT_BREAK_WORD = 2,        /* chain probe: four bytes differ */
+    TSQO_OUT_BREAK_OFFSET = 3,      /* chain probe: offset outside [4, 0xFFFE] */
+    TSQO_OUT_BREAK_SHORT = 4,       /* accepted probe, but k < 4 after the room clamp */
+    TSQO_OUT_BREAK_TAIL = 5,        /* chain probe at i >= n - 5 */
+    TSQO_OUT_END = 6,               /* scan reached n */
+    TSQO_OUT_BREAK_OFFSET_LATE = 7  /* accepted scan probe whose offset the forced flush moved out of range */
+};
+enum { TSQO_TF_WORD_EQUAL = 1, TSQO_TF_CHAIN_PROBE = 2 };
+enum { TSQO_FL_FORCED = 1, TSQO_FL_BEFORE_MATCH = 2 };
+
+/* Mutants: one deliberate single-rule error each.  0 is the oracle. */
+enum {
+    TSQO_MUT_NONE = 0,
+    TSQO_MUT_OFFSET_BOUND_PLUS,    /* offsets up to 0xFFFF accepted */
+    TSQO_MUT_OFFSET_BOUND_MINUS,   /* offsets up to 0xFFFD only */
+    TSQO_MUT_LO_GT,                /* lo > (i & 0xFFFF): a candidate 65 536 back becomes the position itself */
+    TSQO_MUT_ROOM_WHOLE,           /* the room clamp yields room, not room - 1 */
+    TSQO_MUT_ROOM_DROPPED,         /* no room clamp */
+    TSQO_MUT_CHAIN_N4,             /* chain goes on while i < n - 4 */
+    TSQO_MUT_CHAIN_N6,             /* chain goes on while i < n - 6 */
+    TSQO_MUT_FLUSH_AT_32,          /* forced flush at 33 pending bytes instead of 32 */
+    TSQO_MUT_OFFSET_AFTER_FLUSH,   /* offset recomputed after the forced flush */
+    TSQO_MUT_NIB17_PLUS, TSQO_MUT_NIB32_PLUS, TSQO_MUT_NIB32_MINUS, TSQO_MUT_NIB48_PLUS, TSQO_MUT_NIB48_MINUS,
+    TSQO_MUT_NIB64_PLUS, TSQO_MUT_NIB64_MINUS,   /* length_nibble thresholds off by one */
+    TSQO_MUT_CAP48,                /* extension cap 48 */
+    TSQO_MUT_NO_CHAIN_INSERT,      /* the table is not updated at chain positions */
+    TSQO_MUT_INSERT_POS0,          /* the table is updated for position 0 (no effect: it stores the 0 the table starts with) */
+    TSQO_MUT_SECOND_RECENT,        /* second most recent insertion when the most recent is at most 256 back: a missed twin */
+    TSQO_MUT_SKIP_PREV_TILE,       /* insertions of the previous 64-aligned tile ignored: a missed patch */
+    TSQO_MUT_TRIM_SPILL,           /* literal stores trimmed to their length: no spill into control / size bytes */
+    TSQO_MUT_COUNT
+};
+
+/* As tsqo_encode_block.  Writes at most `trace_cap` records (trace may be NULL) and stores the number
+ * of probes in *trace_count.  Returns 0 for an unknown mutant.  A mutant's stream may be invalid. */
+uint32_t tsqo_encode_block_traced(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t ext, uint16_t *table,
+                                  uint32_t mutant, tsqo_trace_rec *trace, uint64_t trace_cap, uint64_t *trace_count);
+
+/*
  * Decode one block stream.  `in_len` bounds the reads (the reference ignores
  * it and over-reads; we stop instead).  Writes exactly the header's size
  * bytes to `out` (never beyond) and returns that size; returns 0 with

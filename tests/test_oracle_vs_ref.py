@@ -56,3 +56,18 @@ def test_fuzz_large_blocks(oracle):
             assert_reference_stream("large", case, ext, a)
             back, st = oracle.decode_block(a, ext)
             assert st == 0 and back == data
+
+
+def test_traced_form_equals_plain_form_and_reference(oracle):
+    """tsqo_encode_block_traced is the same body as tsqo_encode_block (oracle/tsq_oracle.c: encode_body): with mutant 0 its bytes are
+    the plain form's and the reference's on the fuzz above, and it writes one record per probed position, none for position 0."""
+    n_cases = min(int(os.environ.get("TSQ_FUZZ_CASES", "3000")), len(REF["small_len"]))
+    groups = [("small", fuzzgen.oracle_vs_ref_small(n_cases)), ("large", fuzzgen.oracle_vs_ref_large())]
+    for group, cases in groups:
+        for case, (data, halo) in enumerate(cases):
+            for ext in (0, 1):
+                a, trace = oracle.encode_block_traced(data, ext, halo)
+                assert a == oracle.encode_block(data, ext, halo), (group, case, ext)
+                assert_reference_stream(group, case, ext, a)
+                assert trace.size >= 1 and int(trace["i"][0]) == 1 and np.all(np.diff(trace["i"].astype(np.int64)) > 0), (group, case, ext)
+
