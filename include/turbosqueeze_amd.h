@@ -308,6 +308,56 @@ int tsqa_decompress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const
                           void *d_out, size_t out_size, uint64_t *sizes, int32_t *item_status, void *hip_stream);
 
 /*
+ * Packed batches: the same compress, with every container's place chosen on the device once its size exists, so that the arena is
+ * dense.  The caller gives no out_at / out_cap; the call gives back the places.
+ *
+ * Layout rule (align: a power of two, 1 to 4096):
+ *   offsets[0] = 0
+ *   offsets[i + 1] = round_up(offsets[i] + sizes[i], align)     for i + 1 < n_items
+ *   offsets[n_items] = offsets[n_items - 1] + sizes[n_items - 1]     (the bytes used: no padding behind the last container)
+ * Container i is bytes [offsets[i], offsets[i] + sizes[i]) of the arena.  The padding bytes between containers are never written.
+ *
+ * tsqa_batch_bound: host only.  Room that always holds the container of an n-byte item, much tighter than tsqa_container_bound below
+ *   a block: 16, then per block 3 + min(TSQ_OUTPUT_SZ, 11 + k + k/8 + k/2) for its k bytes.  The sum over a batch's items (plus
+ *   align - 1 per item) always holds its packed arena.
+ * tsqa_plan_packed: host only.  The rule above: sizes[n_items] -> offsets[n_items + 1].  TSQA_ERR_ARG for n_items == 0, an align
+ *   that is not a power of two from 1 to 4096, or a NULL pointer.
+ */
+size_t tsqa_batch_bound(size_t n);
+int    tsqa_plan_packed(const uint64_t *sizes, uint32_t n_items, uint32_t align, uint64_t *offsets);
+
+/* Compress every item into a dense arena.  items: in_at and in_len as for tsqa_compress_batch_async (input ranges may overlap);
+ * out_at and out_cap are ignored.  Container i is byte for byte what tsqa_compress_device gives for item i alone, at d_out +
+ * offsets[i].  d_offsets (device, n_items + 1) and d_sizes (device, n_items) follow the layout rule and are always complete and
+ * correct for every item, also when the arena is too small.  Overflow: a frame is written only if it ends at or before out_size,
+ * and nothing at or past d_out + out_size is ever written; when offsets[n_items] > out_size, *d_status (device) becomes
+ * TSQA_ERR_OVERFLOW, every item that lies wholly inside out_size is complete and exact, and a retry with offsets[n_items] bytes of
+ * room succeeds.  TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL pointer, n_items == 0, an empty item,
+ * an input range past in_size, a bad align, out_size < 16.  Encoder variants 0, 6 and 7; the others are refused (TSQA_ERR_ARG).
+ * The asynchronous form returns at once and may be called again on the same stream before the first has run (a call that needs
+ * more scratch than any before it, more items or more blocks per launch, first waits for the device, then grows the scratch).
+ * tsqa_compress_batch_packed waits, fills offsets and sizes (host) and returns TSQA_ERR_OVERFLOW, with both tables filled, when
+ * the arena was too small. */
+int tsqa_compress_batch_packed_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                                     uint32_t ext, uint32_t align, void *d_out, size_t out_size, uint64_t *d_offsets,
+                                     uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
+int tsqa_compress_batch_packed(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                               uint32_t ext, uint32_t align, void *d_out, size_t out_size, uint64_t *offsets, uint64_t *sizes,
+                               void *hip_stream);
+
+/* tsqa_decompress_batch_async with each container's place read on the device: container i is bytes [d_offsets[i], d_offsets[i] +
+ * d_sizes[i]) of d_arena (both tables in device memory, as tsqa_compress_batch_packed_async leaves them: the two calls chain on one
+ * stream with no host read between them).  items (host): out_at and out_cap are used, in_at and in_len ignored; n_blocks (host) as
+ * for tsqa_decompress_batch_async.  The tables are not trusted: an item with offsets[i] + sizes[i] > arena_size, sizes[i] < 16 or a
+ * block count that sizes[i] bytes cannot hold is refused on the device like a malformed container (TSQA_ERR_FORMAT in *d_status,
+ * d_out_sizes[i] = 0, all or nothing) and is never read.  The host checks the output ranges (inside out_size, no overlap) and
+ * n_blocks[i] >= 1: TSQA_ERR_ARG.  TSQA_ERR_STALL as for tsqa_decompress_batch_async. */
+int tsqa_decompress_batch_packed_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets,
+                                       const uint64_t *d_sizes, const tsqa_batch_item *items, const uint32_t *n_blocks,
+                                       uint32_t n_items, void *d_out, size_t out_size, uint64_t *d_out_sizes, int32_t *d_status,
+                                       void *hip_stream);
+
+/*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
  * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
  * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.

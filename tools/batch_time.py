@@ -4,7 +4,13 @@ each, warm-ups first, the median of --reps.  Shapes (text):
   text_1024x1MiB      1 024 items of 1 MiB
   mixed_1B_9MiB       300 items of 1 B ... 9 MiB (log-uniform)
 Prints one JSON line per shape (and writes them to --out): compress / decompress milliseconds of both ways, their ratio, and whether
-the batch's bytes equal the loop's.  The loop's items get the same input and output offsets as the batch's."""
+the batch's bytes equal the loop's.  The loop's items get the same input and output offsets as the batch's.
+The packed column per shape (one more JSON line each, written to --packed-out, profiles/packed_time.jsonl unless --no-packed):
+tsqa_compress_batch_packed_async into a dense arena; the route to the same arena without it (the unpacked tsqa_compress_batch_async, a
+synchronise, the sizes read back, torch.cat of the trimmed views); the unpacked compress alone before and after, whose reps give the
+run-to-run spread; the arena bytes used against the unpacked arena.  --only-packed skips the loops and the decompress side.  The packed
+call does strictly less than the dense route: the tool ends with status 1, its lines written, when a shape's packed median is above
+its dense route's.  profiles/packed_time.jsonl is `python tools/batch_time.py --only-packed`."""
 import argparse
 import ctypes as C
 import json
@@ -22,7 +28,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--ext", type=int, default=1)
     ap.add_argument("--out", default=None, help="also write the JSON lines to this file")
+    ap.add_argument("--packed-out", default=os.path.join(ROOT, "profiles", "packed_time.jsonl"), help="the packed column's JSON lines go to this file")
+    ap.add_argument("--no-packed", action="store_true", help="skip the packed column")
+    ap.add_argument("--only-packed", action="store_true", help="skip the single-call loops and the decompress side")
+    ap.add_argument("--align", type=int, default=16, help="alignment of the packed containers")
     args = ap.parse_args()
+    if args.no_packed:
+        args.packed_out = None
     import numpy as np
     import torch
     import turbosqueeze_amd as tsq
@@ -41,7 +53,7 @@ def main():
         "mixed_1B_9MiB": [int(x) for x in np.exp(rng.uniform(0, np.log(9 << 20), 300))],
     }
 
-    def timed(enqueue):
+    def timed(enqueue, spread=None):
         times = []
         for r in range(args.warmup + args.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -53,9 +65,60 @@ def main():
                 raise SystemExit(f"device status {codec.status()}")
             if r >= args.warmup:
                 times.append(e0.elapsed_time(e1))
+        if spread is not None:
+            spread.extend(times)
         return round(statistics.median(times), 3)
 
-    lines = []
+    def packed_column(name, lengths, src, items, arr, out, d_sizes, caps):
+        """the packed call, today's dense route and the unpacked compress alone (before and after), alternating"""
+        n, st = len(items), codec._status.data_ptr()
+        arena = torch.zeros(sum(caps) + n * (args.align - 1), dtype=torch.uint8, device="cuda")
+        d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        d_psizes = torch.zeros(n, dtype=torch.int64, device="cuda")
+        dense = {}
+
+        def unpacked():
+            rc = L.tsqa_compress_batch_async(codec.h, src.data_ptr(), src.numel(), arr, n, args.ext, out.data_ptr(), out.numel(),
+                                             d_sizes.data_ptr(), st, hs)
+            assert rc == 0, codec.last_error()
+
+        def packed(align=args.align):
+            rc = L.tsqa_compress_batch_packed_async(codec.h, src.data_ptr(), src.numel(), arr, n, args.ext, align, arena.data_ptr(), arena.numel(),
+                                                    d_offsets.data_ptr(), d_psizes.data_ptr(), st, hs)
+            assert rc == 0, codec.last_error()
+
+        def route():
+            unpacked()
+            s.synchronize()
+            sizes = d_sizes.cpu().tolist()
+            dense["arena"] = torch.cat([out[a:a + z] for (_, _, a, _), z in zip(items, sizes)])
+
+        res = {"shape": name, "items": n, "bytes": sum(lengths), "reps": args.reps, "align": args.align}
+        before, after = [], []
+        res["unpacked_ms"] = timed(unpacked, before)
+        res["packed_ms"] = timed(packed)
+        res["dense_route_ms"] = timed(route)
+        res["unpacked_again_ms"] = timed(unpacked, after)
+        # the packed call against the unpacked compress alone, and the unpacked reps' own spread about their median (both runs pooled)
+        pooled = statistics.median(before + after)
+        res["unpacked_spread_ms"] = [round(min(before + after), 3), round(max(before + after), 3)]
+        res["unpacked_spread_over_median"] = [round(min(before + after) / pooled, 3), round(max(before + after) / pooled, 3)]
+        res["packed_over_unpacked"] = round(res["packed_ms"] / pooled, 3)
+        res["packed_exceeds_unpacked_spread"] = res["packed_ms"] > max(before + after)
+        res["packed_over_dense_route"] = round(res["packed_ms"] / res["dense_route_ms"], 3)
+        res["packed_not_slower_than_dense_route"] = res["packed_ms"] <= res["dense_route_ms"]
+        offsets = d_offsets.cpu().tolist()
+        res["arena_used_bytes"] = offsets[-1]
+        res["arena_unpacked_bytes"] = sum(caps)
+        res["arena_used_over_unpacked"] = round(offsets[-1] / sum(caps), 4)
+        res["offsets_follow_plan"] = offsets == tsq.plan_packed(d_psizes.cpu().tolist(), args.align)
+        # align 1 gives the very arena of the dense route
+        packed(1)
+        s.synchronize()
+        res["same_bytes_as_dense_route"] = bool(torch.equal(arena[:int(d_offsets[-1])], dense["arena"]))
+        return res
+
+    lines, packed_lines, slower = [], [], 0
     for name, lengths in shapes.items():
         total = sum(lengths)
         src = torch.from_numpy(tsq.synth.text(total, seed=5)).cuda()
@@ -78,6 +141,15 @@ def main():
                 rc = L.tsqa_compress_device_async(codec.h, src.data_ptr() + o, n, out.data_ptr() + a, c, sz, st, args.ext, hs)
                 assert rc == 0, codec.last_error()
 
+        if args.packed_out:
+            col = packed_column(name, lengths, src, items, arr, out, d_sizes, caps)
+            slower += not col["packed_not_slower_than_dense_route"]
+            packed_lines.append(json.dumps(col))
+            print(packed_lines[-1], flush=True)
+            if args.only_packed:
+                del src, out
+                torch.cuda.empty_cache()
+                continue
         res = {"shape": name, "items": len(lengths), "bytes": total, "blocks": sum(-(-n // tsq.BLOCK_SZ) for n in lengths), "reps": args.reps}
         res["compress_loop_ms"] = timed(loop_c)
         loop_bytes = out.clone()
@@ -116,9 +188,14 @@ def main():
         lines.append(line)
         del src, out, back
         torch.cuda.empty_cache()
-    if args.out:
+    if args.out and lines:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+    if args.packed_out:
+        with open(args.packed_out, "w") as f:
+            f.write("\n".join(packed_lines) + "\n")
+    if slower:
+        raise SystemExit(f"the packed call is slower than the dense route on {slower} shape(s)")
 
 
 if __name__ == "__main__":

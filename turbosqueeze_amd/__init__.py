@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     BlockGroup,
     DeviceCodec,
     ItemRange,
+    PackedBatch,
     Range,
     RangeIndex,
     RangeItem,
@@ -24,6 +25,7 @@ from .api import (  # noqa: F401
     lib_path,
     plan_batch,
     plan_item_ranges,
+    plan_packed,
     plan_ranges,
     source_fingerprint,
     tsq_compress_mt,

@@ -179,6 +179,16 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_batch_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_batch.restype = C.c_int
     L.tsqa_decompress_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_batch_bound.restype = C.c_size_t
+    L.tsqa_batch_bound.argtypes = [C.c_size_t]
+    L.tsqa_plan_packed.restype = C.c_int
+    L.tsqa_plan_packed.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.tsqa_compress_batch_packed_async.restype = C.c_int
+    L.tsqa_compress_batch_packed_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.tsqa_compress_batch_packed.restype = C.c_int
+    L.tsqa_compress_batch_packed.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_decompress_batch_packed_async.restype = C.c_int
+    L.tsqa_decompress_batch_packed_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_index_create_batch.restype = C.c_int
     L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
     L.tsqa_index_items.restype = C.c_uint32
@@ -348,6 +358,18 @@ def batch_bound(n: int) -> int:
     return cap
 
 
+def plan_packed(sizes, align: int = 16):
+    """tsqa_plan_packed (host only): the packed layout of containers of the given sizes -> their offsets, then the bytes used
+    (offsets[i + 1] = round_up(offsets[i] + sizes[i], align), the last without the rounding).  Raises TsqError(3) when refused."""
+    import numpy as np
+    sz = np.ascontiguousarray(sizes, dtype=np.uint64)
+    offsets = np.zeros(len(sz) + 1, dtype=np.uint64)
+    rc = lib().tsqa_plan_packed(sz.ctypes.data, len(sz), align, offsets.ctypes.data)
+    if rc:
+        raise TsqError(rc, "tsqa_plan_packed refused the sizes")
+    return [int(x) for x in offsets]
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -469,6 +491,35 @@ class BatchIndex(RangeIndex):
     def read_flat_many(self, ranges, out=None):
         """RangeIndex.read_many on the concatenation of the healthy items' data: (offset, length) ranges."""
         return RangeIndex.read_many(self, ranges, out)
+
+
+class PackedBatch:
+    """What DeviceCodec.compress_batch_packed gives: the containers of a batch one after the other in a dense arena.
+    arena: the used bytes (offsets[-1] of them); offsets (n + 1) and sizes (n): host ints, container i = arena[offsets[i]:offsets[i] +
+    sizes[i]] = views[i]; lengths: the items' uncompressed sizes."""
+
+    def __init__(self, codec: "DeviceCodec", arena, offsets, sizes, lengths):
+        self.codec, self.arena, self.offsets, self.sizes, self.lengths = codec, arena, offsets, sizes, lengths
+        self.views = [arena[o:o + n] for o, n in zip(offsets, sizes)]
+
+    def decompress(self, out=None):
+        """The items back, through tsqa_decompress_batch (which decodes again by itself after TSQA_ERR_STALL): a list of views into
+        one output arena (`out`, or a new one of sum(lengths) bytes)."""
+        codec, items, at = self.codec, [], 0
+        for o, n, ln in zip(self.offsets, self.sizes, self.lengths):
+            items.append((o, n, at, ln))
+            at += ln
+        out = codec._out_arena(out, at)
+        got = (C.c_uint64 * len(items))()
+        rc = codec.L.tsqa_decompress_batch(codec.h, self.arena.data_ptr(), self.arena.numel(), _batch_array(items), len(items), out.data_ptr(),
+                                           out.numel(), got, None, codec._stream())
+        if rc:
+            raise codec._err(rc)
+        return [out[a:a + int(got[k])] for k, (_, _, a, _) in enumerate(items)]
+
+    def index(self) -> "BatchIndex":
+        """One index over the dense arena, for record reads: index().read(item, offset, length)."""
+        return BatchIndex(self.codec, self.arena, list(zip(self.offsets, self.sizes)))
 
 
 DONE_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_bool, C.c_void_p)
@@ -701,6 +752,34 @@ class DeviceCodec:
             raise self._err(rc)
         return [out[a:a + int(sizes[k])] for k, (_, _, a, _) in enumerate(items)]
 
+    def compress_batch_packed(self, srcs, ext: int, out=None, align: int = 16) -> PackedBatch:
+        """compress_batch into a dense arena: container i starts where container i - 1 ended, rounded up to `align` (a power of two,
+        1 to 4096); the places are made on the device once the sizes exist.  -> a PackedBatch whose arena is `out`, or a new tensor
+        of the sum(batch_bound(n)) worst case, trimmed to the bytes used.  (The trimmed view keeps the worst-case allocation alive:
+        to hold only the used bytes, compress again into an `out` of offsets[-1] bytes.)  An `out` that is too small raises
+        TsqError(6) with .needed = the bytes a retry needs."""
+        align = int(align)
+        if not 1 <= align <= 4096 or align & (align - 1):
+            raise TsqError(3, f"align {align} is not a power of two from 1 to 4096")
+        if out is not None and (out.dtype != self.torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != self.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        arena, offs = self._arena(srcs)
+        items = [(o, t.numel(), 0, 0) for o, t in zip(offs, srcs)]
+        if out is None:
+            worst = sum(batch_bound(t.numel()) for t in srcs) + (len(srcs) - 1) * (align - 1)           # (and the padding between them)
+            out = self.torch.empty(worst, dtype=self.torch.uint8, device=self.device)
+        offsets = (C.c_uint64 * (len(items) + 1))()
+        sizes = (C.c_uint64 * len(items))()
+        rc = self.L.tsqa_compress_batch_packed(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), len(items), int(ext), int(align),
+                                               out.data_ptr(), out.numel(), offsets, sizes, self._stream())
+        if rc:
+            e = self._err(rc)
+            if rc == 6:
+                e.needed = int(offsets[len(items)])
+            raise e
+        offsets = [int(x) for x in offsets]
+        return PackedBatch(self, out[:offsets[-1]], offsets, [int(x) for x in sizes], [t.numel() for t in srcs])
+
     def decompress_batch(self, blobs, out=None):
         """Decompress many .tsq containers (1-D uint8 CUDA tensors) in one call.  -> a list of views into one output arena, each trimmed
         to its item's size.  A refused item raises TsqError with .item_status (one TSQA_ERR_* or 0 per item) and .results (the views,
@@ -747,6 +826,31 @@ class DeviceCodec:
         nb = np.ascontiguousarray(n_blocks, dtype=np.uint32)
         rc = self.L.tsqa_decompress_batch_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), nb.ctypes.data, len(items),
                                                 out.data_ptr(), out.numel(), d_sizes.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+
+    def compress_batch_packed_async(self, arena, items, ext: int, align: int, out, d_offsets, d_sizes) -> None:
+        """tsqa_compress_batch_packed_async on the current stream, nothing waited for: items = (in_at, in_len) offsets into the uint8
+        CUDA tensor arena (longer tuples: the rest is ignored); the containers land packed in out, their places in d_offsets (int64
+        CUDA tensor, one more than items) and d_sizes (one per item), the status in status()."""
+        quads = [(it[0], it[1], 0, 0) for it in items]
+        rc = self.L.tsqa_compress_batch_packed_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(quads), len(quads), int(ext), int(align),
+                                                     out.data_ptr(), out.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
+                                                     self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def decompress_batch_packed_async(self, arena, d_offsets, d_sizes, items, n_blocks, out, d_out_sizes) -> None:
+        """tsqa_decompress_batch_packed_async on the current stream: the containers' places are read from d_offsets and d_sizes on
+        the device (as compress_batch_packed_async left them); items = (out_at, out_cap) offsets into out, n_blocks each container's
+        block count; the uncompressed sizes land in d_out_sizes (int64 CUDA tensor), the status in status()."""
+        import numpy as np
+        nb = np.ascontiguousarray(n_blocks, dtype=np.uint32)
+        quads = [(0, 0, it[-2], it[-1]) for it in items]
+        rc = self.L.tsqa_decompress_batch_packed_async(self.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
+                                                       _batch_array(quads), nb.ctypes.data, len(quads), out.data_ptr(), out.numel(),
+                                                       d_out_sizes.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 

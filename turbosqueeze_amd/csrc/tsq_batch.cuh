@@ -47,6 +47,96 @@ __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* _
     }
 }
 
+// Exclusive sum of v over the 256 threads of a workgroup, for sums below 2^55 (a batch has at most 2^32 - 1 blocks, so every sum of
+// container sizes is): two 32-bit DPP scans per wavefront, of the low 24 bits and of the rest, then the four wavefront totals through
+// LDS.  *total = the workgroup's sum.  Every thread of the workgroup calls it (the DPP steps read the neighbouring lanes): the
+// workgroup is exactly 256 threads, four full wavefronts, and wave_scan_add is an inclusive sum over 64 active lanes.
+__device__ __forceinline__ uint64_t group_scan_excl64(uint64_t v, uint64_t* wave_sum /* LDS, 4 */, uint64_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint64_t incl = ((uint64_t)wave_scan_add((uint32_t)(v >> 24)) << 24) + wave_scan_add((uint32_t)v & 0xFFFFFFu);
+    __syncthreads();                                         // (the previous call's totals have been read)
+    if (lane == 63u) wave_sum[wid] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (uint32_t w = 0; w < 4u; ++w) { const uint64_t s = wave_sum[w]; if (w < wid) before += s; all += s; }
+    *total = all;
+    return before + incl - v;
+}
+
+// batch_pack_scan_kernel for a packed batch (tsqa_compress_batch_packed*): the items' places are made here, not taken from the
+// caller.  Item i starts at offsets[i]; offsets[i + 1] = round_up(offsets[i] + sizes[i], align), the last without the rounding.
+// ONE workgroup per encode launch: a launch holds at most 2 x CUs blocks, hence at most 2 x CUs + 1 items, and every one of them
+// but the last is complete in it, so their starts are offsets[i0] + an exclusive sum of round_up(size, align) over the launch's
+// items (offsets[i] is a multiple of align, so the rounding may be done per item).  offsets[] is the carry between launches: the
+// first launch writes offsets[0] = 0, an item that a launch completes writes its successor's start, and the next launch reads
+// offsets[i0] whether its first item continues (its start) or begins there (what the last complete item left).  An item that
+// continues keeps its running frame offset in run_at[i], as in batch_pack_scan_kernel.  A header or frame is written only if it ends
+// inside out_size; sizes[] and offsets[] are complete whatever fits.
+__global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0,
+                                                                     uint32_t ni, uint64_t b0, uint32_t nb,
+                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
+                                                                     uint8_t* __restrict__ out, uint64_t out_size,
+                                                                     uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
+                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                     int32_t* __restrict__ status)
+{
+    __shared__ uint64_t wave_sum[4];
+    const uint64_t launch_end = b0 + nb, mask = (uint64_t)align - 1u;
+    uint64_t base = b0 == 0 ? 0ull : d_offsets[i0];          // where the launch's first item starts
+    if (b0 == 0 && threadIdx.x == 0) d_offsets[0] = 0;
+    for (uint32_t j0 = 0; j0 < ni; j0 += 256u) {
+        const uint32_t j = j0 + threadIdx.x, i = i0 + (j < ni ? j : 0u);
+        const bool valid = j < ni;
+        uint64_t first = 0, end = 0, at0 = 0, at = 0, in_len = 0;
+        uint32_t n_blocks = 0;
+        if (valid) {
+            const BatchItem it = items[i];
+            first = it.first_block; end = first + it.n_blocks; in_len = it.in_len; n_blocks = it.n_blocks;
+            at0 = at = first >= b0 ? kHeaderSize : run_at[i];
+            for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) at += kFrameWordSize + sizes[(uint32_t)(b - b0)];
+        }
+        const bool complete = valid && end <= launch_end;    // (only the launch's last item can be incomplete: it adds nothing)
+        uint64_t total;
+        const uint64_t start = base + group_scan_excl64(complete ? (at + mask) & ~mask : 0ull, wave_sum, &total);
+        base += total;
+        if (valid) {                                         // (no lane leaves the loop early: the scan above needs them all)
+            if (first >= b0 && start + kHeaderSize <= out_size) write_header(out + start, n_blocks, in_len);
+            uint64_t w = at0;
+            for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) {
+                const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
+                const uint64_t next = w + kFrameWordSize + sz;
+                if (start + next <= out_size) { write_frame(out + start + w, sz, ext); frame_at[k] = start + w; }
+                else frame_at[k] = kNoFrame;
+                w = next;
+            }
+            run_at[i] = at;
+        }
+        if (complete) {
+            const bool last = i + 1u == n_items;
+            d_sizes[i] = at;
+            d_offsets[i + 1u] = last ? start + at : start + ((at + mask) & ~mask);
+            if (last && start + at > out_size) atomicMax(status, kErrOverflow);
+        }
+    }
+}
+
+// Before batch_walk_kernel in tsqa_decompress_batch_packed_async: one lane per item takes its container's place from tables in
+// device memory (what batch_pack_scan_packed_kernel wrote, or anything else: they are not trusted).  A place that does not lie
+// inside the arena, or that is too short for a header or for the item's block count, becomes an empty input range, which
+// batch_walk_kernel refuses (kErrFormat, d_sizes[i] = 0) without reading a byte of it.
+__global__ __launch_bounds__(256) void batch_place_kernel(BatchItem* __restrict__ items, uint32_t n_items,
+                                                          const uint64_t* __restrict__ d_offsets, const uint64_t* __restrict__ d_sizes,
+                                                          uint64_t arena_size)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const uint64_t at = d_offsets[i], n = d_sizes[i];
+    const bool ok = n <= arena_size && at <= arena_size - n && n >= kHeaderSize && items[i].n_blocks <= (n - kHeaderSize) / kMinFrameSize;
+    items[i].in_at = ok ? at : 0ull;
+    items[i].in_len = ok ? n : 0ull;
+}
+
 // Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.
 // grid = (pieces, blocks of the launch).
 __global__ __launch_bounds__(256) void batch_pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,

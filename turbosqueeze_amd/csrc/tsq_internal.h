@@ -46,10 +46,11 @@ struct tsqa_ctx {
     void* sharded_out = nullptr;
     void forget_sharded() { sharded_n_local = 0; sharded_streams = nullptr; sharded_out = nullptr; }
     tsqa_uploads range_up, batch_up;           // range-read items; batch descriptors
-    // batches: per item, the running frame offset of a compress batch across its launches, and the sizes and headers the
-    // synchronous forms read back
+    // batches: per item, the running frame offset of a compress batch across its launches, and the sizes, the offsets of a packed
+    // batch (one more than items) and the headers the synchronous forms read back
     uint64_t* batch_at = nullptr;
     uint64_t* batch_sizes = nullptr;
+    uint64_t* batch_offsets = nullptr;
     uint8_t* batch_heads = nullptr;
     size_t cap_batch = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
@@ -72,7 +73,7 @@ struct tsqa_ctx {
     void prof_end(int kind, hipStream_t s);
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-    int reserve(size_t n_blocks, bool want_tables, bool want_slots = true);
+    int reserve(size_t n_blocks, bool want_tables, bool want_slots = true, bool all_streams = false);
     int reserve_duo(size_t n_blocks);
     int reserve_host_frames(size_t n);
     // the next slot of `u`, once the call that used it has finished, with room for `bytes`

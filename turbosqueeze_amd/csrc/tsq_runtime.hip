@@ -143,7 +143,7 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
             if (u->host[k]) (void)hipHostFree(u->host[k]);
             if (u->done[k]) (void)hipEventDestroy(u->done[k]);
         }
-    (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_heads);
+    (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
     delete c;
 }
 
@@ -155,12 +155,15 @@ extern "C" void tsqa_set_decode_wait_limit(tsqa_ctx* c, uint32_t polls) { if (c)
 // Scratch in HBM, grown on demand and kept: slots (TSQ_OUTPUT_SZ per block, the reference's
 // per-block output buffer, tsq_context.cpp:89-143), per-block sizes, frame offsets, frame
 // descriptors and one 256 KiB position table per block for the encoders (want_tables).
-int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots)
+// Growing waits for the context's stream, or (all_streams: the batch entry points, which promise that a call may be enqueued behind
+// another on a caller's stream) for the whole device: a call enqueued there may still be using what is freed.
+int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool all_streams)
 {
     (void)hipSetDevice(device);
+    auto wait = [&] { if (all_streams) (void)hipDeviceSynchronize(); else (void)hipStreamSynchronize(stream); };
     if (n_blocks > cap_blocks) {
         size_t nb = n_blocks;
-        (void)hipStreamSynchronize(stream);
+        wait();
         (void)hipFree(sizes); (void)hipFree(frame_at); (void)hipFree(frames);
         sizes = nullptr; frame_at = nullptr; frames = nullptr; cap_blocks = 0;
         forget_sharded();                                // (the descriptors of a sharded decode went with `frames`)
@@ -170,13 +173,13 @@ int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots)
         cap_blocks = nb;
     }
     if (want_slots && n_blocks > cap_slots) {        // (callers that bring their own slots -- the sharded block API -- never pay for these)
-        (void)hipStreamSynchronize(stream);
+        wait();
         (void)hipFree(slots); slots = nullptr; cap_slots = 0;
         TSQ_HIP(this, hipMalloc(&slots, n_blocks * (size_t)kSlotSize + 256));
         cap_slots = n_blocks;
     }
     if (want_tables && n_blocks > cap_tables) {
-        (void)hipStreamSynchronize(stream);
+        wait();
         (void)hipFree(tables); tables = nullptr; cap_tables = 0;
         TSQ_HIP(this, hipMalloc(&tables, n_blocks * (size_t)kHashEntries * sizeof(uint16_t)));
         cap_tables = n_blocks;
@@ -242,12 +245,14 @@ int tsqa_ctx::reserve_batch(size_t n_items)
 {
     (void)hipSetDevice(device);
     if (n_items <= cap_batch) return TSQA_OK;
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_heads);
-    batch_at = nullptr; batch_sizes = nullptr; batch_heads = nullptr; cap_batch = 0;
+    // (batch calls run on callers' streams too, and one enqueued there may still be using the tables that are freed below)
+    (void)hipDeviceSynchronize();
+    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_offsets); (void)hipFree(batch_heads);
+    batch_at = nullptr; batch_sizes = nullptr; batch_offsets = nullptr; batch_heads = nullptr; cap_batch = 0;
     size_t want = 256; while (want < n_items) want *= 2;
     TSQ_HIP(this, hipMalloc(&batch_at, want * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_sizes, want * sizeof(uint64_t)));
+    TSQ_HIP(this, hipMalloc(&batch_offsets, (want + 1) * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_heads, want * kHeaderSize));
     cap_batch = want;
     return TSQA_OK;
@@ -980,17 +985,21 @@ extern "C" int tsqa_decompress_item_ranges(tsqa_ctx* c, const tsqa_index* idx, c
 
 // ---- batches: many independent items at offsets in one input and one output buffer ----
 
-enum BatchPlan { kPlanCompress, kPlanDecompress, kPlanRangesOnly };
+enum BatchPlan { kPlanCompress, kPlanDecompress, kPlanRangesOnly, kPlanPlaced, kPlanPacked };
 
 // tsqa_plan_batch, with the reason for a refusal.  kPlanRangesOnly: the ranges and input lengths of a decompress batch whose block
-// counts are not known yet (first_block is not written).
+// counts are not known yet (first_block is not written).  kPlanPlaced: a decompress batch whose containers are placed by tables on
+// the device (tsqa_decompress_batch_packed_async): the output ranges and the block counts; in_at and in_len are not looked at.
+// kPlanPacked: a compress batch whose output places are made on the device (tsqa_compress_batch_packed_async): kPlanCompress
+// without output ranges; out_at and out_cap are not looked at.
 static int plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_size, size_t out_size, const uint32_t* n_blocks,
                       uint64_t* first_block, const char** why, BatchPlan mode)
 {
     *why = "";
     if (!items || n_items == 0) { *why = "no items"; return TSQA_ERR_ARG; }
     auto blocks_of = [&](uint32_t i) -> uint64_t {
-        return mode == kPlanCompress ? items[i].in_len / kBlockSize + (items[i].in_len % kBlockSize != 0) : mode == kPlanDecompress ? n_blocks[i] : 0;
+        return mode == kPlanCompress || mode == kPlanPacked ? items[i].in_len / kBlockSize + (items[i].in_len % kBlockSize != 0)
+               : mode == kPlanDecompress || mode == kPlanPlaced ? n_blocks[i] : 0;
     };
     std::vector<std::pair<uint64_t, uint64_t>> dst;
     dst.reserve(n_items);
@@ -998,11 +1007,16 @@ static int plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_
     for (uint32_t i = 0; i < n_items; ++i) {
         const tsqa_batch_item& x = items[i];
         const uint64_t nb = blocks_of(i);
-        if (x.in_len == 0) { *why = "an item is empty"; return TSQA_ERR_ARG; }
-        if (x.in_len > in_size || x.in_at > in_size - x.in_len) { *why = "an input range ends past in_size"; return TSQA_ERR_ARG; }
+        if (mode == kPlanPlaced) {
+            if (nb == 0) { *why = "a block count of 0"; return TSQA_ERR_ARG; }
+        } else {
+            if (x.in_len == 0) { *why = "an item is empty"; return TSQA_ERR_ARG; }
+            if (x.in_len > in_size || x.in_at > in_size - x.in_len) { *why = "an input range ends past in_size"; return TSQA_ERR_ARG; }
+        }
+        if (mode == kPlanPacked) { blocks += nb; continue; }
         if (x.out_cap > out_size || x.out_at > out_size - x.out_cap) { *why = "an output range ends past out_size"; return TSQA_ERR_ARG; }
         if (mode == kPlanCompress && x.out_cap < kHeaderSize + kMinFrameSize * nb) { *why = "an output range holds less than 16 + 6 bytes per block"; return TSQA_ERR_ARG; }
-        if (mode != kPlanCompress && x.in_len < kHeaderSize) { *why = "an input range is shorter than a header"; return TSQA_ERR_ARG; }
+        if ((mode == kPlanDecompress || mode == kPlanRangesOnly) && x.in_len < kHeaderSize) { *why = "an input range is shorter than a header"; return TSQA_ERR_ARG; }
         if (mode == kPlanDecompress && (nb == 0 || nb > (x.in_len - kHeaderSize) / kMinFrameSize)) { *why = "a block count that the container cannot hold"; return TSQA_ERR_ARG; }
         if (x.out_cap) dst.emplace_back(x.out_at, x.out_cap);
         blocks += nb;
@@ -1027,18 +1041,14 @@ extern "C" int tsqa_plan_batch(const tsqa_batch_item* items, uint32_t n_items, s
     return plan_batch(items, n_items, in_size, out_size, n_blocks, first_block, &why, n_blocks ? kPlanDecompress : kPlanCompress);
 }
 
-extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                                         uint32_t ext, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+// The launches of a compress batch whose arguments have been checked; first[] is its block plan (tsqa_plan_batch).  align == 0: the
+// caller's output ranges (tsqa_compress_batch_async).  align > 0: a packed batch (tsqa_compress_batch_packed_async): the items'
+// places are made on the device and land in d_offsets.
+static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batch_item* items, uint32_t n_items, const std::vector<uint64_t>& first,
+                                  uint32_t ext, void* d_out, size_t out_size, uint32_t align, uint64_t* d_offsets, uint64_t* d_sizes,
+                                  int32_t* d_status, hipStream_t s)
 {
     static_assert(sizeof(tsqa_batch_item) == 32 && sizeof(BatchItem) == 48 && sizeof(EncBatchBlock) == 24, "descriptor layouts");
-    if (!c) return TSQA_ERR_ARG;
-    if (!d_in || !d_out || !d_sizes || !d_status) { c->set_error("compress_batch: null pointer"); return TSQA_ERR_ARG; }
-    const int v = c->enc_variant;
-    if (v != 0 && v != 6 && v != 7) { c->set_error("compress_batch: encoder variant %d does not take batches (0, 6 and 7 do)", v); return TSQA_ERR_ARG; }
-    std::vector<uint64_t> first((size_t)n_items + 1);
-    const char* why;
-    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanCompress)) { c->set_error("compress_batch: %s", why); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     (void)hipSetDevice(c->device);
     const uint64_t n_blocks = first[n_items];
     // A launch takes at most 2 x n_cus blocks, the lean layout's chip-filling count: the scratch -- a slot and a position table per
@@ -1047,7 +1057,7 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
     const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), bytes = item_bytes + n_blocks * sizeof(EncBatchBlock);
     int k = 0;
     if (int rc = c->reserve_upload(c->batch_up, bytes, &k)) return rc;
-    if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true)) return rc;
+    if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true, true, true)) return rc;
     if (int rc = c->reserve_batch(n_items)) return rc;
     uint8_t* const host = static_cast<uint8_t*>(c->batch_up.host[k]);
     BatchItem* const hi = reinterpret_cast<BatchItem*>(host);
@@ -1055,7 +1065,7 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
     for (uint32_t i = 0; i < n_items; ++i) {
         const tsqa_batch_item& x = items[i];
         const uint32_t nb = (uint32_t)(first[i + 1] - first[i]);
-        hi[i] = BatchItem{x.in_at, x.in_len, x.out_at, x.out_cap, first[i], nb, 0u};
+        hi[i] = align ? BatchItem{x.in_at, x.in_len, 0, 0, first[i], nb, 0u} : BatchItem{x.in_at, x.in_len, x.out_at, x.out_cap, first[i], nb, 0u};
         for (uint32_t j = 0; j < nb; ++j) {
             const uint64_t b = first[i] + j, off = (uint64_t)j * kBlockSize, left = x.in_len - off;
             hb[b] = EncBatchBlock{x.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
@@ -1078,8 +1088,12 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
         rc = launch_batch_encode_kernels(c, in, db + b0, nb, ext, c->slots, c->sizes, d_status, s);
         if (rc) { if (timed) c->prof_used[0]--; break; }
         if (timed) c->prof_end(0, s);
-        hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
-                           c->batch_at, c->frame_at, d_sizes, d_status);
+        if (align)                       // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+            hipLaunchKernelGGL(batch_pack_scan_packed_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, c->sizes, ext, align, out,
+                               (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_status);
+        else
+            hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
+                               c->batch_at, c->frame_at, d_sizes, d_status);
         hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out);
     }
     // (behind the last kernel: neither copy of the descriptors is touched again before the batch that uses them has finished)
@@ -1088,6 +1102,27 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
+}
+
+static bool batch_encoder_ok(tsqa_ctx* c, const char* who)
+{
+    const int v = c->enc_variant;
+    if (v == 0 || v == 6 || v == 7) return true;
+    c->set_error("%s: encoder variant %d does not take batches (0, 6 and 7 do)", who, v);
+    return false;
+}
+
+extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                         uint32_t ext, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_in || !d_out || !d_sizes || !d_status) { c->set_error("compress_batch: null pointer"); return TSQA_ERR_ARG; }
+    if (!batch_encoder_ok(c, "compress_batch")) return TSQA_ERR_ARG;
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanCompress)) { c->set_error("compress_batch: %s", why); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, out_size, 0u, nullptr, d_sizes, d_status, s);
 }
 
 extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items, uint32_t ext,
@@ -1106,26 +1141,106 @@ extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size
     return status_to_rc(c, st, "compress_batch");
 }
 
-// (variant < 0: the context's decode variant; the synchronous form's retry after TSQA_ERR_STALL passes 4)
+// ---- packed batches: the items' containers one after the other in a dense arena, their places made on the device ----
+
+extern "C" size_t tsqa_batch_bound(size_t n)
+{
+    // the header, then per block its frame word and a stream of at most every byte a literal of its own, never more than a slot
+    const size_t full = n / kBlockSize, rest = n % kBlockSize, worst = 11 + rest + (rest >> 3) + (rest >> 1);
+    return kHeaderSize + full * (kFrameWordSize + (size_t)kSlotSize) + (rest ? kFrameWordSize + (worst < kSlotSize ? worst : (size_t)kSlotSize) : 0);
+}
+
+static bool packed_align_ok(uint32_t align) { return align >= 1 && align <= 4096 && (align & (align - 1)) == 0; }
+
+extern "C" int tsqa_plan_packed(const uint64_t* sizes, uint32_t n_items, uint32_t align, uint64_t* offsets)
+{
+    if (!sizes || !offsets || n_items == 0 || !packed_align_ok(align)) return TSQA_ERR_ARG;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        offsets[i] = at;
+        at += sizes[i];
+        if (i + 1 < n_items) at = (at + mask) & ~mask;
+    }
+    offsets[n_items] = at;
+    return TSQA_OK;
+}
+
+// Both packed compress forms: the argument checks, then the launches.  Nothing is reserved, enqueued or written before the checks
+// pass.  d_offsets, d_sizes: the caller's device tables, or NULL for the context's own (the synchronous form), reserved after the checks.
+static int compress_batch_packed_enqueue(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                         uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
+                                         int32_t* d_status, hipStream_t s)
+{
+    if (!d_in || !d_out || !d_status || !items) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    if (!batch_encoder_ok(c, "compress_batch_packed")) return TSQA_ERR_ARG;
+    if (!packed_align_ok(align)) { c->set_error("compress_batch_packed: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
+    if (out_size < kHeaderSize) { c->set_error("compress_batch_packed: out_size holds less than a header"); return TSQA_ERR_ARG; }
+    if (n_items == 0) { c->set_error("compress_batch_packed: no items"); return TSQA_ERR_ARG; }
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanPacked)) { c->set_error("compress_batch_packed: %s", why); return TSQA_ERR_ARG; }
+    if (!d_offsets) {
+        if (int rc = c->reserve_batch(n_items)) return rc;
+        d_offsets = c->batch_offsets; d_sizes = c->batch_sizes;
+    }
+    return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, out_size, align, d_offsets, d_sizes, d_status, s);
+}
+
+extern "C" int tsqa_compress_batch_packed_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                                uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets,
+                                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, d_offsets, d_sizes, d_status, s);
+}
+
+extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                          uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes,
+                                          void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!offsets || !sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    int rc = compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, nullptr, nullptr, c->d_status, s);
+    if (rc) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "compress_batch_packed");
+}
+
+// (variant < 0: the context's decode variant; the synchronous form's retry after TSQA_ERR_STALL passes 4.  d_offsets != NULL: a
+//  packed batch, whose containers' places batch_place_kernel reads from d_offsets and d_packed_sizes; items' in_at, in_len unused)
 static int decompress_batch_async_impl(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
                                        uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, hipStream_t s,
-                                       int variant)
+                                       int variant, const uint64_t* d_offsets = nullptr, const uint64_t* d_packed_sizes = nullptr)
 {
     if (!d_in || !d_out || !d_sizes || !d_status || !n_blocks) { c->set_error("decompress_batch: null pointer"); return TSQA_ERR_ARG; }
     std::vector<uint64_t> first((size_t)n_items + 1);
     const char* why;
-    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, kPlanDecompress)) { c->set_error("decompress_batch: %s", why); return TSQA_ERR_ARG; }
+    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, d_offsets ? kPlanPlaced : kPlanDecompress)) {
+        c->set_error("decompress_batch: %s", why);
+        return TSQA_ERR_ARG;
+    }
     (void)hipSetDevice(c->device);
     const uint32_t total_blocks = (uint32_t)first[n_items];
     int k = 0;
     if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
-    if (int rc = c->reserve(total_blocks, false, false)) return rc;
+    if (int rc = c->reserve(total_blocks, false, false, true)) return rc;
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
     BatchItem* const hi = static_cast<BatchItem*>(c->batch_up.host[k]);
     for (uint32_t i = 0; i < n_items; ++i)
         hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
+    if (d_offsets)
+        hipLaunchKernelGGL(batch_place_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<BatchItem*>(c->batch_up.dev[k]), n_items,
+                           d_offsets, d_packed_sizes, (uint64_t)in_size);
     hipLaunchKernelGGL(batch_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in),
                        static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->frames, d_sizes, d_status);
     // one decode over every frame of the batch (launch_decode_kernels picks the decoder by the block count, as for one container)
@@ -1141,6 +1256,18 @@ extern "C" int tsqa_decompress_batch_async(tsqa_ctx* c, const void* d_in, size_t
     if (!c) return TSQA_ERR_ARG;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     return decompress_batch_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, d_sizes, d_status, s, -1);
+}
+
+extern "C" int tsqa_decompress_batch_packed_async(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets,
+                                                  const uint64_t* d_sizes, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                                  uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_out_sizes, int32_t* d_status,
+                                                  void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_offsets || !d_sizes) { c->set_error("decompress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return decompress_batch_async_impl(c, d_arena, arena_size, items, n_blocks, n_items, d_out, out_size, d_out_sizes, d_status, s, -1, d_offsets,
+                                       d_sizes);
 }
 
 // The synchronous form's decode of a (sub-)batch: the status lands in *st, the items' sizes in sizes[]; after TSQA_ERR_STALL once
