@@ -5,11 +5,14 @@ test_encoder_catalogue_cpu.py and tests/golden/encoder_catalogue.json establish.
 
 No case is dropped: each entry point counts the cases it ran and the last test compares the counts with the catalogue's size."""
 import os
+import types
 
 import numpy as np
 import pytest
 
 import encgen
+import packedgen
+from test_gpu_packed import call_packed, round_trip
 from test_gpu_parity import codec, to_bytes, to_dev, tsq  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -85,6 +88,51 @@ def test_all_cases_of_a_level_as_one_batch(tsq, codec, wanted, variant):
         codec.set_variant(0, 0)
 
 
+@pytest.fixture(scope="module")
+def packed_input(oracle, wanted):
+    """packedgen.catalogue_arena on the device, and per level the oracle's container of every item of it"""
+    arena, items = packedgen.catalogue_arena(CASES)
+    datas = [np.frombuffer(packedgen.item_bytes(it), dtype=np.uint8) for it in items]
+    batch = types.SimpleNamespace(d_in=to_dev(arena), items=[(at, ln, 0, 0) for _, at, ln, _ in items], datas=datas)
+    want = {ext: [oracle.compress(d, ext, threads=2) if it[3] else wanted[it[0].name, ext] for it, d in zip(items, datas)] for ext in (0, 1)}
+    return batch, items, want
+
+
+@pytest.mark.parametrize("variant", [7, 6])
+def test_all_cases_of_a_level_as_one_packed_batch(tsq, codec, packed_input, variant):
+    """tsqa_compress_batch_packed over one input arena (packedgen.catalogue_arena): every case with the next case's bytes directly
+    behind its last byte, and every case that carries a halo once more with that halo behind it -- the bytes its builder chose to
+    continue its last match -- as two overlapping input ranges.  Each container must be the oracle's container of the item alone:
+    the encoder's look-ahead ends at the item's last byte.  Both staged layouts; align 1, 16 and 4096 occur."""
+    batch, items, want = packed_input
+    assert [it[0] for it in items[:len(CASES)]] == CASES
+    try:
+        for ext in (0, 1):
+            align = {(7, 0): 1, (7, 1): 16, (6, 0): 4096, (6, 1): 1}[variant, ext]
+            lengths = [len(w) for w in want[ext]]
+            plan = tsq.plan_packed(lengths, align)
+            codec.set_variant(variant, 0)
+            host, guard, offsets, sizes, rc = call_packed(codec, batch, ext, align, plan[-1] + 5000)
+            codec.set_variant(0, 0)
+            assert rc == 0, codec.last_error()
+            entry = f"compress_batch_packed (align {align}) at encoder variant {variant}"
+            assert offsets == tsq.plan_packed(sizes, align), f"{entry}: the places do not follow the layout rule for the sizes given"
+            untouched = np.ones(host.size, dtype=bool)
+            for k, (it, w) in enumerate(zip(items, want[ext])):
+                # (where a size is wrong the places behind it move: the bytes at the place the device reports, of the length it reports)
+                got = host[offsets[k]:offsets[k] + sizes[k]].tobytes()
+                same(got, w, it[0], ext, entry + (", second copy with its halo" if it[3] else ", second copy before its halo" if k >= len(CASES) else ""))
+                untouched[offsets[k]:offsets[k] + sizes[k]] = False
+            assert sizes == lengths
+            assert offsets == plan
+            assert np.array_equal(host[untouched], guard[untouched]), "bytes outside the containers were written"
+            round_trip(codec, batch, host, offsets, sizes)
+        for case in CASES:
+            count(f"packed_variant_{variant}")
+    finally:
+        codec.set_variant(0, 0)
+
+
 @pytest.mark.parametrize("variant", [0, 6])
 def test_small_cases_under_jitter(tsq, codec, wanted, variant):
     """the hand-off stress build delays every publication by a pseudo-random time that differs from block to block: the small cases,
@@ -118,5 +166,5 @@ def test_every_case_ran_through_every_entry_point():
     assert n >= 80, n                                        # tests/golden/encoder_catalogue.json pins the exact set
     print("encoder catalogue counts:", n, dict(sorted(COUNTS.items())))
     entries = ["block_api"] + [f"compress_variant_{v}" for v in (1, 7, 6, 0)] + [f"batch_variant_{v}" for v in (7, 6)] \
-        + [f"jitter_variant_{v}" for v in (0, 6)]
+        + [f"packed_variant_{v}" for v in (7, 6)] + [f"jitter_variant_{v}" for v in (0, 6)]
     assert {k: COUNTS.get(k, 0) for k in entries} == {k: n for k in entries}

@@ -7,8 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import fuzzgen
-import kat
+import packedgen as pg
 from turbosqueeze_amd.api import _batch_array
 
 pytestmark = pytest.mark.gpu
@@ -45,18 +44,12 @@ def to_dev(a):
 
 
 def sentinel(n):
-    return ((np.arange(n, dtype=np.uint64) * 37 + 11) % 251).astype(np.uint8) ^ 0xA5
+    """((i * 37 + 11) % 251) ^ 0xA5 at byte i (the pattern repeats every 251 bytes)"""
+    return np.resize(((np.arange(251, dtype=np.uint64) * 37 + 11) % 251).astype(np.uint8) ^ 0xA5, n)
 
 
 def small_item(rng, k, n, tsq):
-    kind = k % 4
-    if kind == 0:
-        return fuzzgen.structured(rng, n)
-    if kind == 1:
-        return kat.k7_textlike(n, seed=1000 + k)
-    if kind == 2:
-        return kat.xorshift32_bytes(n, seed=77 + k)
-    return tsq.synth.text(n, seed=k)
+    return pg.small_item(rng, k, n)
 
 
 def arena_of(rng, datas):
@@ -83,7 +76,7 @@ class Batch:
 
     def want(self, ext):
         if ext not in self._want:
-            self._want[ext] = [self.oracle.compress(d, ext) for d in self.datas]
+            self._want[ext] = [self.oracle.compress(d, ext, threads=8 if d.size > MiB4 else 1) for d in self.datas]
         return self._want[ext]
 
 
@@ -148,7 +141,23 @@ def test_layout_and_exactness(codec, tsq, mixed, ext, align):
     round_trip(codec, mixed, host, offsets, sizes)
 
 
-def test_launch_seams(codec, tsq, oracle):
+@pytest.fixture(scope="module")
+def cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.fixture(scope="module")
+def seam(tsq, oracle, cus):
+    """packedgen.seam_batch for the device's launch budget -> (batch, a_at, b_at, each item's first block)"""
+    datas, a_at, b_at = pg.seam_batch(cus)
+    batch = Batch(datas, 24, oracle)
+    caps = [tsq.batch_bound(d.size) for d in datas]
+    first = tsq.plan_batch([(o, d.size, sum(caps[:k]), caps[k]) for k, (o, d) in enumerate(zip(batch.offs, datas))], batch.d_in.numel(), sum(caps))
+    return batch, a_at, b_at, first
+
+
+def test_launch_seams(codec, tsq, seam, cus):
     """Launches of 2 x CUs blocks: item A's three blocks straddle the first seam (it continues into the second launch with its start
     and running frame offset carried), item B's two blocks end a launch exactly (the next item begins one and takes its start from
     what the launch before left).
@@ -156,31 +165,79 @@ def test_launch_seams(codec, tsq, oracle):
     Not reached here: an item of more than 2 x CUs blocks, whose middle launches hold that one item alone, neither begun nor completed
     in them (its input alone would be over 2 GiB).  By the kernel's code that launch reads its start from d_offsets[i0], adds an
     exclusive sum of nothing, and carries the frame offset in run_at, the two carries that items A and B check one at a time."""
-    import torch
-    budget = 2 * torch.cuda.get_device_properties(0).multi_processor_count
-    rng = np.random.default_rng(23)
-    datas, blocks = [], 0
-    while len(datas) < 2 * budget + 40:
-        if blocks == budget - 2:
-            n, a_at = 2 * MiB4 + 1, len(datas)
-        elif blocks == 2 * budget - 2:
-            n, b_at = 2 * MiB4, len(datas)
-        else:
-            n = int(rng.integers(64, 301))
-        datas.append(tsq.synth.text(n, seed=len(datas)) if n > 300 else small_item(rng, len(datas), n, tsq))
-        blocks += -(-n // MiB4)
-    batch = Batch(datas, 24, oracle)
-    caps = [tsq.batch_bound(d.size) for d in datas]
-    first = tsq.plan_batch([(o, d.size, sum(caps[:k]), caps[k]) for k, (o, d) in enumerate(zip(batch.offs, datas))], batch.d_in.numel(), sum(caps))
+    budget = 2 * cus
+    batch, a_at, b_at, first = seam
     assert first[a_at] < budget < first[a_at + 1] == first[a_at] + 3, "item A does not straddle the first launch seam"
     assert first[b_at + 1] == 2 * budget and first[b_at + 1] - first[b_at] == 2, "item B does not end the second launch"
-    assert first[-1] > 2 * budget and b_at + 1 < len(datas)
+    assert first[-1] > 2 * budget and b_at + 1 < len(batch.datas)
     want = batch.want(1)
     used = tsq.plan_packed([len(w) for w in want], 16)[-1]
     host, guard, offsets, sizes, rc = call_packed(codec, batch, 1, 16, used + 999)
     assert rc == 0, codec.last_error()
     check_layout(tsq, host, guard, want, 16, offsets, sizes)
     round_trip(codec, batch, host, offsets, sizes)
+
+
+def check_offsets(tsq, want, align, offsets, sizes):
+    """the first item whose place differs from tsqa_plan_packed of the oracle's lengths, with the difference in hex: a lost or doubled
+    high half of the scan shows as a multiple of 1 << 24"""
+    plan = tsq.plan_packed([len(w) for w in want], align)
+    for i, (got, exp) in enumerate(zip(offsets, plan)):
+        assert got == exp, (f"offsets[{i}] is {got:#x}, the plan says {exp:#x}: off by {'-' if got < exp else '+'}{abs(got - exp):#x} "
+                            f"({abs(got - exp) / (1 << 24):g} x 2^24)")
+    for i, (got, w) in enumerate(zip(sizes, want)):
+        assert got == len(w), f"sizes[{i}] is {got}, the oracle's container has {len(w)} bytes"
+
+
+def test_scan_carries_above_2_to_24(codec, tsq, oracle, cus):
+    """Four containers of more than 2^24 bytes among tiny ones (packedgen.carry_batch): the place-making scan's high half, the
+    (hi << 24) + lo recombination, the carry from one 256-item iteration to the next and the carry through d_offsets[i0] from one
+    launch to the next all have something other than zero to carry.
+
+    Not reached here, as in test_launch_seams: an item of more than 2 x CUs blocks (over 2 GiB of input), and an arena past 4 GiB.
+    By the code every offset is a 64-bit value from the scan on; no test goes there."""
+    cb = pg.carry_batch(cus)
+    batch = Batch(list(cb.datas), 36, oracle)
+    pg.carry_reach(cb, cus, {ext: [len(w) for w in batch.want(ext)] for ext in (0, 1)})        # (fails, never skips)
+    for ext in (0, 1):
+        want = batch.want(ext)
+        for align in (16, 4096):
+            used = tsq.plan_packed([len(w) for w in want], align)[-1]
+            host, guard, offsets, sizes, rc = call_packed(codec, batch, ext, align, used + 4096)
+            assert rc == 0, codec.last_error()
+            check_offsets(tsq, want, align, offsets, sizes)
+            check_layout(tsq, host, guard, want, align, offsets, sizes)
+            round_trip(codec, batch, host, offsets, sizes)
+
+
+def test_last_launch_of_256_257_and_1_items(codec, tsq, oracle, cus):
+    """the place-making loop walks a launch's items 256 at a time: a last launch of exactly one full iteration, of one valid lane in
+    a second iteration, and of one item"""
+    batches = pg.loop_edge_batches(cus)
+    assert [pg.last_launch_items(datas, cus) for datas in batches] == [256, 257, 1]
+    for k, datas in enumerate(batches):
+        batch = Batch(list(datas), 37 + k, oracle)
+        want = batch.want(1)
+        for align in (1, 256):
+            used = tsq.plan_packed([len(w) for w in want], align)[-1]
+            host, guard, offsets, sizes, rc = call_packed(codec, batch, 1, align, used + 300)
+            assert rc == 0, codec.last_error()
+            check_offsets(tsq, want, align, offsets, sizes)
+            check_layout(tsq, host, guard, want, align, offsets, sizes)
+            round_trip(codec, batch, host, offsets, sizes)
+
+
+@pytest.mark.parametrize("align", [2, 16, 4096])
+def test_alignment_residues(codec, tsq, oracle, align):
+    """containers whose size is an exact multiple of align (no padding behind them), 1 past one (align - 1 bytes) and 1 short (1)"""
+    batch = Batch(list(pg.alignment_batch(align)), 40 + align, oracle)
+    want = batch.want(1)
+    sizes = [len(w) for w in want]
+    assert pg.residues_present(sizes, align) == set(pg.RESIDUES)
+    host, guard, offsets, sizes, rc = call_packed(codec, batch, 1, align, tsq.plan_packed(sizes, align)[-1] + 2 * align)
+    assert rc == 0, codec.last_error()
+    check_offsets(tsq, want, align, offsets, sizes)
+    check_layout(tsq, host, guard, want, align, offsets, sizes)
 
 
 def test_overflow_keeps_tables_and_fitting_items(codec, tsq, mixed):
@@ -197,6 +254,46 @@ def test_overflow_keeps_tables_and_fitting_items(codec, tsq, mixed):
     host, guard, offsets, sizes, rc = call_packed(codec, mixed, ext, align, roomy[-1], buf_size=roomy[-1] + 4096)
     assert rc == 0, codec.last_error()
     check_layout(tsq, host, guard, want, align, offsets, sizes)
+
+
+def first_difference(host, expected):
+    bad = np.flatnonzero(host != expected)
+    return f"{bad.size} bytes differ, the first at {int(bad[0])}: {int(host[bad[0]])} for {int(expected[bad[0]])}" if bad.size else "equal"
+
+
+@pytest.mark.parametrize("placing", ["inside_a_launch", "across_a_launch_seam"])
+def test_overflow_cut_at_every_seam(codec, tsq, oracle, seam, cus, placing):
+    """out_size cut at every place where batch_pack_scan_packed_kernel decides (packedgen.cut_points), around a three-block item of
+    text and around a two-block item: inside one launch, and with the three-block item across the first launch seam, where its
+    later frames are placed from run_at[i] and d_offsets[i0].  Whatever is cut: TSQA_ERR_OVERFLOW, both tables complete, and the
+    buffer is the sentinel overlaid with exactly the headers and frames that end at or before out_size (packedgen.fitting_image) --
+    over the whole buffer, so nothing at or past out_size and no padding byte may change."""
+    if placing == "inside_a_launch":
+        datas, a_at, b_at = pg.inside_batch()
+        batch = Batch(datas, 38, oracle)
+        assert len(pg.launches([d.size for d in datas], cus)) == 1
+    else:
+        batch, a_at, b_at, first = seam
+        assert first[a_at] < 2 * cus < first[a_at + 1] == first[a_at] + 3, "item A does not straddle the first launch seam"
+    ext = 1
+    want = batch.want(ext)
+    lengths = [len(w) for w in want]
+    for k in (a_at, b_at):
+        align = pg.align_with_padding(lengths, k)
+        roomy = tsq.plan_packed(lengths, align)
+        cuts = pg.cut_points(want, roomy, lengths, k)
+        assert len(set(cuts.values())) == 7
+        for name, cut in cuts.items():
+            host, guard, offsets, sizes, rc = call_packed(codec, batch, ext, align, cut, buf_size=roomy[-1] + 4096)
+            assert rc == ERR_OVERFLOW, f"{name} (out_size {cut}, item {k}): rc {rc}"
+            assert offsets == roomy and sizes == lengths, f"{name} (out_size {cut}, item {k}): the tables are not the roomy plan's"
+            expected = guard.copy()
+            for lo, piece in pg.fitting_image(want, roomy, cut):
+                expected[lo:lo + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
+            assert np.array_equal(host, expected), f"{name} (out_size {cut}, item {k} at {roomy[k]}): {first_difference(host, expected)}"
+        host, guard, offsets, sizes, rc = call_packed(codec, batch, ext, align, roomy[-1], buf_size=roomy[-1] + 4096)
+        assert rc == 0, codec.last_error()
+        check_layout(tsq, host, guard, want, align, offsets, sizes)
 
 
 def fenced_outputs(rng, lengths):
