@@ -322,6 +322,32 @@ def test_two_async_batches_back_to_back(codec, oracle, tsq):
             assert host[outs[k]:outs[k] + int(sizes[k])].tobytes() == oracle.compress(d, 0), k
 
 
+def test_three_async_batches_in_flight(codec, oracle, tsq):
+    """Three batches on one stream with no synchronise between them: the descriptors go through a ring of two slots, so the third
+    batch takes the slot of the first, once that one has finished.  Three items of 1000 bytes each."""
+    import torch
+    rng = np.random.default_rng(9)
+    side = torch.cuda.Stream()
+    runs = []
+    with torch.cuda.stream(side):
+        for b in range(3):
+            datas = [tsq.synth.text(1000, seed=900 + 3 * b + k) for k in range(3)]
+            arena, offs = arena_of(rng, datas)
+            d_in = to_dev(arena)
+            caps = [tsq.batch_bound(d.size) for d in datas]
+            outs, out_size = fenced(rng, caps)
+            out = torch.empty(out_size, dtype=torch.uint8, device="cuda")
+            d_sizes = torch.zeros(3, dtype=torch.int64, device="cuda")
+            codec.compress_batch_async(d_in, [(o, d.size, a, cap) for o, d, a, cap in zip(offs, datas, outs, caps)], 0, out, d_sizes)
+            runs.append((datas, outs, out, d_sizes, d_in))
+    side.synchronize()
+    assert codec.status() == 0
+    for datas, outs, out, d_sizes, _ in runs:
+        host, sizes = out.cpu().numpy(), d_sizes.cpu().numpy()
+        for k, d in enumerate(datas):
+            assert host[outs[k]:outs[k] + int(sizes[k])].tobytes() == oracle.compress(d, 0), k
+
+
 def test_refused_arguments_write_nothing(codec, tsq):
     import torch
     src = to_dev(tsq.synth.text(10_000, seed=1))

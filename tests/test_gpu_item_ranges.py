@@ -298,6 +298,28 @@ def test_async_calls_back_to_back(mixed, codec):
         assert np.array_equal(views[-1].cpu().numpy(), plains[i][o:o + ln])
 
 
+def test_three_async_calls_in_flight(tsq, codec, oracle):
+    """Three calls on one stream with no synchronise between them: the staged items and groups go through a ring of two slots, so
+    the third call takes the slot of the first, once that one has finished.  One container of two blocks, three ranges of 1..100
+    bytes per call, one of them across the block edge."""
+    import torch
+    n = MiB4 + 1000
+    blob = oracle.compress(tsq.synth.text(n, seed=62), 1, threads=2)
+    plain = np.frombuffer(oracle.decompress(blob, threads=2), dtype=np.uint8)
+    idx = codec.index_batch([to_dev(np.frombuffer(blob, dtype=np.uint8))])
+    sets = [[(0, 1), (MiB4 - 40, 100), (n - 7, 7)], [(123457, 100), (MiB4 - 1, 2), (MiB4, 33)], [(5, 64), (MiB4 + 900, 100), (MiB4 - 99, 100)]]
+    results = []
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        for rs in sets:
+            results.append((rs, idx.read_many_async([(0, o, ln) for o, ln in rs])[0]))
+    side.synchronize()
+    assert codec.status() == 0
+    for rs, packed in results:
+        assert np.array_equal(packed.cpu().numpy(), np.concatenate([plain[o:o + ln] for o, ln in rs])), rs
+    idx.close()
+
+
 def test_an_index_of_one_container_takes_item_reads(tsq, codec, oracle):
     """tsqa_index_create's index is a batch of one item"""
     n = 2 * MiB4 + 4321

@@ -11,16 +11,41 @@
 
 namespace tsq { struct FrameInfo; }
 
-// Descriptors a call plans on the host for its kernels (range-read items, batch descriptors): two slots, used in turn, each a pinned
-// host buffer and its copy on the device.  A slot is reused once the call that used it has finished (done[k], recorded behind its
-// last kernel): two calls can be in flight.
-struct tsqa_uploads {
-    void* host[2] = {nullptr, nullptr};
-    void* dev[2] = {nullptr, nullptr};
-    size_t cap[2] = {0, 0};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    bool pending[2] = {false, false};
-    int next = 0;
+struct tsqa_ctx;
+
+// Descriptors a call plans on the host for its kernels (range-read items, batch descriptors): a ring of two slots, used in turn, each a
+// pinned host buffer and its copy on the device, grown by doubling.  A slot is reused once the call that used it has finished: two
+// calls can be in flight, the third waits for the first.
+class tsqa_uploads {
+    void* host_[2] = {nullptr, nullptr};
+    void* dev_[2] = {nullptr, nullptr};
+    size_t cap_[2] = {0, 0};
+    hipEvent_t done_[2] = {nullptr, nullptr};
+    bool pending_[2] = {false, false};
+    int next_ = 0;
+
+public:
+    // An acquired slot: fill host<T>(at), send(), launch what reads dev<T>(at), commit().  A call that ends before anything is
+    // enqueued simply drops it: the slot is not pending.  (`at`: the byte offset of a second table in the same buffer.)
+    struct Slot {
+        tsqa_uploads* u = nullptr;
+        int k = 0;
+        template <class T> T* host(size_t at = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(u->host_[k]) + at); }
+        template <class T> T* dev(size_t at = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(u->dev_[k]) + at); }
+        size_t cap() const { return u->cap_[k]; }
+        hipError_t send(size_t bytes, hipStream_t s) const { return hipMemcpyAsync(u->dev_[k], u->host_[k], bytes, hipMemcpyHostToDevice, s); }
+        // Behind the LAST kernel of the call that reads the slot, however that launch went: neither copy of the descriptors is touched
+        // again before the work that uses them has finished.
+        hipError_t commit(hipStream_t s) const
+        {
+            const hipError_t e = hipEventRecord(u->done_[k], s);
+            if (e == hipSuccess) u->pending_[k] = true;
+            return e;
+        }
+    };
+    // the next slot, once the call that used it last has finished, with room for `bytes`
+    int acquire(tsqa_ctx* c, size_t bytes, Slot* slot);
+    void destroy();
 };
 
 struct tsqa_ctx {
@@ -69,15 +94,11 @@ struct tsqa_ctx {
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
     uint32_t prof_used[kProfKinds] = {0, 0, 0, 0};
-    bool prof_begin(int kind, hipStream_t s);
-    void prof_end(int kind, hipStream_t s);
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     int reserve(size_t n_blocks, bool want_tables, bool want_slots = true, bool all_streams = false);
     int reserve_duo(size_t n_blocks);
     int reserve_host_frames(size_t n);
-    // the next slot of `u`, once the call that used it has finished, with room for `bytes`
-    int reserve_upload(tsqa_uploads& u, size_t bytes, int* slot);
     int reserve_batch(size_t n_items);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);

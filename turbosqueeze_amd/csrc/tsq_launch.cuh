@@ -7,6 +7,7 @@
 #pragma once
 
 #include <atomic>
+#include <initializer_list>
 
 #include "tsq_common.cuh"
 #include "tsq_emit.cuh"
@@ -21,125 +22,94 @@
 
 namespace tsq {
 
-// the dynamic-LDS limit is a per-device attribute of a kernel function: raised once per device the process uses
-template <size_t N>
-inline int raise_lds_limit(tsqa_ctx* c, std::atomic<uint64_t>& done, const void* const (&fns)[N], const uint32_t (&bytes)[N])
+// The dynamic-LDS limit is a per-device attribute of a kernel function: raised once per device the process uses (`done`: the devices
+// that have it).  TSQ_RAISE_LDS(c, lds_need(kernel, bytes), ...) is that for the kernels of one launcher, which it leaves on a failure.
+struct LdsNeed { const void* fn; uint32_t bytes; };
+template <class K> inline LdsNeed lds_need(K kernel, uint32_t bytes) { return {reinterpret_cast<const void*>(kernel), bytes}; }
+inline int raise_lds_limit(tsqa_ctx* c, std::atomic<uint64_t>& done, std::initializer_list<LdsNeed> needs)
 {
     const uint64_t dev_bit = 1ull << (c->device & 63);
     if (done.load() & dev_bit) return 0;
-    for (size_t k = 0; k < N; ++k)
-        if (hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes[k]) != hipSuccess) {
-            c->set_error("cannot reserve %u B of LDS", bytes[k]);
+    for (const LdsNeed& k : needs)
+        if (hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes) != hipSuccess) {
+            c->set_error("cannot reserve %u B of LDS", k.bytes);
             return TSQA_ERR_HIP;
         }
     done.fetch_or(dev_bit);
     return 0;
 }
+#define TSQ_RAISE_LDS(c, ...)                                                                                                       \
+    do {                                                                                                                            \
+        static std::atomic<uint64_t> raised_{0};                                                                                    \
+        if (int rc_ = raise_lds_limit((c), raised_, {__VA_ARGS__})) return rc_;                                                     \
+    } while (0)
 
-#define TSQ_LAUNCH_ENC(KERNEL, THREADS, LDS)                                                                                        \
-    hipLaunchKernelGGL((KERNEL), dim3(nb), dim3(THREADS), (LDS), s, in, (uint64_t)n, (uint64_t)readable, (uint64_t)stride, slots, sizes, c->tables, status)
+// One generation of the staged encoder in one role: its four builds in the order <ext, standard>, <plain, standard>, <ext, lean>,
+// <plain, lean>, and the workgroup size and LDS of its two layouts ([0] standard, [1] lean).
+template <class K> struct StagedFamily { K kernel[4]; uint32_t threads[2], lds[2]; std::atomic<uint64_t> raised{0}; };
+#define TSQ_STAGED_FAMILY(KERNEL, CFG)                                                                                              \
+    {{KERNEL<true, true>, KERNEL<false, true>, KERNEL<true, false>, KERNEL<false, false>}, {CFG<true>::THREADS, CFG<false>::THREADS_LEAN}, {CFG<true>::total, CFG<false>::total}}
+
+// The staged pipeline (tsq_enc_stage.cuh) over nb blocks, one workgroup each.  More blocks than CUs: the lean layout (no input window
+// in LDS, candidate bytes from L2) lets several blocks share a CU; each is a little slower, together they are faster.  Variant 6
+// takes the lean layout at any count, variants 0 and 5 (the frozen generation) by the count, every other one the standard layout.
+template <class K, class... Args>
+inline int launch_staged(tsqa_ctx* c, StagedFamily<K>& f, uint32_t ext, uint32_t nb, hipStream_t s, Args... args)
+{
+    if (int rc = raise_lds_limit(c, f.raised, {lds_need(f.kernel[0], f.lds[0]), lds_need(f.kernel[1], f.lds[0]), lds_need(f.kernel[2], f.lds[1]), lds_need(f.kernel[3], f.lds[1])})) return rc;
+    const int v = c->enc_variant;
+    const int lean = v == 6 || ((v == 0 || v == 5) && nb > (uint32_t)c->n_cus);
+    hipLaunchKernelGGL(f.kernel[2 * lean + (ext ? 0 : 1)], dim3(nb), dim3(f.threads[lean]), f.lds[lean], s, args...);
+    return 0;
+}
 
 // Encode nb = ceil(n / 4 MiB) blocks; block b is read at in + b * stride, streams land in slots[b], sizes in sizes[b].
 inline int launch_encode_kernels(tsqa_ctx* c, const uint8_t* in, size_t n, size_t readable, size_t stride, uint32_t ext,
                                  uint8_t* slots, uint32_t* sizes, int32_t* status, hipStream_t s)
 {
     const uint32_t nb = (uint32_t)((n + kBlockSize - 1) / kBlockSize);
-    static std::atomic<uint64_t> attr_devices{0};
-    {
-        const void* const fns[4] = {reinterpret_cast<const void*>(enc_stage_kernel<true, true>), reinterpret_cast<const void*>(enc_stage_kernel<false, true>),
-                                    reinterpret_cast<const void*>(enc_stage_kernel<true, false>), reinterpret_cast<const void*>(enc_stage_kernel<false, false>)};
-        const uint32_t bytes[4] = {StageCfgT<true>::total, StageCfgT<true>::total, StageCfgT<false>::total, StageCfgT<false>::total};
-        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
-    }
+    static StagedFamily<decltype(&enc_stage_kernel<true, true>)> staged = TSQ_STAGED_FAMILY(enc_stage_kernel, StageCfgT);
     const int v = c->enc_variant;
     if (v == 1) {                       // one lane walks the block: the correctness baseline
-        if (ext) TSQ_LAUNCH_ENC(enc_serial_kernel<true>, 64, 0);
-        else     TSQ_LAUNCH_ENC(enc_serial_kernel<false>, 64, 0);
+        hipLaunchKernelGGL(ext ? enc_serial_kernel<true> : enc_serial_kernel<false>, dim3(nb), dim3(64), 0, s, in, (uint64_t)n, (uint64_t)readable,
+                           (uint64_t)stride, slots, sizes, c->tables, status);
         return 0;
     }
 #ifdef TSQ_AB_VARIANTS
     if (v == 5) {                       // round 5's production encoder, frozen (ab/tsq_enc_stage_r05.cuh)
-        static std::atomic<uint64_t> ab_devices{0};
-        const void* const fns[4] = {reinterpret_cast<const void*>(r05::enc_stage_kernel<true, true>), reinterpret_cast<const void*>(r05::enc_stage_kernel<false, true>),
-                                    reinterpret_cast<const void*>(r05::enc_stage_kernel<true, false>), reinterpret_cast<const void*>(r05::enc_stage_kernel<false, false>)};
-        const uint32_t bytes[4] = {r05::StageCfgT<true>::total, r05::StageCfgT<true>::total, r05::StageCfgT<false>::total, r05::StageCfgT<false>::total};
-        if (int rc = raise_lds_limit(c, ab_devices, fns, bytes)) return rc;
-        if (nb > (uint32_t)c->n_cus) {
-            if (ext) TSQ_LAUNCH_ENC((r05::enc_stage_kernel<true, false>), r05::StageCfgT<false>::THREADS_LEAN, r05::StageCfgT<false>::total);
-            else     TSQ_LAUNCH_ENC((r05::enc_stage_kernel<false, false>), r05::StageCfgT<false>::THREADS_LEAN, r05::StageCfgT<false>::total);
-        } else {
-            if (ext) TSQ_LAUNCH_ENC((r05::enc_stage_kernel<true, true>), r05::StageCfgT<true>::THREADS, r05::StageCfgT<true>::total);
-            else     TSQ_LAUNCH_ENC((r05::enc_stage_kernel<false, true>), r05::StageCfgT<true>::THREADS, r05::StageCfgT<true>::total);
-        }
-        return 0;
+        static StagedFamily<decltype(&r05::enc_stage_kernel<true, true>)> frozen = TSQ_STAGED_FAMILY(r05::enc_stage_kernel, r05::StageCfgT);
+        return launch_staged(c, frozen, ext, nb, s, in, (uint64_t)n, (uint64_t)readable, (uint64_t)stride, slots, sizes, c->tables, status);
     }
 #else
     if (v == 5) { c->set_error("kernel variant %d lives in the A/B library only (make ab)", v); return TSQA_ERR_ARG; }
 #endif
     if (v >= 2 && v <= 4) { c->set_error("kernel variant %d is not built", v); return TSQA_ERR_ARG; }
-    // staged pipeline (tsq_enc_stage.cuh).  More blocks than CUs: the lean layout (no input window in LDS, candidate
-    // bytes from L2) lets several blocks share a CU; each is a little slower, together they are faster.
-    const bool lean = v == 6 || (v == 0 && nb > (uint32_t)c->n_cus);
-    if (lean) {
-        if (ext) TSQ_LAUNCH_ENC((enc_stage_kernel<true, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
-        else     TSQ_LAUNCH_ENC((enc_stage_kernel<false, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
-    } else {
-        if (ext) TSQ_LAUNCH_ENC((enc_stage_kernel<true, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
-        else     TSQ_LAUNCH_ENC((enc_stage_kernel<false, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
-    }
-    return 0;
+    return launch_staged(c, staged, ext, nb, s, in, (uint64_t)n, (uint64_t)readable, (uint64_t)stride, slots, sizes, c->tables, status);
 }
-#undef TSQ_LAUNCH_ENC
-
-#define TSQ_LAUNCH_BATCH(KERNEL, THREADS, LDS)                                                                                      \
-    hipLaunchKernelGGL((KERNEL), dim3(nb), dim3(THREADS), (LDS), s, in, blocks, slots, sizes, c->tables, status)
 
 // Encode nb blocks of a batch (tsqa_compress_batch_async) from their descriptors: the staged encoder in the layout
 // launch_encode_kernels takes for nb blocks.  Encoder variants 0, 6 and 7 only.
 inline int launch_batch_encode_kernels(tsqa_ctx* c, const uint8_t* in, const EncBatchBlock* blocks, uint32_t nb, uint32_t ext,
                                        uint8_t* slots, uint32_t* sizes, int32_t* status, hipStream_t s)
 {
-    static std::atomic<uint64_t> attr_devices{0};
-    {
-        const void* const fns[4] = {reinterpret_cast<const void*>(enc_batch_kernel<true, true>), reinterpret_cast<const void*>(enc_batch_kernel<false, true>),
-                                    reinterpret_cast<const void*>(enc_batch_kernel<true, false>), reinterpret_cast<const void*>(enc_batch_kernel<false, false>)};
-        const uint32_t bytes[4] = {StageCfgT<true>::total, StageCfgT<true>::total, StageCfgT<false>::total, StageCfgT<false>::total};
-        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
-    }
+    static StagedFamily<decltype(&enc_batch_kernel<true, true>)> staged = TSQ_STAGED_FAMILY(enc_batch_kernel, StageCfgT);
     const int v = c->enc_variant;
     if (v != 0 && v != 6 && v != 7) { c->set_error("kernel variant %d does not encode batches (0, 6 and 7 do)", v); return TSQA_ERR_ARG; }
-    const bool lean = v == 6 || (v == 0 && nb > (uint32_t)c->n_cus);
-    if (lean) {
-        if (ext) TSQ_LAUNCH_BATCH((enc_batch_kernel<true, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
-        else     TSQ_LAUNCH_BATCH((enc_batch_kernel<false, false>), StageCfgT<false>::THREADS_LEAN, StageCfgT<false>::total);
-    } else {
-        if (ext) TSQ_LAUNCH_BATCH((enc_batch_kernel<true, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
-        else     TSQ_LAUNCH_BATCH((enc_batch_kernel<false, true>), StageCfgT<true>::THREADS, StageCfgT<true>::total);
-    }
-    return 0;
+    return launch_staged(c, staged, ext, nb, s, in, blocks, slots, sizes, c->tables, status);
 }
-#undef TSQ_LAUNCH_BATCH
 
 inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_blocks, uint8_t* out,
                                  int32_t* status, hipStream_t s, int variant = -1)
 {
-    static std::atomic<uint64_t> attr_devices{0};
-    {
-        const void* const fns[1] = {reinterpret_cast<const void*>(dec_sym_kernel)};
-        const uint32_t bytes[1] = {SymLds::total};
-        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
-    }
+    TSQ_RAISE_LDS(c, lds_need(dec_sym_kernel, SymLds::total));
     const int v = variant >= 0 ? variant : c->dec_variant;
     if (v == 1) { hipLaunchKernelGGL(dec_serial_kernel, dim3(n_blocks), dim3(64), 0, s, container, frames, out, status); return 0; }
     if (v == 8 || v == 9) { c->set_error("kernel variant %d is not built", v); return TSQA_ERR_ARG; }
     // Few blocks (every GPU of a multi-GPU job on enwik9): several workgroups per block on different CUs of one XCD -- the block's
     // copy chain on one, its parse on one (at most half as many blocks as CUs) or two (at most a third) (tsq_dec_duo.cuh).
     auto launch_multi = [&](const FrameInfo* fr, uint32_t nblk, bool three) -> int {
-        static std::atomic<uint64_t> duo_devices{0};
-        const void* const fns[2] = {reinterpret_cast<const void*>(dec_duo_kernel<1>), reinterpret_cast<const void*>(dec_duo_kernel<2>)};
         const uint32_t lds_bytes = DuoCopyLds::total > SymLds::total ? DuoCopyLds::total : SymLds::total;
-        const uint32_t bytes[2] = {lds_bytes, lds_bytes};
-        if (int rc = raise_lds_limit(c, duo_devices, fns, bytes)) return rc;
+        TSQ_RAISE_LDS(c, lds_need(dec_duo_kernel<1>, lds_bytes), lds_need(dec_duo_kernel<2>, lds_bytes));
         if (int rc = c->reserve_duo(nblk)) return rc;
         if (hipMemsetAsync(c->duo_flags, 0, (size_t)nblk * DuoCfg::FLAG_STRIDE * sizeof(uint32_t), s) != hipSuccess) { c->set_error("hipMemsetAsync failed"); return TSQA_ERR_HIP; }
         const uint32_t groups = (nblk + 7u) / 8u;
@@ -167,31 +137,13 @@ inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const Fr
     return 0;
 }
 
-// Range reads: one workgroup per item (dec_range_kernel), at any item count.  The items are in device memory.
-inline int launch_range_kernel(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
-                               uint32_t n_items, uint8_t* out, int32_t* status, hipStream_t s)
+// Range reads (dec_range_kernel, one workgroup per item) and record reads (dec_group_kernel, one per group), at any count: `args`
+// are the kernel's own.  Items and groups are in device memory.
+template <auto Kernel, class... Args>
+inline int launch_read_kernel(tsqa_ctx* c, uint32_t n_groups, hipStream_t s, Args... args)
 {
-    static std::atomic<uint64_t> attr_devices{0};
-    {
-        const void* const fns[1] = {reinterpret_cast<const void*>(dec_range_kernel)};
-        const uint32_t bytes[1] = {SymLds::total};
-        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
-    }
-    hipLaunchKernelGGL(dec_range_kernel, dim3(n_items), dim3(SymCfg::T), SymLds::total, s, container, frames, n_frames, items, out, status);
-    return 0;
-}
-
-// Record reads: one workgroup per group (dec_group_kernel), at any group count.  Items and groups are in device memory.
-inline int launch_group_kernel(tsqa_ctx* c, const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
-                               uint32_t n_items, const BlockGroup* groups, uint32_t n_groups, uint8_t* out, int32_t* status, hipStream_t s)
-{
-    static std::atomic<uint64_t> attr_devices{0};
-    {
-        const void* const fns[1] = {reinterpret_cast<const void*>(dec_group_kernel)};
-        const uint32_t bytes[1] = {SymLds::total};
-        if (int rc = raise_lds_limit(c, attr_devices, fns, bytes)) return rc;
-    }
-    hipLaunchKernelGGL(dec_group_kernel, dim3(n_groups), dim3(SymCfg::T), SymLds::total, s, container, frames, n_frames, items, n_items, groups, out, status);
+    TSQ_RAISE_LDS(c, lds_need(Kernel, SymLds::total));
+    hipLaunchKernelGGL(Kernel, dim3(n_groups), dim3(SymCfg::T), SymLds::total, s, args...);
     return 0;
 }
 

@@ -18,6 +18,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 
 using namespace tsq;
@@ -38,6 +39,8 @@ void tsqa_ctx::set_error(const char* fmt, ...)
     vsnprintf(err, sizeof(err), fmt, ap);
     va_end(ap);
 }
+
+static hipStream_t stream_of(const tsqa_ctx* c, void* hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream; }
 
 extern "C" size_t tsqa_block_count(size_t n) { return (n + kBlockSize - 1) / kBlockSize; }
 
@@ -137,12 +140,7 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     (void)hipFree(c->duo_ring); (void)hipFree(c->duo_flags);
     if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
-    for (tsqa_uploads* u : {&c->range_up, &c->batch_up})
-        for (int k = 0; k < 2; ++k) {
-            (void)hipFree(u->dev[k]);
-            if (u->host[k]) (void)hipHostFree(u->host[k]);
-            if (u->done[k]) (void)hipEventDestroy(u->done[k]);
-        }
+    c->range_up.destroy(); c->batch_up.destroy();
     (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
     delete c;
 }
@@ -219,25 +217,33 @@ int tsqa_ctx::reserve_host_frames(size_t n)
     return TSQA_OK;
 }
 
-// Planned descriptors: the next of the two slots, once the call that used it last has finished, grown on demand.
-int tsqa_ctx::reserve_upload(tsqa_uploads& u, size_t bytes, int* slot)
+int tsqa_uploads::acquire(tsqa_ctx* c, size_t bytes, Slot* slot)
 {
-    (void)hipSetDevice(device);
-    const int k = u.next;
-    u.next ^= 1;
-    if (u.pending[k]) { (void)hipEventSynchronize(u.done[k]); u.pending[k] = false; }
-    if (!u.done[k]) TSQ_HIP(this, hipEventCreateWithFlags(&u.done[k], hipEventDisableTiming));
-    if (bytes > u.cap[k]) {
-        if (u.host[k]) (void)hipHostFree(u.host[k]);
-        (void)hipFree(u.dev[k]);
-        u.host[k] = nullptr; u.dev[k] = nullptr; u.cap[k] = 0;
+    (void)hipSetDevice(c->device);
+    const int k = next_;
+    next_ ^= 1;
+    if (pending_[k]) { (void)hipEventSynchronize(done_[k]); pending_[k] = false; }
+    if (!done_[k]) TSQ_HIP(c, hipEventCreateWithFlags(&done_[k], hipEventDisableTiming));
+    if (bytes > cap_[k]) {
+        if (host_[k]) (void)hipHostFree(host_[k]);
+        (void)hipFree(dev_[k]);
+        host_[k] = nullptr; dev_[k] = nullptr; cap_[k] = 0;
         size_t want = 4096; while (want < bytes) want *= 2;
-        TSQ_HIP(this, hipHostMalloc(&u.host[k], want, hipHostMallocDefault));
-        TSQ_HIP(this, hipMalloc(&u.dev[k], want));
-        u.cap[k] = want;
+        TSQ_HIP(c, hipHostMalloc(&host_[k], want, hipHostMallocDefault));
+        TSQ_HIP(c, hipMalloc(&dev_[k], want));
+        cap_[k] = want;
     }
-    *slot = k;
+    *slot = Slot{this, k};
     return TSQA_OK;
+}
+
+void tsqa_uploads::destroy()
+{
+    for (int k = 0; k < 2; ++k) {
+        (void)hipFree(dev_[k]);
+        if (host_[k]) (void)hipHostFree(host_[k]);
+        if (done_[k]) (void)hipEventDestroy(done_[k]);
+    }
 }
 
 // Per-item scratch of the batch entry points (tsq_internal.h), grown on demand.
@@ -259,19 +265,24 @@ int tsqa_ctx::reserve_batch(size_t n_items)
 }
 
 // ---- kernel timing ----
-bool tsqa_ctx::prof_begin(int kind, hipStream_t s)
-{
-    if (!profiling || prof_used[kind] >= (uint32_t)kProfPairs) return false;
-    const size_t at = ((size_t)kind * kProfPairs + prof_used[kind]) * 2;
-    prof_used[kind]++;
-    (void)hipEventRecord(prof_pool[at], s);
-    return true;
-}
-void tsqa_ctx::prof_end(int kind, hipStream_t s)
-{
-    const size_t at = ((size_t)kind * kProfPairs + prof_used[kind] - 1) * 2 + 1;
-    (void)hipEventRecord(prof_pool[at], s);
-}
+// One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
+// closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
+struct ProfSpan {
+    tsqa_ctx* const c;
+    const int kind;
+    const hipStream_t s;
+    size_t at = 0;
+    bool timed = false;
+    ProfSpan(tsqa_ctx* c_, int kind_, hipStream_t s_) : c(c_), kind(kind_), s(s_)
+    {
+        if (!c->profiling || c->prof_used[kind] >= (uint32_t)tsqa_ctx::kProfPairs) return;
+        at = ((size_t)kind * tsqa_ctx::kProfPairs + c->prof_used[kind]++) * 2;
+        (void)hipEventRecord(c->prof_pool[at], s);
+        timed = true;
+    }
+    void end() { if (timed) (void)hipEventRecord(c->prof_pool[at + 1], s); }
+    void cancel() { if (timed) c->prof_used[kind]--; }
+};
 
 extern "C" int tsqa_profile_enable(tsqa_ctx* c, int on)
 {
@@ -334,10 +345,10 @@ int tsqa_ctx::launch_encode_to(const void* d_in, size_t n, size_t readable, size
     const uint32_t nb = (uint32_t)tsqa_block_count(n);
     int rc = reserve(nb, true, false);                   // (the streams go to the caller's slots: the context's own are not needed here)
     if (rc) return rc;
-    const bool timed = prof_begin(0, s);
+    ProfSpan span(this, 0, s);
     rc = launch_encode_kernels(this, static_cast<const uint8_t*>(d_in), n, readable, stride, ext, slots_out, sizes_out, status, s);
-    if (rc) { if (timed) prof_used[0]--; return rc; }     // (the pair's end event was never recorded: give the pair back)
-    if (timed) prof_end(0, s);
+    if (rc) { span.cancel(); return rc; }
+    span.end();
     TSQ_HIP(this, hipGetLastError());
     return TSQA_OK;
 }
@@ -363,10 +374,10 @@ int tsqa_ctx::launch_pack(size_t n, uint32_t ext, void* d_out, size_t out_cap, u
 
 int tsqa_ctx::launch_decode_frames(const void* d_streams, const FrameInfo* d_frames, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant)
 {
-    const bool timed = prof_begin(1, s);
+    ProfSpan span(this, 1, s);
     int rc = launch_decode_kernels(this, static_cast<const uint8_t*>(d_streams), d_frames, n_blocks, static_cast<uint8_t*>(d_out), status, s, variant);
-    if (rc) { if (timed) prof_used[1]--; return rc; }
-    if (timed) prof_end(1, s);
+    if (rc) { span.cancel(); return rc; }
+    span.end();
     TSQ_HIP(this, hipGetLastError());
     return TSQA_OK;
 }
@@ -390,14 +401,14 @@ extern "C" int tsqa_compress_device_async(tsqa_ctx* c, const void* d_in, size_t 
     if (!c) return TSQA_ERR_ARG;
     if (!d_in || !d_out || !d_out_size || !d_status || n == 0) { c->set_error("compress: null pointer or zero size"); return TSQA_ERR_ARG; }
     if (out_cap < 16 + 6 * tsqa_block_count(n)) { c->set_error("compress: output capacity too small"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    const bool timed = c->prof_begin(2, s);
+    ProfSpan span(c, 2, s);
     int rc = c->launch_encode(d_in, n, n, ext, d_status, s);
-    if (rc) { if (timed) c->prof_used[2]--; return rc; }
+    if (rc) { span.cancel(); return rc; }
     rc = c->launch_pack(n, ext, d_out, out_cap, d_out_size, d_status, s);
-    if (timed) c->prof_end(2, s);
+    span.end();
     return rc;
 }
 
@@ -408,17 +419,31 @@ static int status_to_rc(tsqa_ctx* c, int32_t st, const char* what)
     return st;
 }
 
+// The tail of the synchronous entry points: the context's status word comes back behind whatever the caller has queued on `s`
+// (the call itself, copies of its sizes or offsets to the host), and the stream is waited for.
+static int read_status(tsqa_ctx* c, hipStream_t s, int32_t* st)
+{
+    TSQ_HIP(c, hipMemcpyAsync(st, c->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return TSQA_OK;
+}
+static int finish_sync(tsqa_ctx* c, hipStream_t s, const char* what)
+{
+    int32_t st = 0;
+    if (int rc = read_status(c, s, &st)) return rc;
+    return status_to_rc(c, st, what);
+}
+
 extern "C" int tsqa_compress_device(tsqa_ctx* c, const void* d_in, size_t n, void* d_out, size_t out_cap,
                                     size_t* out_size, uint32_t ext, void* hip_stream)
 {
     if (!c || !out_size) return TSQA_ERR_ARG;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     int rc = tsqa_compress_device_async(c, d_in, n, d_out, out_cap, c->d_size, c->d_status, ext, s);
     if (rc) return rc;
     uint64_t sz = 0; int32_t st = 0;
     TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
+    if (int rc = read_status(c, s, &st)) return rc;
     *out_size = (size_t)sz;
     return status_to_rc(c, st, "compress");
 }
@@ -429,17 +454,17 @@ static int decompress_device_async_impl(tsqa_ctx* c, const void* d_in, size_t n,
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_in || !d_out || !d_out_size || !d_status || n < 16 || n_blocks == 0) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     int rc = c->reserve(n_blocks, false, false);
     if (rc) return rc;
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    const bool timed = c->prof_begin(3, s);
+    ProfSpan span(c, 3, s);
     hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
                        (uint64_t)out_cap, c->frames, d_out_size, d_status);
     rc = c->launch_decode(d_in, n_blocks, d_out, d_status, s, variant);
-    if (timed) c->prof_end(3, s);
+    span.end();
     return rc;
 }
 
@@ -459,7 +484,7 @@ extern "C" int tsqa_encode_blocks_async(tsqa_ctx* c, const void* d_in, uint32_t 
         c->set_error("encode_blocks: bad argument");
         return TSQA_ERR_ARG;
     }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     // the virtual total gives every block but the last 4 MiB; what may be read ends with the last block's look-ahead
@@ -475,7 +500,7 @@ extern "C" int tsqa_decode_blocks_async(tsqa_ctx* c, const void* d_streams, cons
     if (!c) return TSQA_ERR_ARG;
     if (!d_streams || !d_frames || !d_out || !d_status || n_blocks == 0) { c->set_error("decode_blocks: bad argument"); return TSQA_ERR_ARG; }
     static_assert(sizeof(tsqa_frame) == sizeof(FrameInfo), "public frame descriptor = kernel frame descriptor");
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     return c->launch_decode_frames(d_streams, reinterpret_cast<const FrameInfo*>(d_frames), n_blocks, d_out, d_status, s);
@@ -486,7 +511,7 @@ extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, v
 {
     if (!c || !out_size) return TSQA_ERR_ARG;
     if (!d_in || n < 16) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     uint8_t head[kHeaderSize];
     TSQ_HIP(c, hipMemcpyAsync(head, d_in, kHeaderSize, hipMemcpyDeviceToHost, s));
@@ -497,20 +522,14 @@ extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, v
     if (total > out_cap) { c->set_error("decompress: output capacity %zu < %llu", out_cap, (unsigned long long)total); return TSQA_ERR_ARG; }
     // (an implausible header is refused with *out_size = 0, as the frame walk would refuse it)
     if (h != kHeaderOk) { *out_size = 0; c->set_error("decompress: more blocks or bytes than a container of %zu B can hold", n); return TSQA_ERR_FORMAT; }
-    int rc = tsqa_decompress_device_async(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s);
-    if (rc) return rc;
     uint64_t sz = 0; int32_t st = 0;
-    TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
-    if (st == kErrStall) {
-        // a workgroup of a several-workgroups-per-block decode did not get onto the GPU in time (other work held the CUs): the
-        // container is not at fault -- once more with one workgroup per block, which waits for nobody
-        rc = decompress_device_async_impl(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s, 4);
-        if (rc) return rc;
+    // after TSQA_ERR_STALL -- a workgroup of a several-workgroups-per-block decode did not get onto the GPU in time (other work held
+    // the CUs): the container is not at fault -- once more with one workgroup per block, which waits for nobody
+    for (int variant : {-1, 4}) {
+        if (int rc = decompress_device_async_impl(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s, variant)) return rc;
         TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipStreamSynchronize(s));
+        if (int rc = read_status(c, s, &st)) return rc;
+        if (st != kErrStall) break;
     }
     *out_size = (size_t)sz;
     return status_to_rc(c, st, "decompress");
@@ -524,7 +543,7 @@ extern "C" int tsqa_frames_to_host_async(tsqa_ctx* c, const void* d_slots, const
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_slots || !sizes || !frame_at || !host_container) { c->set_error("frames_to_host: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     uint8_t* base = static_cast<uint8_t*>(host_container);
     for (uint32_t b = 0; b < n_blocks; ++b) {
@@ -541,7 +560,7 @@ extern "C" int tsqa_frames_from_host_async(tsqa_ctx* c, const void* host_contain
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_streams || !sizes || !frame_at || !host_container) { c->set_error("frames_from_host: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint8_t* base = static_cast<const uint8_t*>(host_container);
     for (uint32_t b = 0; b < n_blocks; ++b) {
@@ -611,7 +630,7 @@ extern "C" int tsqa_sharded_place_async(tsqa_ctx* c, const void* d_slots, const 
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_slots || !all_sizes || !host_container || !container_size || world == 0 || rank >= world || n_blocks == 0) { c->set_error("sharded_place: bad argument"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     uint8_t* base = static_cast<uint8_t*>(host_container);
     // every size and the capacity are checked before anything is written or enqueued (no partial container on an error)
@@ -644,7 +663,7 @@ extern "C" int tsqa_sharded_fetch_decode_async(tsqa_ctx* c, const void* host_con
 {
     if (!c) return TSQA_ERR_ARG;
     if (!host_container || !d_streams || !d_out || !d_status || !total || world == 0 || rank >= world) { c->set_error("sharded_fetch_decode: bad argument"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint8_t* p = static_cast<const uint8_t*>(host_container);
     c->forget_sharded();                                 // whatever happens below, an older call's descriptors are not to be decoded again
@@ -692,12 +711,16 @@ extern "C" int tsqa_sharded_decode_again_async(tsqa_ctx* c, const void* d_stream
     if (c->sharded_n_local == 0) { c->set_error("sharded_decode_again: no sharded decode to repeat on this context (none yet, or another call has used the context since)"); return TSQA_ERR_ARG; }
     // the descriptors hold offsets into the buffers of THAT call: a retry into other buffers would decode them against the wrong memory
     if (d_streams != c->sharded_streams || d_out != c->sharded_out) { c->set_error("sharded_decode_again: not the buffers of the sharded decode being repeated"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     return c->decode_again(d_streams, c->frames, c->sharded_n_local, d_out, d_status, s);
 }
 
 // ---- range reads: an index of a device-resident container, and reads of byte ranges of its uncompressed data ----
+
+// An index under construction: destroyed with whatever it holds by then, unless it is released to the caller.
+struct IndexDeleter { void operator()(tsqa_index* idx) const { tsqa_index_destroy(idx); } };
+using IndexPtr = std::unique_ptr<tsqa_index, IndexDeleter>;
 
 extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n, tsqa_index** out)
 {
@@ -713,34 +736,28 @@ extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n,
     TSQ_HIP(c, hipStreamSynchronize(s));
     uint32_t nb; uint64_t total;
     if (read_header(head, n, &nb, &total) != kHeaderOk) { c->set_error("index_create: bad header"); return TSQA_ERR_FORMAT; }
-    tsqa_index* idx = new (std::nothrow) tsqa_index();
+    IndexPtr idx(new (std::nothrow) tsqa_index());
     if (!idx) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
     idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = total;
-    int rc = TSQA_OK;
-    int32_t st = 0;
     try {
         idx->host_frames.resize(nb);
         idx->out_start.resize((size_t)nb + 1);
-    } catch (...) { rc = TSQA_ERR_ARG; c->set_error("index_create: out of host memory"); }
+        idx->item_first = {0ull, (uint64_t)nb};
+        idx->item_status = {TSQA_OK};
+    } catch (...) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
     // the frame walk of a full decompress, into the index's own descriptors (the context's are left alone)
-    auto walk = [&]() -> int {
-        TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)nb * sizeof(FrameInfo)));
-        TSQ_HIP(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t), s));
-        hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, idx->container, (uint64_t)n, nb, total, idx->frames, c->d_size, c->d_status);
-        TSQ_HIP(c, hipGetLastError());
-        TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipMemcpyAsync(idx->host_frames.data(), idx->frames, (size_t)nb * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipStreamSynchronize(s));
-        return TSQA_OK;
-    };
-    if (rc == TSQA_OK) rc = walk();
-    if (rc == TSQA_OK && st != 0) { c->set_error("index_create: malformed container (status %d)", st); rc = TSQA_ERR_FORMAT; }
-    if (rc != TSQA_OK) { tsqa_index_destroy(idx); return rc; }
+    int32_t st = 0;
+    TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)nb * sizeof(FrameInfo)));
+    TSQ_HIP(c, hipMemsetAsync(c->d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, idx->container, (uint64_t)n, nb, total, idx->frames, c->d_size, c->d_status);
+    TSQ_HIP(c, hipGetLastError());
+    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(idx->host_frames.data(), idx->frames, (size_t)nb * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    if (st != 0) { c->set_error("index_create: malformed container (status %d)", st); return TSQA_ERR_FORMAT; }
     for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = idx->host_frames[b].out_at;
     idx->out_start[nb] = total;
-    try { idx->item_first = {0ull, (uint64_t)nb}; idx->item_status = {TSQA_OK}; }
-    catch (...) { c->set_error("index_create: out of host memory"); tsqa_index_destroy(idx); return TSQA_ERR_ARG; }
-    *out = idx;
+    *out = idx.release();
     return TSQA_OK;
 }
 
@@ -763,6 +780,15 @@ extern "C" uint64_t tsqa_index_item_total(const tsqa_index* idx, uint32_t i)
 extern "C" int tsqa_index_item_status(const tsqa_index* idx, uint32_t i)
 {
     return idx && i < idx->item_status.size() ? idx->item_status[i] : TSQA_ERR_ARG;
+}
+
+// Two workgroups writing the same bytes would race: the destinations (at, length) of a call may touch, not overlap.  Sorts them.
+static bool destinations_overlap(std::vector<std::pair<uint64_t, uint64_t>>& dst)
+{
+    std::sort(dst.begin(), dst.end());
+    for (size_t k = 1; k < dst.size(); ++k)
+        if (dst[k - 1].first + dst[k - 1].second > dst[k].first) return true;
+    return false;
 }
 
 // tsqa_plan_ranges, with the reason for a refusal.  count_only: validate and count, write no item.
@@ -788,10 +814,7 @@ static int plan_ranges(const uint64_t* out_start, uint32_t nb, const tsqa_range*
         const uint64_t end = x.offset + x.length;
         for (uint32_t b = first_block(x.offset); b < nb && out_start[b] < end; ++b) count += out_start[b + 1] > out_start[b];
     }
-    // two workgroups writing the same bytes would race: destinations may touch, not overlap
-    std::sort(dst.begin(), dst.end());
-    for (size_t k = 1; k < dst.size(); ++k)
-        if (dst[k - 1].first + dst[k - 1].second > dst[k].first) { *why = "the destinations of two ranges overlap"; return TSQA_ERR_ARG; }
+    if (destinations_overlap(dst)) { *why = "the destinations of two ranges overlap"; return TSQA_ERR_ARG; }
     if (count > 0xFFFFFFFFull) { *why = "more than 2^32 - 1 items"; return TSQA_ERR_ARG; }
     *n_items = (uint32_t)count;
     if (count_only) return TSQA_OK;
@@ -831,23 +854,21 @@ extern "C" int tsqa_decompress_ranges_async(tsqa_ctx* c, const tsqa_index* idx, 
         c->set_error("decompress_ranges: %s", why);
         return TSQA_ERR_ARG;
     }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
-    int k = 0;
-    if (int rc = c->reserve_upload(c->range_up, (size_t)(n_items ? n_items : 1) * sizeof(tsqa_range_item), &k)) return rc;
-    tsqa_range_item* const host_items = static_cast<tsqa_range_item*>(c->range_up.host[k]);
-    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, host_items, (uint32_t)(c->range_up.cap[k] / sizeof(tsqa_range_item)), &n_items, &why)) {
+    tsqa_uploads::Slot up;
+    if (int rc = c->range_up.acquire(c, (size_t)(n_items ? n_items : 1) * sizeof(tsqa_range_item), &up)) return rc;
+    // (the items are planned straight into the pinned buffer)
+    if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, up.host<tsqa_range_item>(), (uint32_t)(up.cap() / sizeof(tsqa_range_item)), &n_items, &why)) {
         c->set_error("decompress_ranges: %s", why);
         return TSQA_ERR_ARG;
     }
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     if (n_items == 0) return TSQA_OK;
-    TSQ_HIP(c, hipMemcpyAsync(c->range_up.dev[k], host_items, (size_t)n_items * sizeof(tsqa_range_item), hipMemcpyHostToDevice, s));
-    const int rc = launch_range_kernel(c, idx->container, idx->frames, idx->n_blocks, static_cast<const RangeItem*>(c->range_up.dev[k]),
-                                       n_items, static_cast<uint8_t*>(d_out), d_status, s);
-    // (behind the kernel: neither copy of the items is touched again before the read that uses them has finished)
-    TSQ_HIP(c, hipEventRecord(c->range_up.done[k], s));
-    c->range_up.pending[k] = true;
+    TSQ_HIP(c, up.send((size_t)n_items * sizeof(tsqa_range_item), s));
+    const int rc = launch_read_kernel<dec_range_kernel>(c, n_items, s, idx->container, idx->frames, idx->n_blocks, up.dev<RangeItem>(),
+                                                        static_cast<uint8_t*>(d_out), d_status);
+    TSQ_HIP(c, up.commit(s));
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
@@ -857,13 +878,10 @@ extern "C" int tsqa_decompress_ranges(tsqa_ctx* c, const tsqa_index* idx, const 
                                       size_t out_cap, void* hip_stream)
 {
     if (!c) return TSQA_ERR_ARG;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     int rc = tsqa_decompress_ranges_async(c, idx, ranges, n_ranges, d_out, out_cap, c->d_status, s);
     if (rc) return rc;
-    int32_t st = 0;
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
-    return status_to_rc(c, st, "decompress_ranges");
+    return finish_sync(c, s, "decompress_ranges");
 }
 
 // ---- record reads: ranges addressed by item, one decode per touched block ----
@@ -945,26 +963,22 @@ extern "C" int tsqa_decompress_item_ranges_async(tsqa_ctx* c, const tsqa_index* 
                                out_cap, vi, vg, &why);
     } catch (...) {}
     if (prc) { c->set_error("decompress_item_ranges: %s", why); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint32_t n_items = (uint32_t)vi.size(), n_groups = (uint32_t)vg.size();
     // one upload: the items, then (on a 16-byte boundary) the groups
     const size_t groups_at = ((size_t)n_items * sizeof(tsqa_range_item) + 15u) & ~(size_t)15u, bytes = groups_at + (size_t)n_groups * sizeof(tsqa_block_group);
-    int k = 0;
-    if (int rc = c->reserve_upload(c->range_up, bytes ? bytes : 16, &k)) return rc;
+    tsqa_uploads::Slot up;
+    if (int rc = c->range_up.acquire(c, bytes ? bytes : 16, &up)) return rc;
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     if (n_groups == 0) return TSQA_OK;
-    uint8_t* const host = static_cast<uint8_t*>(c->range_up.host[k]);
-    memset(host, 0, bytes);
-    memcpy(host, vi.data(), (size_t)n_items * sizeof(tsqa_range_item));
-    memcpy(host + groups_at, vg.data(), (size_t)n_groups * sizeof(tsqa_block_group));
-    TSQ_HIP(c, hipMemcpyAsync(c->range_up.dev[k], host, bytes, hipMemcpyHostToDevice, s));
-    const uint8_t* const dev = static_cast<const uint8_t*>(c->range_up.dev[k]);
-    const int rc = launch_group_kernel(c, idx->container, idx->frames, idx->n_blocks, reinterpret_cast<const RangeItem*>(dev), n_items,
-                                       reinterpret_cast<const BlockGroup*>(dev + groups_at), n_groups, static_cast<uint8_t*>(d_out), d_status, s);
-    // (behind the kernel: neither copy of the descriptors is touched again before the read that uses them has finished)
-    TSQ_HIP(c, hipEventRecord(c->range_up.done[k], s));
-    c->range_up.pending[k] = true;
+    memset(up.host<uint8_t>(), 0, bytes);
+    std::copy(vi.begin(), vi.end(), up.host<tsqa_range_item>());
+    std::copy(vg.begin(), vg.end(), up.host<tsqa_block_group>(groups_at));
+    TSQ_HIP(c, up.send(bytes, s));
+    const int rc = launch_read_kernel<dec_group_kernel>(c, n_groups, s, idx->container, idx->frames, idx->n_blocks, up.dev<RangeItem>(), n_items,
+                                                        up.dev<BlockGroup>(groups_at), static_cast<uint8_t*>(d_out), d_status);
+    TSQ_HIP(c, up.commit(s));
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
@@ -974,13 +988,10 @@ extern "C" int tsqa_decompress_item_ranges(tsqa_ctx* c, const tsqa_index* idx, c
                                            size_t out_cap, void* hip_stream)
 {
     if (!c) return TSQA_ERR_ARG;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     int rc = tsqa_decompress_item_ranges_async(c, idx, ranges, n_ranges, d_out, out_cap, c->d_status, s);
     if (rc) return rc;
-    int32_t st = 0;
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
-    return status_to_rc(c, st, "decompress_item_ranges");
+    return finish_sync(c, s, "decompress_item_ranges");
 }
 
 // ---- batches: many independent items at offsets in one input and one output buffer ----
@@ -1021,10 +1032,7 @@ static int plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_
         if (x.out_cap) dst.emplace_back(x.out_at, x.out_cap);
         blocks += nb;
     }
-    // two items writing the same bytes would race: output ranges may touch, not overlap (input ranges may)
-    std::sort(dst.begin(), dst.end());
-    for (size_t k = 1; k < dst.size(); ++k)
-        if (dst[k - 1].first + dst[k - 1].second > dst[k].first) { *why = "two output ranges overlap"; return TSQA_ERR_ARG; }
+    if (destinations_overlap(dst)) { *why = "two output ranges overlap"; return TSQA_ERR_ARG; }          // (input ranges may)
     if (blocks > 0xFFFFFFFFull) { *why = "more than 2^32 - 1 blocks"; return TSQA_ERR_ARG; }
     if (mode == kPlanRangesOnly) return TSQA_OK;
     uint64_t at = 0;
@@ -1055,13 +1063,12 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
     // block -- stays bounded whatever the batch holds.  Items may span launches.
     const uint32_t budget = 2u * (uint32_t)c->n_cus;
     const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), bytes = item_bytes + n_blocks * sizeof(EncBatchBlock);
-    int k = 0;
-    if (int rc = c->reserve_upload(c->batch_up, bytes, &k)) return rc;
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, bytes, &up)) return rc;
     if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true, true, true)) return rc;
     if (int rc = c->reserve_batch(n_items)) return rc;
-    uint8_t* const host = static_cast<uint8_t*>(c->batch_up.host[k]);
-    BatchItem* const hi = reinterpret_cast<BatchItem*>(host);
-    EncBatchBlock* const hb = reinterpret_cast<EncBatchBlock*>(host + item_bytes);
+    BatchItem* const hi = up.host<BatchItem>();
+    EncBatchBlock* const hb = up.host<EncBatchBlock>(item_bytes);
     for (uint32_t i = 0; i < n_items; ++i) {
         const tsqa_batch_item& x = items[i];
         const uint32_t nb = (uint32_t)(first[i + 1] - first[i]);
@@ -1071,12 +1078,12 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
             hb[b] = EncBatchBlock{x.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
         }
     }
-    const BatchItem* const di = static_cast<const BatchItem*>(c->batch_up.dev[k]);
-    const EncBatchBlock* const db = reinterpret_cast<const EncBatchBlock*>(static_cast<const uint8_t*>(c->batch_up.dev[k]) + item_bytes);
+    const BatchItem* const di = up.dev<BatchItem>();
+    const EncBatchBlock* const db = up.dev<EncBatchBlock>(item_bytes);
     const uint8_t* const in = static_cast<const uint8_t*>(d_in);
     uint8_t* const out = static_cast<uint8_t*>(d_out);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], host, bytes, hipMemcpyHostToDevice, s));
+    TSQ_HIP(c, up.send(bytes, s));
     const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
     int rc = TSQA_OK;
     for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget) {
@@ -1084,10 +1091,10 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
         // the items with blocks in this launch: from the one that holds block b0 to the last that starts before b0 + nb
         const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
         const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
-        const bool timed = c->prof_begin(0, s);
+        ProfSpan span(c, 0, s);
         rc = launch_batch_encode_kernels(c, in, db + b0, nb, ext, c->slots, c->sizes, d_status, s);
-        if (rc) { if (timed) c->prof_used[0]--; break; }
-        if (timed) c->prof_end(0, s);
+        if (rc) { span.cancel(); break; }
+        span.end();
         if (align)                       // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
             hipLaunchKernelGGL(batch_pack_scan_packed_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, c->sizes, ext, align, out,
                                (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_status);
@@ -1096,9 +1103,7 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
                                c->batch_at, c->frame_at, d_sizes, d_status);
         hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out);
     }
-    // (behind the last kernel: neither copy of the descriptors is touched again before the batch that uses them has finished)
-    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
-    c->batch_up.pending[k] = true;
+    TSQ_HIP(c, up.commit(s));                            // (behind a partial batch too)
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
@@ -1121,7 +1126,7 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
     std::vector<uint64_t> first((size_t)n_items + 1);
     const char* why;
     if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanCompress)) { c->set_error("compress_batch: %s", why); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, out_size, 0u, nullptr, d_sizes, d_status, s);
 }
 
@@ -1130,15 +1135,12 @@ extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size
 {
     if (!c) return TSQA_ERR_ARG;
     if (!sizes) { c->set_error("compress_batch: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     if (int rc = c->reserve_batch(n_items)) return rc;
     int rc = tsqa_compress_batch_async(c, d_in, in_size, items, n_items, ext, d_out, out_size, c->batch_sizes, c->d_status, s);
     if (rc) return rc;
-    int32_t st = 0;
     TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
-    return status_to_rc(c, st, "compress_batch");
+    return finish_sync(c, s, "compress_batch");
 }
 
 // ---- packed batches: the items' containers one after the other in a dense arena, their places made on the device ----
@@ -1193,7 +1195,7 @@ extern "C" int tsqa_compress_batch_packed_async(tsqa_ctx* c, const void* d_in, s
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     return compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, d_offsets, d_sizes, d_status, s);
 }
 
@@ -1203,15 +1205,12 @@ extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t 
 {
     if (!c) return TSQA_ERR_ARG;
     if (!offsets || !sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     int rc = compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, nullptr, nullptr, c->d_status, s);
     if (rc) return rc;
-    int32_t st = 0;
     TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(&st, c->d_status, sizeof(st), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
-    return status_to_rc(c, st, "compress_batch_packed");
+    return finish_sync(c, s, "compress_batch_packed");
 }
 
 // (variant < 0: the context's decode variant; the synchronous form's retry after TSQA_ERR_STALL passes 4.  d_offsets != NULL: a
@@ -1229,24 +1228,23 @@ static int decompress_batch_async_impl(tsqa_ctx* c, const void* d_in, size_t in_
     }
     (void)hipSetDevice(c->device);
     const uint32_t total_blocks = (uint32_t)first[n_items];
-    int k = 0;
-    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
     if (int rc = c->reserve(total_blocks, false, false, true)) return rc;
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
-    BatchItem* const hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    BatchItem* const hi = up.host<BatchItem>();
     for (uint32_t i = 0; i < n_items; ++i)
         hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
-    if (d_offsets)
-        hipLaunchKernelGGL(batch_place_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<BatchItem*>(c->batch_up.dev[k]), n_items,
+    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
+    if (d_offsets)                       // (the one kernel that writes a slot's device copy: the items' places)
+        hipLaunchKernelGGL(batch_place_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, up.dev<BatchItem>(), n_items,
                            d_offsets, d_packed_sizes, (uint64_t)in_size);
-    hipLaunchKernelGGL(batch_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in),
-                       static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->frames, d_sizes, d_status);
+    hipLaunchKernelGGL(batch_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(),
+                       n_items, c->frames, d_sizes, d_status);
     // one decode over every frame of the batch (launch_decode_kernels picks the decoder by the block count, as for one container)
     const int rc = c->launch_decode_frames(d_in, c->frames, total_blocks, d_out, d_status, s, variant);
-    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
-    c->batch_up.pending[k] = true;
+    TSQ_HIP(c, up.commit(s));
     return rc;
 }
 
@@ -1254,7 +1252,7 @@ extern "C" int tsqa_decompress_batch_async(tsqa_ctx* c, const void* d_in, size_t
                                            uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
 {
     if (!c) return TSQA_ERR_ARG;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     return decompress_batch_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, d_sizes, d_status, s, -1);
 }
 
@@ -1265,9 +1263,27 @@ extern "C" int tsqa_decompress_batch_packed_async(tsqa_ctx* c, const void* d_are
 {
     if (!c) return TSQA_ERR_ARG;
     if (!d_offsets || !d_sizes) { c->set_error("decompress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     return decompress_batch_async_impl(c, d_arena, arena_size, items, n_blocks, n_items, d_out, out_size, d_out_sizes, d_status, s, -1, d_offsets,
                                        d_sizes);
+}
+
+// The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
+static int gather_heads(tsqa_ctx* c, const void* d_in, const tsqa_batch_item* items, uint32_t n_items, hipStream_t s, std::vector<uint8_t>& heads)
+{
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
+    BatchItem* const hi = up.host<BatchItem>();
+    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, 0, 0, 0, 0, 0};    // (the kernel reads no more)
+    heads.resize((size_t)n_items * kHeaderSize);
+    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
+    hipLaunchKernelGGL(batch_heads_kernel, dim3((uint32_t)(((uint64_t)n_items * kHeaderSize + 255u) / 256u)), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(), n_items, c->batch_heads);
+    TSQ_HIP(c, up.commit(s));
+    TSQ_HIP(c, hipMemcpyAsync(heads.data(), c->batch_heads, heads.size(), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return TSQA_OK;
 }
 
 // The synchronous form's decode of a (sub-)batch: the status lands in *st, the items' sizes in sizes[]; after TSQA_ERR_STALL once
@@ -1278,8 +1294,7 @@ static int decompress_batch_wait(tsqa_ctx* c, const void* d_in, size_t in_size, 
     for (int variant : {-1, 4}) {
         if (int rc = decompress_batch_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, c->batch_sizes, c->d_status, s, variant)) return rc;
         TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipMemcpyAsync(st, c->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipStreamSynchronize(s));
+        if (int rc = read_status(c, s, st)) return rc;
         if (*st != kErrStall) break;
     }
     return TSQA_OK;
@@ -1292,24 +1307,12 @@ extern "C" int tsqa_decompress_batch(tsqa_ctx* c, const void* d_in, size_t in_si
     if (!d_in || !d_out || !sizes) { c->set_error("decompress_batch: null pointer"); return TSQA_ERR_ARG; }
     const char* why;
     if (plan_batch(items, n_items, in_size, out_size, nullptr, nullptr, &why, kPlanRangesOnly)) { c->set_error("decompress_batch: %s", why); return TSQA_ERR_ARG; }
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     std::vector<int32_t> own;
     if (!item_status) { own.resize(n_items); item_status = own.data(); }
-    if (int rc = c->reserve_batch(n_items)) return rc;
-    // every header with one gather kernel and one copy
-    int k = 0;
-    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
-    BatchItem* const hi = static_cast<BatchItem*>(c->batch_up.host[k]);
-    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, 0, 0, 0};
-    std::vector<uint8_t> heads((size_t)n_items * kHeaderSize);
-    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(batch_heads_kernel, dim3((uint32_t)(((uint64_t)n_items * kHeaderSize + 255u) / 256u)), dim3(256), 0, s,
-                       static_cast<const uint8_t*>(d_in), static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->batch_heads);
-    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
-    c->batch_up.pending[k] = true;
-    TSQ_HIP(c, hipMemcpyAsync(heads.data(), c->batch_heads, heads.size(), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
+    std::vector<uint8_t> heads;
+    if (int rc = gather_heads(c, d_in, items, n_items, s, heads)) return rc;
     // items whose header is refused are reported and left out of the launch
     std::vector<tsqa_batch_item> ok_items;
     std::vector<uint32_t> ok_blocks, ok_index;
@@ -1346,10 +1349,9 @@ extern "C" int tsqa_decompress_batch(tsqa_ctx* c, const void* d_in, size_t in_si
 
 // ---- an index over a batch of containers (record reads: tsqa_decompress_item_ranges*) ----
 
-// tsqa_index_create_batch behind its argument checks.  The index under construction is the caller's (*made) from the moment it
-// exists: whatever ends this function early, an exception of a host allocation included, the caller destroys it.
+// tsqa_index_create_batch behind its argument checks; a host allocation may throw.
 static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                              tsqa_index** out, int32_t* item_status, tsqa_index** made)
+                              tsqa_index** out, int32_t* item_status)
 {
     // the batch planner's checks of the input ranges (the output ranges of the items are not used)
     std::vector<tsqa_batch_item> plain;
@@ -1364,26 +1366,15 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
     }
     hipStream_t s = c->stream;
     (void)hipSetDevice(c->device);
-    if (int rc = c->reserve_batch(n_items)) return rc;
     const uint8_t* const in = static_cast<const uint8_t*>(d_in);
-    // every header with one gather kernel and one copy (as tsqa_decompress_batch reads them)
-    int k = 0;
-    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
-    BatchItem* hi = static_cast<BatchItem*>(c->batch_up.host[k]);
-    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, 0, 0, 0, 0, 0};
-    std::vector<uint8_t> heads((size_t)n_items * kHeaderSize);
-    TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(batch_heads_kernel, dim3((uint32_t)(((uint64_t)n_items * kHeaderSize + 255u) / 256u)), dim3(256), 0, s, in,
-                       static_cast<const BatchItem*>(c->batch_up.dev[k]), n_items, c->batch_heads);
-    TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
-    c->batch_up.pending[k] = true;
-    TSQ_HIP(c, hipMemcpyAsync(heads.data(), c->batch_heads, heads.size(), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipStreamSynchronize(s));
+    std::vector<uint8_t> heads;
+    if (int rc = gather_heads(c, d_in, items, n_items, s, heads)) return rc;
     // the block counts the headers state (0: refused here), each item's first block, and its start in the concatenation of the data
     std::vector<uint32_t> nbs(n_items);
     std::vector<uint64_t> first((size_t)n_items + 1), verdicts(n_items);
-    if (int rc = c->reserve_upload(c->batch_up, (size_t)n_items * sizeof(BatchItem), &k)) return rc;
-    hi = static_cast<BatchItem*>(c->batch_up.host[k]);
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
+    BatchItem* const hi = up.host<BatchItem>();
     uint64_t blocks = 0, cat = 0;
     for (uint32_t i = 0; i < n_items; ++i) {
         uint32_t nb = 0; uint64_t total = 0;
@@ -1394,26 +1385,20 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
     }
     first[n_items] = blocks;
     if (blocks > 0xFFFFFFFFull) { c->set_error("index_create_batch: more than 2^32 - 1 blocks"); return TSQA_ERR_ARG; }
-    tsqa_index* idx = new (std::nothrow) tsqa_index();
+    IndexPtr idx(new (std::nothrow) tsqa_index());
     if (!idx) { c->set_error("index_create_batch: out of host memory"); return TSQA_ERR_ARG; }
-    *made = idx;
     idx->device = c->device; idx->container = in; idx->n = in_size;
     std::vector<tsqa_frame> walked(blocks);
     // one frame walk over all items, one lane each, into the index's own descriptors; verdicts and descriptors come back together
-    auto walk = [&]() -> int {
-        TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)(blocks ? blocks : 1) * sizeof(FrameInfo)));
-        TSQ_HIP(c, hipMemcpyAsync(c->batch_up.dev[k], hi, (size_t)n_items * sizeof(BatchItem), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(batch_index_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, in, static_cast<const BatchItem*>(c->batch_up.dev[k]),
-                           n_items, idx->frames, c->batch_sizes);
-        TSQ_HIP(c, hipGetLastError());
-        TSQ_HIP(c, hipEventRecord(c->batch_up.done[k], s));
-        c->batch_up.pending[k] = true;
-        TSQ_HIP(c, hipMemcpyAsync(verdicts.data(), c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        if (blocks) TSQ_HIP(c, hipMemcpyAsync(walked.data(), idx->frames, (size_t)blocks * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
-        TSQ_HIP(c, hipStreamSynchronize(s));
-        return TSQA_OK;
-    };
-    if (int rc = walk()) return rc;
+    TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)(blocks ? blocks : 1) * sizeof(FrameInfo)));
+    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
+    hipLaunchKernelGGL(batch_index_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, in, up.dev<BatchItem>(), n_items, idx->frames,
+                       c->batch_sizes);
+    TSQ_HIP(c, hipGetLastError());
+    TSQ_HIP(c, up.commit(s));
+    TSQ_HIP(c, hipMemcpyAsync(verdicts.data(), c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (blocks) TSQ_HIP(c, hipMemcpyAsync(walked.data(), idx->frames, (size_t)blocks * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
     // the healthy items' blocks, one after the other.  (An item whose header passed and whose frames did not leaves a gap in the
     // table the walk wrote: the table is closed up here and goes to the device once more.  Rare, and still a constant number of copies.)
     idx->item_first.resize((size_t)n_items + 1);
@@ -1445,7 +1430,7 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
         if (e != hipSuccess) { c->set_error("index_create_batch: hipMemcpy failed: %s", hipGetErrorString(e)); return TSQA_ERR_HIP; }
     }
     if (worst) c->set_error("index_create_batch: %u of %u items refused", refused, n_items);
-    *out = idx;
+    *out = idx.release();
     return worst;
 }
 
@@ -1456,13 +1441,9 @@ extern "C" int tsqa_index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_
     *out = nullptr;
     if (!c) return TSQA_ERR_ARG;
     if (!d_in) { c->set_error("index_create_batch: null pointer"); return TSQA_ERR_ARG; }
-    tsqa_index* made = nullptr;
-    int rc;
     // (the block counts come from the containers' own headers: the host tables may be refused by the allocator)
-    try { rc = index_create_batch(c, d_in, in_size, items, n_items, out, item_status, &made); }
-    catch (...) { c->set_error("index_create_batch: out of host memory"); rc = TSQA_ERR_ARG; *out = nullptr; }
-    if (!*out) tsqa_index_destroy(made);
-    return rc;
+    try { return index_create_batch(c, d_in, in_size, items, n_items, out, item_status); }
+    catch (...) { c->set_error("index_create_batch: out of host memory"); return TSQA_ERR_ARG; }
 }
 
 // ---- the second roofline denominator: what a plain device copy reaches on this GPU ----
