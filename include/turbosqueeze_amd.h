@@ -64,7 +64,10 @@ typedef struct tsqa_ctx tsqa_ctx;   /* one per (process, device): streams + scra
 /* device < 0: use the current HIP device.  Scratch is grown on demand and kept.
  * A context owns ONE set of scratch buffers (block slots, sizes, frame tables): calls on the same context must be
  * ordered on one stream at a time -- issue the next call on the same stream, or after the previous one has drained.
- * Two streams that want to run concurrently take two contexts. */
+ * Two streams that want to run concurrently take two contexts.
+ * Every *_async call reports into the status, size and table words it was GIVEN (d_status, d_out_size, d_sizes, d_offsets), and a
+ * later call never clears an earlier call's words unless the caller passes the same ones (the Python DeviceCodec passes one shared
+ * word to every call, so its status() is the last call's). */
 int         tsqa_create(int device, tsqa_ctx **out);
 void        tsqa_destroy(tsqa_ctx *ctx);
 const char *tsqa_last_error(const tsqa_ctx *ctx);

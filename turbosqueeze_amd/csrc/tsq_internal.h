@@ -96,8 +96,10 @@ struct tsqa_ctx {
     uint32_t prof_used[kProfKinds] = {0, 0, 0, 0};
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-    int reserve(size_t n_blocks, bool want_tables, bool want_slots = true, bool all_streams = false);
-    int reserve_duo(size_t n_blocks);
+    // what a growing reserve waits for before it frees scratch: the context's own stream and `s`, the stream the call was given
+    void wait_for(hipStream_t s) { (void)hipStreamSynchronize(stream); if (s && s != stream) (void)hipStreamSynchronize(s); }
+    int reserve(size_t n_blocks, bool want_tables, bool want_slots = true, bool all_streams = false, hipStream_t s = nullptr);
+    int reserve_duo(size_t n_blocks, hipStream_t s = nullptr);
     int reserve_host_frames(size_t n);
     int reserve_batch(size_t n_items);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it

@@ -110,7 +110,7 @@ inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const Fr
     auto launch_multi = [&](const FrameInfo* fr, uint32_t nblk, bool three) -> int {
         const uint32_t lds_bytes = DuoCopyLds::total > SymLds::total ? DuoCopyLds::total : SymLds::total;
         TSQ_RAISE_LDS(c, lds_need(dec_duo_kernel<1>, lds_bytes), lds_need(dec_duo_kernel<2>, lds_bytes));
-        if (int rc = c->reserve_duo(nblk)) return rc;
+        if (int rc = c->reserve_duo(nblk, s)) return rc;
         if (hipMemsetAsync(c->duo_flags, 0, (size_t)nblk * DuoCfg::FLAG_STRIDE * sizeof(uint32_t), s) != hipSuccess) { c->set_error("hipMemsetAsync failed"); return TSQA_ERR_HIP; }
         const uint32_t groups = (nblk + 7u) / 8u;
         if (three) hipLaunchKernelGGL(dec_duo_kernel<2>, dim3(24u * groups), dim3(SymCfg::T), lds_bytes, s, container, fr, nblk, out, status, c->duo_ring, c->duo_flags, c->decode_wait_limit);

@@ -153,12 +153,12 @@ extern "C" void tsqa_set_decode_wait_limit(tsqa_ctx* c, uint32_t polls) { if (c)
 // Scratch in HBM, grown on demand and kept: slots (TSQ_OUTPUT_SZ per block, the reference's
 // per-block output buffer, tsq_context.cpp:89-143), per-block sizes, frame offsets, frame
 // descriptors and one 256 KiB position table per block for the encoders (want_tables).
-// Growing waits for the context's stream, or (all_streams: the batch entry points, which promise that a call may be enqueued behind
-// another on a caller's stream) for the whole device: a call enqueued there may still be using what is freed.
-int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool all_streams)
+// Growing waits for the context's stream and for `s`, the stream the call was given (a call enqueued there before this one may still
+// be using what is freed), or (all_streams: the batch entry points) for the whole device.
+int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool all_streams, hipStream_t s)
 {
     (void)hipSetDevice(device);
-    auto wait = [&] { if (all_streams) (void)hipDeviceSynchronize(); else (void)hipStreamSynchronize(stream); };
+    auto wait = [&] { if (all_streams) (void)hipDeviceSynchronize(); else wait_for(s); };
     if (n_blocks > cap_blocks) {
         size_t nb = n_blocks;
         wait();
@@ -186,11 +186,11 @@ int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool a
 }
 
 // Scratch of the two-workgroup decoder (tsq_dec_duo.cuh): four chunk records and two counters per block.
-int tsqa_ctx::reserve_duo(size_t n_blocks)
+int tsqa_ctx::reserve_duo(size_t n_blocks, hipStream_t s)
 {
     (void)hipSetDevice(device);
     if (n_blocks <= cap_duo) return TSQA_OK;
-    (void)hipStreamSynchronize(stream);
+    wait_for(s);                                         // (a multi-workgroup decode enqueued on `s` may still be using the ring)
     (void)hipFree(duo_ring); (void)hipFree(duo_flags);
     duo_ring = nullptr; duo_flags = nullptr; cap_duo = 0;
     TSQ_HIP(this, hipMalloc(&duo_ring, n_blocks * (size_t)DuoCfg::SLOTS * DuoCfg::REC_WORDS * sizeof(uint32_t)));
@@ -343,7 +343,7 @@ int tsqa_ctx::launch_encode_to(const void* d_in, size_t n, size_t readable, size
                                uint32_t* sizes_out, int32_t* status, hipStream_t s)
 {
     const uint32_t nb = (uint32_t)tsqa_block_count(n);
-    int rc = reserve(nb, true, false);                   // (the streams go to the caller's slots: the context's own are not needed here)
+    int rc = reserve(nb, true, false, false, s);         // (the streams go to the caller's slots: the context's own are not needed here)
     if (rc) return rc;
     ProfSpan span(this, 0, s);
     rc = launch_encode_kernels(this, static_cast<const uint8_t*>(d_in), n, readable, stride, ext, slots_out, sizes_out, status, s);
@@ -355,7 +355,7 @@ int tsqa_ctx::launch_encode_to(const void* d_in, size_t n, size_t readable, size
 
 int tsqa_ctx::launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s)
 {
-    int rc = reserve((uint32_t)tsqa_block_count(n), true);
+    int rc = reserve((uint32_t)tsqa_block_count(n), true, true, false, s);
     if (rc) return rc;
     return launch_encode_to(d_in, n, readable, kBlockSize, ext, slots, sizes, status, s);
 }
@@ -456,7 +456,7 @@ static int decompress_device_async_impl(tsqa_ctx* c, const void* d_in, size_t n,
     if (!d_in || !d_out || !d_out_size || !d_status || n < 16 || n_blocks == 0) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
-    int rc = c->reserve(n_blocks, false, false);
+    int rc = c->reserve(n_blocks, false, false, false, s);
     if (rc) return rc;
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
@@ -674,7 +674,7 @@ extern "C" int tsqa_sharded_fetch_decode_async(tsqa_ctx* c, const void* host_con
     // buffers can hold -- before a single copy is enqueued (a container with more, shorter blocks than the job the buffers were sized
     // for must not overrun them).
     if ((uint64_t)n_local * kSlotSize > streams_cap) { c->set_error("sharded_fetch_decode: %u owned frames do not fit d_streams (%zu B)", n_local, streams_cap); return TSQA_ERR_FORMAT; }
-    if (int rc = c->reserve(n_local ? n_local : 1, false, false)) return rc;
+    if (int rc = c->reserve(n_local ? n_local : 1, false, false, false, s)) return rc;
     if (int rc = c->reserve_host_frames(n_local ? n_local : 1)) return rc;
     const char* why;
     const int rc = walk_host_frames(p, container_size, nb, tot, &why, [&](uint32_t b, uint64_t at, FrameInfo f) {
