@@ -301,14 +301,38 @@ int tsqa_compress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const t
  * for tsqa_decompress_device_async (decode again with decode variant 4).
  * tsqa_decompress_batch reads every header itself (one gather, one copy), leaves items with a refused header out (item_status:
  * TSQA_ERR_FORMAT, or TSQA_ERR_ARG when the total exceeds out_cap), decodes the rest in one batch, retries once after
- * TSQA_ERR_STALL on one workgroup per block, and when the batch reports a malformed container decodes the items one by one to find
- * those at fault.  item_status (host, may be NULL) and sizes (host) per item; every healthy item is delivered; the return value is
- * the largest item status.  Nothing is written outside the items' output ranges. */
+ * TSQA_ERR_STALL on one workgroup per block, and when the batch reports a malformed container sends the same items once more
+ * through the form with a verdict per item (tsqa_decompress_batch_items_async below): one more launch whatever the item count, and
+ * the statuses and sizes come back with one wait.  item_status (host, may be NULL) and sizes (host) per item; every healthy item is
+ * delivered; the return value is the largest item status.  Nothing is written outside the items' output ranges. */
 int tsqa_decompress_batch_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items,
                                 const uint32_t *n_blocks, uint32_t n_items, void *d_out, size_t out_size,
                                 uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
 int tsqa_decompress_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
                           void *d_out, size_t out_size, uint64_t *sizes, int32_t *item_status, void *hip_stream);
+
+/* tsqa_decompress_batch_async with a verdict per item, made on the device: a damaged container costs its own item and nothing
+ * else.  Arguments as for tsqa_decompress_batch_async, plus d_item_status (device, n_items words).
+ *   - Item i's bytes and d_sizes[i] are exactly those of tsqa_decompress_batch_async whenever d_item_status[i] == 0, whatever the
+ *     other items are.
+ *   - d_item_status[i] is the word that tsqa_decompress_device_async leaves for container i alone with the same block count and
+ *     capacity: TSQA_ERR_FORMAT for anything the frame walk refuses (a total above out_cap and, in the packed form, a bad place
+ *     included), else the decoder's code for a malformed stream (TSQA_ERR_STREAM), else 0.
+ *   - An item refused by the walk has nothing written to its output range.  An item refused by a decoder has undefined contents
+ *     in its own range.  Either way d_sizes[i] = 0.  Nothing outside the items' ranges is ever written.
+ *   - *d_status = the largest item status.
+ *   - TSQA_ERR_ARG before anything is enqueued, with nothing written, as for tsqa_decompress_batch_async; a NULL d_item_status is
+ *     one more such error.
+ * Every block runs on one workgroup of its own (the decoder of decode variant 4) at any block count: the context's decode variant
+ * and wait limit are not looked at, and TSQA_ERR_STALL is never reported.  The several-workgroups decoders end their waits on
+ * "another block has reported an error", which means the launch, not the item, so they are not offered here; the price is that a
+ * batch with fewer blocks than half the CUs decodes at the one-workgroup latency per block (4.68 against 2.66 ms at 30 blocks of
+ * 4 MiB).  Where every item is expected to be healthy and the batch is that small, tsqa_decompress_batch_async is the faster call.
+ * tsqa_decompress_batch_packed_items_async: the same for tsqa_decompress_batch_packed_async's arguments; a bad place is that
+ * item's TSQA_ERR_FORMAT and is never read. */
+int tsqa_decompress_batch_items_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items,
+                                      const uint32_t *n_blocks, uint32_t n_items, void *d_out, size_t out_size,
+                                      uint64_t *d_sizes, int32_t *d_item_status, int32_t *d_status, void *hip_stream);
 
 /*
  * Packed batches: the same compress, with every container's place chosen on the device once its size exists, so that the arena is
@@ -359,6 +383,10 @@ int tsqa_decompress_batch_packed_async(tsqa_ctx *ctx, const void *d_arena, size_
                                        const uint64_t *d_sizes, const tsqa_batch_item *items, const uint32_t *n_blocks,
                                        uint32_t n_items, void *d_out, size_t out_size, uint64_t *d_out_sizes, int32_t *d_status,
                                        void *hip_stream);
+int tsqa_decompress_batch_packed_items_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets,
+                                             const uint64_t *d_sizes, const tsqa_batch_item *items, const uint32_t *n_blocks,
+                                             uint32_t n_items, void *d_out, size_t out_size, uint64_t *d_out_sizes,
+                                             int32_t *d_item_status, int32_t *d_status, void *hip_stream);
 
 /*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in

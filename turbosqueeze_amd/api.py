@@ -189,6 +189,10 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_compress_batch_packed.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_batch_packed_async.restype = C.c_int
     L.tsqa_decompress_batch_packed_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_decompress_batch_items_async.restype = C.c_int
+    L.tsqa_decompress_batch_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.tsqa_decompress_batch_packed_items_async.restype = C.c_int
+    L.tsqa_decompress_batch_packed_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
     L.tsqa_index_create_batch.restype = C.c_int
     L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
     L.tsqa_index_items.restype = C.c_uint32
@@ -502,20 +506,26 @@ class PackedBatch:
         self.codec, self.arena, self.offsets, self.sizes, self.lengths = codec, arena, offsets, sizes, lengths
         self.views = [arena[o:o + n] for o, n in zip(offsets, sizes)]
 
-    def decompress(self, out=None):
+    def decompress(self, out=None, item_status: bool = False):
         """The items back, through tsqa_decompress_batch (which decodes again by itself after TSQA_ERR_STALL): a list of views into
-        one output arena (`out`, or a new one of sum(lengths) bytes)."""
+        one output arena (`out`, or a new one of sum(lengths) bytes).  item_status=True: a refused item does not raise; -> (views,
+        statuses), the view None and the status a TSQA_ERR_* where an item was refused, every healthy item delivered."""
         codec, items, at = self.codec, [], 0
         for o, n, ln in zip(self.offsets, self.sizes, self.lengths):
             items.append((o, n, at, ln))
             at += ln
         out = codec._out_arena(out, at)
         got = (C.c_uint64 * len(items))()
+        status = (C.c_int32 * len(items))(*([-1] * len(items))) if item_status else None
         rc = codec.L.tsqa_decompress_batch(codec.h, self.arena.data_ptr(), self.arena.numel(), _batch_array(items), len(items), out.data_ptr(),
-                                           out.numel(), got, None, codec._stream())
-        if rc:
+                                           out.numel(), got, status, codec._stream())
+        # (a return value that is no item's status is an error of the call itself: bad arguments, the HIP runtime)
+        if rc and (status is None or rc != max(status)):
             raise codec._err(rc)
-        return [out[a:a + int(got[k])] for k, (_, _, a, _) in enumerate(items)]
+        views = [out[a:a + int(got[k])] for k, (_, _, a, _) in enumerate(items)]
+        if status is None:
+            return views
+        return [v if st == 0 else None for v, st in zip(views, status)], [int(st) for st in status]
 
     def index(self) -> "BatchIndex":
         """One index over the dense arena, for record reads: index().read(item, offset, length)."""
@@ -829,6 +839,18 @@ class DeviceCodec:
         if rc:
             raise self._err(rc)
 
+    def decompress_batch_items_async(self, arena, items, n_blocks, out, d_sizes, d_item_status) -> None:
+        """tsqa_decompress_batch_items_async on the current stream: decompress_batch_async with a verdict per item.  d_item_status
+        (an int32 CUDA tensor, one per item) gets each item's TSQA_ERR_* or 0, d_sizes[i] = 0 where it is not 0, and every other
+        item is complete; status() becomes the largest item status."""
+        import numpy as np
+        nb = np.ascontiguousarray(n_blocks, dtype=np.uint32)
+        rc = self.L.tsqa_decompress_batch_items_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), nb.ctypes.data, len(items),
+                                                      out.data_ptr(), out.numel(), d_sizes.data_ptr(),
+                                                      d_item_status.data_ptr() if d_item_status is not None else None,
+                                                      self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
 
     def compress_batch_packed_async(self, arena, items, ext: int, align: int, out, d_offsets, d_sizes) -> None:
         """tsqa_compress_batch_packed_async on the current stream, nothing waited for: items = (in_at, in_len) offsets into the uint8
@@ -851,6 +873,21 @@ class DeviceCodec:
         rc = self.L.tsqa_decompress_batch_packed_async(self.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
                                                        _batch_array(quads), nb.ctypes.data, len(quads), out.data_ptr(), out.numel(),
                                                        d_out_sizes.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def decompress_batch_packed_items_async(self, arena, d_offsets, d_sizes, items, n_blocks, out, d_out_sizes, d_item_status) -> None:
+        """tsqa_decompress_batch_packed_items_async on the current stream: decompress_batch_packed_async with a verdict per item in
+        d_item_status (an int32 CUDA tensor, one per item), as decompress_batch_items_async; a bad place is its item's
+        TSQA_ERR_FORMAT."""
+        import numpy as np
+        nb = np.ascontiguousarray(n_blocks, dtype=np.uint32)
+        quads = [(0, 0, it[-2], it[-1]) for it in items]
+        rc = self.L.tsqa_decompress_batch_packed_items_async(self.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
+                                                             _batch_array(quads), nb.ctypes.data, len(quads), out.data_ptr(), out.numel(),
+                                                             d_out_sizes.data_ptr(),
+                                                             d_item_status.data_ptr() if d_item_status is not None else None,
+                                                             self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 

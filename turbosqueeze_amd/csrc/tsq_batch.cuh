@@ -182,6 +182,54 @@ __global__ __launch_bounds__(256) void batch_walk_kernel(const uint8_t* __restri
     atomicMax(status, kErrFormat);
 }
 
+// batch_walk_kernel with a verdict per item (tsqa_decompress_batch_items_async): the same walk and the same validation, but a
+// refusal goes to item_status[i] (kErrFormat) and not to a word of the batch, and every block of every item learns its owner:
+// owner[first_block_i + k] = i, for a refused item too -- its workgroups are launched like the others and find their item's word
+// through the table in order to leave (dec_item_kernel).  d_sizes[i] = the item's total, 0 when it is refused here; the closing
+// kernel clears it for an item that a decoder refuses.  item_status is zero before this kernel runs and nothing else writes it yet.
+__global__ __launch_bounds__(256) void batch_walk_items_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items,
+                                                               uint32_t n_items, FrameInfo* __restrict__ frames, uint32_t* __restrict__ owner,
+                                                               uint64_t* __restrict__ d_sizes, int32_t* __restrict__ item_status)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const BatchItem it = items[i];
+    const uint8_t* const c = in + it.in_at;
+    const uint64_t n = it.in_len;
+    FrameInfo* const fr = frames + it.first_block;
+    uint32_t* const own = owner + it.first_block;
+    for (uint32_t b = 0; b < it.n_blocks; ++b) own[b] = i;
+    uint32_t nb = 0;
+    uint64_t total = 0, at = kHeaderSize, oat = 0;
+    bool bad = read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks || total > it.out_cap;
+    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
+        FrameInfo f;
+        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
+        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
+        fr[b] = f;
+        oat += f.out_len;
+        at += kFrameWordSize + f.stream_len;
+    }
+    if (!bad && oat != total) bad = true;
+    d_sizes[i] = bad ? 0 : total;
+    if (!bad) return;
+    for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
+    item_status[i] = kErrFormat;
+}
+
+// Behind the decode of tsqa_decompress_batch_items_async, one lane per item: an item that the walk or a decoder refused gives no
+// size, and the batch's word is the largest item status.  No other kernel of that path writes *status.
+__global__ __launch_bounds__(256) void batch_close_items_kernel(uint32_t n_items, const int32_t* __restrict__ item_status,
+                                                                uint64_t* __restrict__ d_sizes, int32_t* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const int32_t st = item_status[i];
+    if (st == 0) return;
+    d_sizes[i] = 0;
+    atomicMax(status, st);
+}
+
 constexpr uint64_t kItemRefused = ~0ull;  // verdicts[i] of an item whose container batch_index_walk_kernel refuses
 
 // One lane per item of a batch index (tsqa_index_create_batch): batch_walk_kernel's walk with a verdict per item instead of one

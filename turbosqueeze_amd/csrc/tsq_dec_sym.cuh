@@ -350,6 +350,15 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
     sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, status);
 }
 
+// dec_sym_kernel with a status word per batch item (tsqa_decompress_batch_items_async): block blockIdx.x reads and reports into the
+// word of the item that owns it (owner[]: batch_walk_items_kernel), so a fault ends that item's remaining blocks and nobody else's.
+__global__ __launch_bounds__(1024) void dec_item_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                        const uint32_t* __restrict__ owner, uint8_t* __restrict__ outbuf,
+                                                        int32_t* __restrict__ item_status)
+{
+    sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, item_status + owner[blockIdx.x]);
+}
+
 // Range reads (tsqa_decompress_ranges_async): one workgroup per item; nothing outside [out_at, out_at + hi - lo) of `outbuf` is written.
 __global__ __launch_bounds__(1024) void dec_range_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames, uint32_t n_frames,
                                                          const RangeItem* __restrict__ items, uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)

@@ -57,6 +57,7 @@ struct tsqa_ctx {
     uint32_t* sizes = nullptr;         // n_blocks stream sizes
     uint64_t* frame_at = nullptr;      // n_blocks + 1 frame offsets in the container
     tsq::FrameInfo* frames = nullptr;  // n_blocks frame descriptors (decode)
+    uint32_t* block_owner = nullptr;   // n_blocks: the batch item each frame belongs to (tsqa_decompress_batch_items_async)
     uint16_t* tables = nullptr;        // n_blocks x 2^17 u16 position tables of the encoders
     size_t cap_blocks = 0, cap_tables = 0, cap_slots = 0;
     tsq::FrameInfo* host_frames = nullptr;     // frame descriptors built on the host (sharded fetch + decode): pinned
@@ -72,7 +73,8 @@ struct tsqa_ctx {
     void forget_sharded() { sharded_n_local = 0; sharded_streams = nullptr; sharded_out = nullptr; }
     tsqa_uploads range_up, batch_up;           // range-read items; batch descriptors
     // batches: per item, the running frame offset of a compress batch across its launches, and the sizes, the offsets of a packed
-    // batch (one more than items) and the headers the synchronous forms read back
+    // batch (one more than items), the headers the synchronous forms read back and the item statuses of the synchronous decompress
+    int32_t* batch_status = nullptr;
     uint64_t* batch_at = nullptr;
     uint64_t* batch_sizes = nullptr;
     uint64_t* batch_offsets = nullptr;

@@ -137,8 +137,9 @@ inline int launch_decode_kernels(tsqa_ctx* c, const uint8_t* container, const Fr
     return 0;
 }
 
-// Range reads (dec_range_kernel, one workgroup per item) and record reads (dec_group_kernel, one per group), at any count: `args`
-// are the kernel's own.  Items and groups are in device memory.
+// Range reads (dec_range_kernel, one workgroup per item), record reads (dec_group_kernel, one per group) and the batch decode with
+// a verdict per item (dec_item_kernel, one per block), at any count: `args` are the kernel's own.  Items, groups and owners are in
+// device memory.
 template <auto Kernel, class... Args>
 inline int launch_read_kernel(tsqa_ctx* c, uint32_t n_groups, hipStream_t s, Args... args)
 {

@@ -136,12 +136,13 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_pool) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->slots); (void)hipFree(c->tables); (void)hipFree(c->sizes); (void)hipFree(c->frame_at);
-    (void)hipFree(c->frames); (void)hipFree(c->d_size); (void)hipFree(c->d_status);
+    (void)hipFree(c->frames); (void)hipFree(c->block_owner); (void)hipFree(c->d_size); (void)hipFree(c->d_status);
     (void)hipFree(c->duo_ring); (void)hipFree(c->duo_flags);
     if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
     c->range_up.destroy(); c->batch_up.destroy();
     (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
+    (void)hipFree(c->batch_status);
     delete c;
 }
 
@@ -152,7 +153,7 @@ extern "C" void tsqa_set_decode_wait_limit(tsqa_ctx* c, uint32_t polls) { if (c)
 
 // Scratch in HBM, grown on demand and kept: slots (TSQ_OUTPUT_SZ per block, the reference's
 // per-block output buffer, tsq_context.cpp:89-143), per-block sizes, frame offsets, frame
-// descriptors and one 256 KiB position table per block for the encoders (want_tables).
+// descriptors with the batch item that owns each, and one 256 KiB position table per block for the encoders (want_tables).
 // Growing waits for the context's stream and for `s`, the stream the call was given (a call enqueued there before this one may still
 // be using what is freed), or (all_streams: the batch entry points) for the whole device.
 int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool all_streams, hipStream_t s)
@@ -162,12 +163,13 @@ int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool a
     if (n_blocks > cap_blocks) {
         size_t nb = n_blocks;
         wait();
-        (void)hipFree(sizes); (void)hipFree(frame_at); (void)hipFree(frames);
-        sizes = nullptr; frame_at = nullptr; frames = nullptr; cap_blocks = 0;
+        (void)hipFree(sizes); (void)hipFree(frame_at); (void)hipFree(frames); (void)hipFree(block_owner);
+        sizes = nullptr; frame_at = nullptr; frames = nullptr; block_owner = nullptr; cap_blocks = 0;
         forget_sharded();                                // (the descriptors of a sharded decode went with `frames`)
         TSQ_HIP(this, hipMalloc(&sizes, nb * sizeof(uint32_t)));
         TSQ_HIP(this, hipMalloc(&frame_at, (nb + 1) * sizeof(uint64_t)));
         TSQ_HIP(this, hipMalloc(&frames, nb * sizeof(FrameInfo)));
+        TSQ_HIP(this, hipMalloc(&block_owner, nb * sizeof(uint32_t)));
         cap_blocks = nb;
     }
     if (want_slots && n_blocks > cap_slots) {        // (callers that bring their own slots -- the sharded block API -- never pay for these)
@@ -253,13 +255,14 @@ int tsqa_ctx::reserve_batch(size_t n_items)
     if (n_items <= cap_batch) return TSQA_OK;
     // (batch calls run on callers' streams too, and one enqueued there may still be using the tables that are freed below)
     (void)hipDeviceSynchronize();
-    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_offsets); (void)hipFree(batch_heads);
-    batch_at = nullptr; batch_sizes = nullptr; batch_offsets = nullptr; batch_heads = nullptr; cap_batch = 0;
+    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_offsets); (void)hipFree(batch_heads); (void)hipFree(batch_status);
+    batch_at = nullptr; batch_sizes = nullptr; batch_offsets = nullptr; batch_heads = nullptr; batch_status = nullptr; cap_batch = 0;
     size_t want = 256; while (want < n_items) want *= 2;
     TSQ_HIP(this, hipMalloc(&batch_at, want * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_sizes, want * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_offsets, (want + 1) * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_heads, want * kHeaderSize));
+    TSQ_HIP(this, hipMalloc(&batch_status, want * sizeof(int32_t)));
     cap_batch = want;
     return TSQA_OK;
 }
@@ -1268,6 +1271,70 @@ extern "C" int tsqa_decompress_batch_packed_async(tsqa_ctx* c, const void* d_are
                                        d_sizes);
 }
 
+// The batch decompress with a verdict per item (tsqa_decompress_batch_items_async; d_offsets != NULL: the packed form, as in
+// decompress_batch_async_impl): the same planning, upload slot and scratch rule; batch_walk_items_kernel, one dec_item_kernel
+// workgroup per block whatever the context's decode variant (it waits for nobody: no TSQA_ERR_STALL), batch_close_items_kernel.
+static int decompress_batch_items_async_impl(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                             uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_item_status,
+                                             int32_t* d_status, hipStream_t s, const uint64_t* d_offsets = nullptr,
+                                             const uint64_t* d_packed_sizes = nullptr)
+{
+    if (!d_in || !d_out || !d_sizes || !d_item_status || !d_status || !n_blocks) { c->set_error("decompress_batch_items: null pointer"); return TSQA_ERR_ARG; }
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, d_offsets ? kPlanPlaced : kPlanDecompress)) {
+        c->set_error("decompress_batch_items: %s", why);
+        return TSQA_ERR_ARG;
+    }
+    (void)hipSetDevice(c->device);
+    const uint32_t total_blocks = (uint32_t)first[n_items];
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
+    if (int rc = c->reserve(total_blocks, false, false, true)) return rc;
+    c->forget_sharded();                                 // the frame walk below overwrites c->frames
+    BatchItem* const hi = up.host<BatchItem>();
+    for (uint32_t i = 0; i < n_items; ++i)
+        hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
+    TSQ_HIP(c, hipMemsetAsync(d_item_status, 0, (size_t)n_items * sizeof(int32_t), s));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
+    const dim3 per_item((n_items + 255u) / 256u);
+    if (d_offsets)
+        hipLaunchKernelGGL(batch_place_kernel, per_item, dim3(256), 0, s, up.dev<BatchItem>(), n_items, d_offsets, d_packed_sizes, (uint64_t)in_size);
+    hipLaunchKernelGGL(batch_walk_items_kernel, per_item, dim3(256), 0, s, static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(), n_items,
+                       c->frames, c->block_owner, d_sizes, d_item_status);
+    ProfSpan span(c, 1, s);
+    int rc = launch_read_kernel<dec_item_kernel>(c, total_blocks, s, static_cast<const uint8_t*>(d_in), static_cast<const FrameInfo*>(c->frames),
+                                                 static_cast<const uint32_t*>(c->block_owner), static_cast<uint8_t*>(d_out), d_item_status);
+    if (rc) span.cancel(); else span.end();
+    hipLaunchKernelGGL(batch_close_items_kernel, per_item, dim3(256), 0, s, n_items, static_cast<const int32_t*>(d_item_status), d_sizes, d_status);
+    TSQ_HIP(c, up.commit(s));                            // (however the decode launch went: the walk has been enqueued)
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_batch_items_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items,
+                                                 const uint32_t* n_blocks, uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes,
+                                                 int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    return decompress_batch_items_async_impl(c, d_in, in_size, items, n_blocks, n_items, d_out, out_size, d_sizes, d_item_status, d_status, s);
+}
+
+extern "C" int tsqa_decompress_batch_packed_items_async(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets,
+                                                        const uint64_t* d_sizes, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                                        uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_out_sizes,
+                                                        int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_offsets || !d_sizes) { c->set_error("decompress_batch_packed_items: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    return decompress_batch_items_async_impl(c, d_arena, arena_size, items, n_blocks, n_items, d_out, out_size, d_out_sizes, d_item_status,
+                                             d_status, s, d_offsets, d_sizes);
+}
+
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
 static int gather_heads(tsqa_ctx* c, const void* d_in, const tsqa_batch_item* items, uint32_t n_items, hipStream_t s, std::vector<uint8_t>& heads)
 {
@@ -1331,12 +1398,17 @@ extern "C" int tsqa_decompress_batch(tsqa_ctx* c, const void* d_in, size_t in_si
         if (st == 0) {
             for (uint32_t j = 0; j < m; ++j) sizes[ok_index[j]] = got[j];
         } else {
-            // (the error path only) the items at fault are found by decoding each alone; every healthy item's bytes are delivered
+            // (the error path only) the same items once more with a status word each: the items at fault are found on the device, in
+            // one launch, and every healthy item's bytes are delivered; sizes and statuses come back with one wait
+            std::vector<int32_t> verdict(m);
+            if (int rc = decompress_batch_items_async_impl(c, d_in, in_size, ok_items.data(), ok_blocks.data(), m, d_out, out_size, c->batch_sizes,
+                                                           c->batch_status, c->d_status, s)) return rc;
+            TSQ_HIP(c, hipMemcpyAsync(got.data(), c->batch_sizes, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            TSQ_HIP(c, hipMemcpyAsync(verdict.data(), c->batch_status, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (int rc = read_status(c, s, &st)) return rc;
             for (uint32_t j = 0; j < m; ++j) {
-                uint64_t one = 0;
-                if (int rc = decompress_batch_wait(c, d_in, in_size, &ok_items[j], &ok_blocks[j], 1, d_out, out_size, &one, &st, s)) return rc;
-                item_status[ok_index[j]] = st;
-                sizes[ok_index[j]] = st ? 0 : one;
+                item_status[ok_index[j]] = verdict[j];
+                sizes[ok_index[j]] = verdict[j] ? 0 : got[j];
             }
         }
     }
