@@ -389,6 +389,53 @@ int tsqa_decompress_batch_packed_items_async(tsqa_ctx *ctx, const void *d_arena,
                                              int32_t *d_item_status, int32_t *d_status, void *hip_stream);
 
 /*
+ * Dense decompress of a packed batch that takes nothing about the items from the host: block counts and output places are made on
+ * the device from the 16 header bytes of each container, and the items land one after the other in d_out.  What a consumer that
+ * only received an arena and its two tables needs (another rank, a file staged into device memory, an earlier pipeline stage).
+ *
+ * Layout rule: tsqa_plan_packed's, applied to the uncompressed sizes (align: a power of two, 1 to 4096):
+ *   out_offsets[0] = 0;  out_offsets[i + 1] = round_up(out_offsets[i] + total_i, align) for i + 1 < n_items;  the last entry is not
+ *   rounded: out_offsets[n_items] = the bytes needed.  first_block[0] = 0;  first_block[i + 1] = first_block[i] + blocks_i:
+ *   first_block[n_items] = the blocks needed.  An item refused at its header counts as total 0, blocks 0.  Item i's data is
+ *   d_out[out_offsets[i], out_offsets[i] + out_sizes[i]); padding bytes are never written.
+ *
+ * tsqa_plan_dense: host only.  The rule above from totals[] and blocks[] (blocks[i] == 0: a refused item, its total is not looked
+ *   at) -> out_offsets[n_items + 1], first_block[n_items + 1].  *n_fit = the index of the first accepted item that does not fit
+ *   cap_blocks blocks and out_size bytes, n_items when all do.  TSQA_ERR_ARG for a NULL pointer, n_items == 0 or a bad align.
+ *
+ * tsqa_decompress_batch_packed_dense_async: d_offsets, d_sizes (device, n_items) place the containers in d_arena, as
+ * tsqa_compress_batch_packed_async leaves them; nothing in them or in the arena is trusted.  Per item, on the device:
+ *   1. Place: sizes[i] <= arena_size, offsets[i] <= arena_size - sizes[i], sizes[i] >= 16, else TSQA_ERR_FORMAT and not one byte
+ *      of the item is read.
+ *   2. Header: the magic, 1 <= count <= (sizes[i] - 16) / 6, total <= count * TSQ_BLOCK_SZ, else TSQA_ERR_FORMAT; only the 16
+ *      header bytes have been read by then.
+ *   3. Fit: first_block[i] + blocks_i <= cap_blocks and out_offsets[i] + total_i <= out_size.  Both sums only grow, so the fitting
+ *      items are a prefix of the accepted ones.  An accepted item that does not fit gets TSQA_ERR_OVERFLOW, and nothing of it is
+ *      read or written.  d_out_offsets (n_items + 1), d_first_block (n_items + 1) and d_out_sizes are complete and correct for
+ *      every item whatever fits (sums below 2^55), and a retry with out_offsets[n_items] bytes and first_block[n_items] blocks
+ *      succeeds: the contract of the packed compress.
+ *   4. Decode: the fitting items go through tsqa_decompress_batch_packed_items_async's kernels.  d_item_status[i] is the word
+ *      that call leaves for the item when given the header's block count and out_cap = total_i; d_out_sizes[i] = the uncompressed
+ *      size, 0 for any nonzero status; *d_status = the largest item status.  One workgroup per block: TSQA_ERR_STALL is never
+ *      reported.  Nothing outside the fitting items' ranges is written.
+ * cap_blocks: the blocks the call may decode (it sizes the context's frame scratch and the decode launch: pass a tight value).
+ * Measure only: d_out == NULL with out_size == 0 (cap_blocks is not looked at).  The tables are filled, every accepted item reads
+ * TSQA_ERR_OVERFLOW, d_out_sizes is all 0 and nothing else is written: one small read of out_offsets[n_items] and
+ * first_block[n_items] tells a caller the room a decode needs.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL arena, table or status pointer, n_items == 0, a bad
+ * align, a non-NULL d_out with out_size == 0 or cap_blocks == 0, a NULL d_out with out_size != 0.
+ * The item table lives in the context's scratch and nothing is uploaded; the call returns at once and may be enqueued again on the
+ * same stream before the first has run (a call with more items or blocks than any before it first waits for the device, then
+ * grows the scratch).
+ */
+int tsqa_plan_dense(const uint64_t *totals, const uint32_t *blocks, uint32_t n_items, uint32_t align, uint64_t out_size,
+                    uint32_t cap_blocks, uint64_t *out_offsets, uint64_t *first_block, uint32_t *n_fit);
+int tsqa_decompress_batch_packed_dense_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets,
+                                             const uint64_t *d_sizes, uint32_t n_items, uint32_t align, uint32_t cap_blocks,
+                                             void *d_out, size_t out_size, uint64_t *d_out_offsets, uint64_t *d_out_sizes,
+                                             uint64_t *d_first_block, int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+
+/*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
  * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
  * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.

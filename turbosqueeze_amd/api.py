@@ -191,6 +191,11 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_batch_packed_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_batch_items_async.restype = C.c_int
     L.tsqa_decompress_batch_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.tsqa_plan_dense.restype = C.c_int
+    L.tsqa_plan_dense.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, vp]
+    L.tsqa_decompress_batch_packed_dense_async.restype = C.c_int
+    L.tsqa_decompress_batch_packed_dense_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                                           vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_batch_packed_items_async.restype = C.c_int
     L.tsqa_decompress_batch_packed_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
     L.tsqa_index_create_batch.restype = C.c_int
@@ -374,6 +379,22 @@ def plan_packed(sizes, align: int = 16):
     return [int(x) for x in offsets]
 
 
+def plan_dense(totals, blocks, align: int = 16, out_size: int = 0, cap_blocks: int = 0):
+    """tsqa_plan_dense (host only): the dense output layout of items with these uncompressed sizes and block counts (blocks[i] == 0:
+    an item refused at its header) -> (out_offsets, then the bytes needed; first_block, then the blocks needed; n_fit: the first
+    accepted item that does not fit out_size bytes and cap_blocks blocks, len(totals) when all do)."""
+    import numpy as np
+    tot = np.ascontiguousarray(totals, dtype=np.uint64)
+    nb = np.ascontiguousarray(blocks, dtype=np.uint32)
+    offsets, first = np.zeros(len(tot) + 1, dtype=np.uint64), np.zeros(len(tot) + 1, dtype=np.uint64)
+    n_fit = C.c_uint32(0)
+    rc = lib().tsqa_plan_dense(tot.ctypes.data, nb.ctypes.data, len(tot), align, out_size, cap_blocks, offsets.ctypes.data, first.ctypes.data,
+                               C.byref(n_fit))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_dense refused the arguments")
+    return [int(x) for x in offsets], [int(x) for x in first], int(n_fit.value)
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -505,6 +526,24 @@ class PackedBatch:
     def __init__(self, codec: "DeviceCodec", arena, offsets, sizes, lengths):
         self.codec, self.arena, self.offsets, self.sizes, self.lengths = codec, arena, offsets, sizes, lengths
         self.views = [arena[o:o + n] for o, n in zip(offsets, sizes)]
+
+    @classmethod
+    def from_device(cls, codec: "DeviceCodec", arena, d_offsets, d_sizes) -> "PackedBatch":
+        """A packed batch received as an arena and its two tables in device memory (int64 CUDA tensors: a place per item; one more
+        entry in d_offsets is ignored), from whoever made them: no host lengths are needed.  The headers are measured on the
+        device (DeviceCodec.decompress_batch_packed_dense_async without an output) and both tables and the measured sizes come to
+        the host, so that decompress() and index() work as for a batch compressed here; an item whose header is refused has
+        length 0 and is refused again by them (a place outside the arena makes tsqa_decompress_batch refuse the call).  To
+        decompress only, DeviceCodec.decompress_packed needs none of this and takes such places too."""
+        n = int(d_sizes.numel())
+        tables = codec._dense_tables(n)
+        codec._join()
+        codec.decompress_batch_packed_dense_async(arena, d_offsets, d_sizes, n, 0, 1, None, *tables)
+        codec._join()
+        torch = codec.torch
+        host = torch.cat([d_offsets[:n], d_sizes[:n], tables[0][1:] - tables[0][:-1]]).cpu().tolist()   # (align 1: the differences are the totals)
+        offsets, sizes, lengths = host[:n], host[n:2 * n], host[2 * n:]
+        return cls(codec, arena, offsets + [max(o + z for o, z in zip(offsets, sizes))], sizes, lengths)
 
     def decompress(self, out=None, item_status: bool = False):
         """The items back, through tsqa_decompress_batch (which decodes again by itself after TSQA_ERR_STALL): a list of views into
@@ -890,6 +929,66 @@ class DeviceCodec:
                                                              self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
+
+    def _join(self) -> None:
+        """Around the asynchronous calls of a synchronous method.  A call given torch's default stream runs on the context's own
+        stream, which does not wait for torch's work and which torch's reads do not wait for: there, wait for the device.  On any
+        other stream the call is enqueued where the caller's work and the reads behind it are."""
+        if self.torch.cuda.current_stream(self.device).cuda_stream == 0:
+            self.torch.cuda.synchronize(self.device)
+
+    def _dense_tables(self, n: int):
+        """-> (d_out_offsets, d_out_sizes, d_first_block, d_item_status) for n items"""
+        i64 = lambda k: self.torch.empty(k, dtype=self.torch.int64, device=self.device)
+        return i64(n + 1), i64(n), i64(n + 1), self.torch.empty(n, dtype=self.torch.int32, device=self.device)
+
+    def decompress_batch_packed_dense_async(self, arena, d_offsets, d_sizes, n_items: int, cap_blocks: int, align: int, out, d_out_offsets,
+                                            d_out_sizes, d_first_block, d_item_status) -> None:
+        """tsqa_decompress_batch_packed_dense_async on the current stream, nothing waited for and nothing about the items taken from
+        the host: the containers' places are read from d_offsets and d_sizes (int64 CUDA tensors, as compress_batch_packed_async left
+        them), their block counts and sizes from their headers on the device, and item i lands at out[d_out_offsets[i]:][:d_out_sizes[i]]
+        (int64 CUDA tensors of n_items + 1 and n_items entries; d_first_block: n_items + 1; d_item_status: int32, n_items).  An
+        item that does not fit out or cap_blocks blocks gets TSQA_ERR_OVERFLOW (6) and the tables say what a retry needs.  out None:
+        measure only.  The largest item status lands in status()."""
+        rc = self.L.tsqa_decompress_batch_packed_dense_async(self.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
+                                                             int(n_items), int(align), int(cap_blocks),
+                                                             out.data_ptr() if out is not None else None, out.numel() if out is not None else 0,
+                                                             d_out_offsets.data_ptr(), d_out_sizes.data_ptr(), d_first_block.data_ptr(),
+                                                             d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def decompress_packed(self, arena, d_offsets, d_sizes, align: int = 16, out=None, item_status: bool = False):
+        """The items of a packed batch known only by its arena and device tables: measure on the device, read the two "needed" words
+        back with one copy, allocate exactly (or check `out`), decode.  -> a list of views into the output arena, item i at
+        round_up(end of item i - 1, align); item_status=True: -> (views, statuses) as PackedBatch.decompress gives them, the view
+        None and the status a TSQA_ERR_* where an item was refused; without it a refused item raises TsqError with .item_status and
+        .results.  An `out` that is too small raises TsqError(6) with .needed = the bytes a retry needs."""
+        torch = self.torch
+        n = int(d_sizes.numel())
+        tables = self._dense_tables(n)
+        self._join()
+        self.decompress_batch_packed_dense_async(arena, d_offsets, d_sizes, n, 0, align, None, *tables)
+        self._join()
+        need_bytes, need_blocks = torch.stack([tables[0][n], tables[2][n]]).cpu().tolist()
+        if out is not None and out.numel() < need_bytes:
+            e = TsqError(6, f"out holds {out.numel()} bytes, the batch needs {need_bytes}")
+            e.needed = need_bytes
+            raise e
+        out = self._out_arena(out, need_bytes)
+        if need_blocks:
+            self.decompress_batch_packed_dense_async(arena, d_offsets, d_sizes, n, need_blocks, align, out, *tables)
+            self._join()
+        host = torch.cat([tables[0][:n], tables[1], tables[3].to(torch.int64)]).cpu().tolist()
+        status = host[2 * n:]
+        views = [out[a:a + z] if st == 0 else None for a, z, st in zip(host[:n], host[n:2 * n], status)]
+        if item_status:
+            return views, status
+        if any(status):
+            e = self._err(max(status))
+            e.item_status, e.results = status, views
+            raise e
+        return views
 
 
 # ---------------------------------------------------------------------------

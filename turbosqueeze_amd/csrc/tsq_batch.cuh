@@ -9,7 +9,8 @@
 namespace tsq {
 
 // One item of a batch as the kernels see it, planned on the host (tsqa_plan_batch): its input and output ranges, relative to the
-// batch's input and output, its first block in the batch and its block count.
+// batch's input and output, its first block in the batch and its block count.  The dense decompress makes the table on the device
+// (batch_measure_kernel, batch_layout_kernel); only there is pad used: 1 marks an item that did not fit the caller's room.
 struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_t n_blocks, pad; };
 
 constexpr uint64_t kNoFrame = ~0ull;      // frame_at of a block whose frame does not fit its item: batch_pack_copy_kernel skips it
@@ -135,6 +136,92 @@ __global__ __launch_bounds__(256) void batch_place_kernel(BatchItem* __restrict_
     const bool ok = n <= arena_size && at <= arena_size - n && n >= kHeaderSize && items[i].n_blocks <= (n - kHeaderSize) / kMinFrameSize;
     items[i].in_at = ok ? at : 0ull;
     items[i].in_len = ok ? n : 0ull;
+}
+
+// First kernel of tsqa_decompress_batch_packed_dense_async, which takes nothing about the items from the host: one lane per item
+// makes the item's descriptor from the 16 header bytes in the arena.  The place is checked as batch_place_kernel checks it and the
+// header with read_header, whose limits are the host planner's (count >= 1, count <= (size - 16) / 6, total <= count * TSQ_BLOCK_SZ);
+// only the header of a well-placed item is read.  An accepted item gets in_at, in_len, n_blocks and out_cap = its total, and status
+// 0; a refused one an empty input range, no blocks and kErrFormat.  out_at and first_block are batch_layout_kernel's.
+__global__ __launch_bounds__(256) void batch_measure_kernel(const uint8_t* __restrict__ in, BatchItem* __restrict__ items, uint32_t n_items,
+                                                            const uint64_t* __restrict__ d_offsets, const uint64_t* __restrict__ d_sizes,
+                                                            uint64_t arena_size, int32_t* __restrict__ item_status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const uint64_t at = d_offsets[i], n = d_sizes[i];
+    uint32_t nb = 0;
+    uint64_t total = 0;
+    const bool ok = n <= arena_size && at <= arena_size - n && n >= kHeaderSize && read_header(in + at, n, &nb, &total) == kHeaderOk;
+    items[i] = ok ? BatchItem{at, n, 0, total, 0, nb, 0u} : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
+    item_status[i] = ok ? kOk : kErrFormat;
+}
+
+constexpr uint64_t kDenseRoomMax = 1ull << 48;  // batch_layout_kernel looks at no more of out_size: sums of fitting items stay far below 2^55
+
+// Behind batch_measure_kernel: the places of a dense output, made from the measured totals and block counts.  ONE workgroup of
+// exactly 256 threads walks the items 256 at a time, as batch_pack_scan_packed_kernel does, with two group_scan_excl64 sums per pass
+// -- block counts, and round_up(total, align): every start is a multiple of align, so the rounding may be done per item -- and
+// carries both between passes.  A refused item counts as no blocks and no bytes.  The public tables follow tsqa_plan_dense and are
+// complete whatever fits:
+//   first_block[i + 1] = first_block[i] + blocks_i;  out_offsets[i + 1] = round_up(out_offsets[i] + total_i, align), the last not rounded.
+// An accepted item fits when first_block[i] + blocks_i <= cap_blocks and out_offsets[i] + total_i <= out_size.  Both sums only grow,
+// so the fitting items are a prefix of the accepted ones, and the kernel holds on to that: the first item that does not fit
+// (first_unfit) ends the prefix whatever the sums behind it say, so the sums that a verdict rests on are sums of items that fit --
+// at most cap_blocks blocks and kDenseRoomMax bytes -- and cannot wrap, whatever the headers claim.  An item that does not fit gets
+// kErrOverflow, an empty input range and no blocks (pad = 1 marks it for batch_overflow_kernel), so nothing of it is read or
+// written.  *live_blocks = the blocks of the fitting prefix: dec_dense_kernel's workgroups at or past it leave at once.
+// status != NULL (the measure-only call, which runs nothing behind this kernel): *status = the largest item status.
+__global__ __launch_bounds__(256) void batch_layout_kernel(BatchItem* __restrict__ items, uint32_t n_items, uint32_t align, uint64_t out_size,
+                                                           uint32_t cap_blocks, uint64_t* __restrict__ d_out_offsets,
+                                                           uint64_t* __restrict__ d_out_sizes, uint64_t* __restrict__ d_first_block,
+                                                           int32_t* __restrict__ item_status, uint32_t* __restrict__ live_blocks,
+                                                           int32_t* __restrict__ status)
+{
+    __shared__ uint64_t wave_sum[4];
+    __shared__ uint32_t first_unfit, live;
+    const uint64_t mask = (uint64_t)align - 1u, room = out_size < kDenseRoomMax ? out_size : kDenseRoomMax;
+    if (threadIdx.x == 0) { first_unfit = ~0u; live = 0u; d_out_offsets[0] = 0; d_first_block[0] = 0; }
+    uint64_t block_base = 0, out_base = 0;
+    for (uint64_t i0 = 0; i0 < n_items; i0 += 256u) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool valid = i < n_items;
+        uint64_t total = 0;
+        uint32_t nb = 0;
+        int32_t st = kOk;
+        if (valid) { nb = items[i].n_blocks; total = items[i].out_cap; st = item_status[i]; }
+        const uint64_t padded = (total + mask) & ~mask;
+        uint64_t sum;
+        const uint64_t first = block_base + group_scan_excl64(nb, wave_sum, &sum);
+        block_base += sum;
+        const uint64_t at = out_base + group_scan_excl64(padded, wave_sum, &sum);
+        out_base += sum;
+        const bool accepted = valid && st == kOk;
+        const bool fits = accepted && first + nb <= cap_blocks && at <= room && total <= room - at;
+        if (accepted && !fits) atomicMin(&first_unfit, (uint32_t)i);
+        __syncthreads();                                     // (no lane leaves the loop early: the scans and this barrier need them all)
+        if (valid) {
+            const bool fit = fits && i < first_unfit, over = accepted && !fit;
+            if (fit) { items[i].out_at = at; items[i].first_block = first; atomicMax(&live, (uint32_t)(first + nb)); }
+            else items[i] = BatchItem{0, 0, 0, 0, 0, 0u, over ? 1u : 0u};
+            if (over) item_status[i] = kErrOverflow;
+            if (status && !fit) atomicMax(status, over ? kErrOverflow : st);
+            d_out_sizes[i] = fit ? total : 0ull;
+            d_out_offsets[i + 1u] = at + (i + 1u == n_items ? total : padded);
+            d_first_block[i + 1u] = first + nb;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *live_blocks = live;
+}
+
+// Behind batch_walk_items_kernel in the dense call: the walk refuses every item with an empty input range as a malformed container,
+// the items that did not fit among them; they get their own verdict back.
+__global__ __launch_bounds__(256) void batch_overflow_kernel(const BatchItem* __restrict__ items, uint32_t n_items, int32_t* __restrict__ item_status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    if (items[i].pad) item_status[i] = kErrOverflow;
 }
 
 // Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.

@@ -359,6 +359,17 @@ __global__ __launch_bounds__(1024) void dec_item_kernel(const uint8_t* __restric
     sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, item_status + owner[blockIdx.x]);
 }
 
+// dec_item_kernel for a batch whose block count is made on the device (tsqa_decompress_batch_packed_dense_async): the launch has as
+// many workgroups as the caller has room for blocks, and those at or past *live_blocks (batch_layout_kernel) leave before they touch
+// a descriptor or an owner.
+__global__ __launch_bounds__(1024) void dec_dense_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                         const uint32_t* __restrict__ owner, uint8_t* __restrict__ outbuf,
+                                                         int32_t* __restrict__ item_status, const uint32_t* __restrict__ live_blocks)
+{
+    if (blockIdx.x >= *live_blocks) return;
+    sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, item_status + owner[blockIdx.x]);
+}
+
 // Range reads (tsqa_decompress_ranges_async): one workgroup per item; nothing outside [out_at, out_at + hi - lo) of `outbuf` is written.
 __global__ __launch_bounds__(1024) void dec_range_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames, uint32_t n_frames,
                                                          const RangeItem* __restrict__ items, uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)

@@ -9,7 +9,7 @@
 
 #include "../../include/turbosqueeze_amd.h"
 
-namespace tsq { struct FrameInfo; }
+namespace tsq { struct FrameInfo; struct BatchItem; }
 
 struct tsqa_ctx;
 
@@ -79,6 +79,9 @@ struct tsqa_ctx {
     uint64_t* batch_sizes = nullptr;
     uint64_t* batch_offsets = nullptr;
     uint8_t* batch_heads = nullptr;
+    // the item table that tsqa_decompress_batch_packed_dense_async makes on the device, and the block count of its fitting items
+    tsq::BatchItem* batch_items = nullptr;
+    uint32_t* batch_live = nullptr;
     size_t cap_batch = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     uint32_t* duo_ring = nullptr;      // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block

@@ -142,7 +142,7 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
     c->range_up.destroy(); c->batch_up.destroy();
     (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
-    (void)hipFree(c->batch_status);
+    (void)hipFree(c->batch_status); (void)hipFree(c->batch_items); (void)hipFree(c->batch_live);
     delete c;
 }
 
@@ -256,13 +256,17 @@ int tsqa_ctx::reserve_batch(size_t n_items)
     // (batch calls run on callers' streams too, and one enqueued there may still be using the tables that are freed below)
     (void)hipDeviceSynchronize();
     (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_offsets); (void)hipFree(batch_heads); (void)hipFree(batch_status);
+    (void)hipFree(batch_items); (void)hipFree(batch_live);
     batch_at = nullptr; batch_sizes = nullptr; batch_offsets = nullptr; batch_heads = nullptr; batch_status = nullptr; cap_batch = 0;
+    batch_items = nullptr; batch_live = nullptr;
     size_t want = 256; while (want < n_items) want *= 2;
     TSQ_HIP(this, hipMalloc(&batch_at, want * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_sizes, want * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_offsets, (want + 1) * sizeof(uint64_t)));
     TSQ_HIP(this, hipMalloc(&batch_heads, want * kHeaderSize));
     TSQ_HIP(this, hipMalloc(&batch_status, want * sizeof(int32_t)));
+    TSQ_HIP(this, hipMalloc(&batch_items, want * sizeof(BatchItem)));
+    TSQ_HIP(this, hipMalloc(&batch_live, sizeof(uint32_t)));
     cap_batch = want;
     return TSQA_OK;
 }
@@ -1333,6 +1337,75 @@ extern "C" int tsqa_decompress_batch_packed_items_async(tsqa_ctx* c, const void*
     hipStream_t s = stream_of(c, hip_stream);
     return decompress_batch_items_async_impl(c, d_arena, arena_size, items, n_blocks, n_items, d_out, out_size, d_out_sizes, d_item_status,
                                              d_status, s, d_offsets, d_sizes);
+}
+
+// ---- dense decompress of a packed batch: block counts and output places made on the device from the headers ----
+
+extern "C" int tsqa_plan_dense(const uint64_t* totals, const uint32_t* blocks, uint32_t n_items, uint32_t align, uint64_t out_size,
+                               uint32_t cap_blocks, uint64_t* out_offsets, uint64_t* first_block, uint32_t* n_fit)
+{
+    if (!totals || !blocks || !out_offsets || !first_block || !n_fit || n_items == 0 || !packed_align_ok(align)) return TSQA_ERR_ARG;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t at = 0, fb = 0;
+    uint32_t fit = n_items;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const uint64_t nb = blocks[i], total = nb ? totals[i] : 0;           // (an item refused at its header: no blocks, no bytes)
+        out_offsets[i] = at; first_block[i] = fb;
+        if (nb && fit == n_items && (fb + nb > cap_blocks || at > out_size || total > out_size - at)) fit = i;
+        fb += nb;
+        at += total;
+        if (i + 1 < n_items) at = (at + mask) & ~mask;
+    }
+    out_offsets[n_items] = at; first_block[n_items] = fb;
+    *n_fit = fit;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_decompress_batch_packed_dense_async(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets,
+                                                        const uint64_t* d_sizes, uint32_t n_items, uint32_t align, uint32_t cap_blocks,
+                                                        void* d_out, size_t out_size, uint64_t* d_out_offsets, uint64_t* d_out_sizes,
+                                                        uint64_t* d_first_block, int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_arena || !d_offsets || !d_sizes || !d_out_offsets || !d_out_sizes || !d_first_block || !d_item_status || !d_status) {
+        c->set_error("decompress_batch_packed_dense: null pointer");
+        return TSQA_ERR_ARG;
+    }
+    if (n_items == 0) { c->set_error("decompress_batch_packed_dense: no items"); return TSQA_ERR_ARG; }
+    if (!packed_align_ok(align)) { c->set_error("decompress_batch_packed_dense: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
+    if (d_out ? (out_size == 0 || cap_blocks == 0) : out_size != 0) {
+        c->set_error("decompress_batch_packed_dense: an output needs out_size and cap_blocks above 0; measuring takes d_out NULL and out_size 0");
+        return TSQA_ERR_ARG;
+    }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    if (d_out) {
+        if (int rc = c->reserve(cap_blocks, false, false, true)) return rc;
+        c->forget_sharded();                             // the frame walk below overwrites c->frames
+    }
+    const uint8_t* const in = static_cast<const uint8_t*>(d_arena);
+    const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(batch_measure_kernel, per_item, dim3(256), 0, s, in, c->batch_items, n_items, d_offsets, d_sizes, (uint64_t)arena_size,
+                       d_item_status);
+    // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts.  Measuring: nothing fits, and the kernel
+    //  closes the batch's word itself)
+    hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, (uint64_t)out_size, d_out ? cap_blocks : 0u,
+                       d_out_offsets, d_out_sizes, d_first_block, d_item_status, c->batch_live, d_out ? nullptr : d_status);
+    if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
+    hipLaunchKernelGGL(batch_walk_items_kernel, per_item, dim3(256), 0, s, in, static_cast<const BatchItem*>(c->batch_items), n_items, c->frames,
+                       c->block_owner, d_out_sizes, d_item_status);
+    hipLaunchKernelGGL(batch_overflow_kernel, per_item, dim3(256), 0, s, static_cast<const BatchItem*>(c->batch_items), n_items, d_item_status);
+    ProfSpan span(c, 1, s);
+    const int rc = launch_read_kernel<dec_dense_kernel>(c, cap_blocks, s, in, static_cast<const FrameInfo*>(c->frames),
+                                                        static_cast<const uint32_t*>(c->block_owner), static_cast<uint8_t*>(d_out), d_item_status,
+                                                        static_cast<const uint32_t*>(c->batch_live));
+    if (rc) span.cancel(); else span.end();
+    hipLaunchKernelGGL(batch_close_items_kernel, per_item, dim3(256), 0, s, n_items, static_cast<const int32_t*>(d_item_status), d_out_sizes, d_status);
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
 }
 
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
