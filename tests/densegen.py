@@ -9,7 +9,7 @@ What is restated from the library, and must be re-derived when it changes there:
   layout       batch_layout_kernel and tsqa_plan_dense: tsqa_plan_packed's rule on the totals, the block sum, the fitting prefix
   GROUP, WAVE  batch_layout_kernel is ONE workgroup of 256 threads (four wavefronts of 64) that takes the items 256 at a time
   SPLIT        group_scan_excl64 sums v & 0xFFFFFF and v >> 24 apart
-  walk verdicts   faultgen.walk_refuses (batch_walk_items_kernel)
+  walk verdicts   faultgen.walk_refuses (batch_walk_kernel<kWalkPerItem>)
 """
 from __future__ import annotations
 

@@ -18,8 +18,9 @@ decodes to another length than the header states), except for the two tight item
 must refuse for the room they are given.
 
 What is restated from the library, and must be re-derived when it changes there:
-  walk_refuses        batch_walk_kernel / frame_walk_kernel (tsq_batch.cuh, tsq_container.cuh) with read_header and read_frame
-                      (tsq_format.h): which items the frame walk refuses (TSQA_ERR_FORMAT, nothing written to their range) as
+  walk_refuses        batch_walk_kernel / frame_walk_kernel (tsq_batch.cuh, tsq_container.cuh) with read_header and walk_frames
+                      (tsq_format.h, the one frame walk of host and device; test_batch_faults_cpu.py holds it against this
+                      restatement): which items the frame walk refuses (TSQA_ERR_FORMAT, nothing written to their range) as
                       opposed to a block decoder (TSQA_ERR_STREAM, the range undefined)
   stated_count, MIN_ITEM   plan_batch (tsq_runtime.hip): an item is at least a header long and states a block count from 1 to
                       (in_len - 16) / 6, or the whole call is refused.  A container cut inside its header therefore travels padded
@@ -61,7 +62,7 @@ def stated_count(blob) -> int:
 
 
 def walk_refuses(blob, n_blocks: int, cap: int) -> bool:
-    """RE-DERIVE with batch_walk_kernel: the header (magic, a count and a total the container can hold), the count against the
+    """RE-DERIVE with batch_walk_kernel and walk_frames (tsq_format.h): the header (magic, a count and a total the container can hold), the count against the
     caller's, the total against the capacity, every frame (a stream of 3 .. TSQ_OUTPUT_SZ bytes inside the container, a block of at
     most 4 MiB, output that stays inside the total), and block sizes that add up to the total."""
     n = len(blob)

@@ -1,11 +1,14 @@
 """No GPU: the seeded batch of tests/faultgen.py reaches what test_gpu_batch_faults.py needs of it.  Every verdict here is the
 oracle's; the generator's restatement of the frame walk is held against the oracle where the two can be compared."""
 import collections
+import ctypes as C
 
+import numpy as np
 import pytest
 
 import faultgen as fg
 import mtgen
+import turbosqueeze_amd as tsq
 
 
 @pytest.fixture(scope="module")
@@ -89,3 +92,27 @@ def test_bad_places(batch):
         n, at = sz2[i], off2[i]
         assert n > arena.size or at > arena.size - n or n < fg.HEADER or batch[i].n_blocks > (n - fg.HEADER) // fg.MIN_FRAME, what
     assert [i for i in range(len(batch)) if (off2[i], sz2[i]) != (offsets[i], sizes[i])] == sorted(bad)
+
+
+def test_the_host_walk_refuses_what_the_restated_walk_refuses(batch):
+    """tsqa_walk_frames (the library's one frame walk, on the host) over every item as it travels, with the count and the total
+    its own header states and no capacity: TSQA_ERR_FORMAT exactly where faultgen.walk_refuses says so, the header's total elsewhere"""
+    L = tsq.lib()
+    refused = []
+    for it in batch:
+        _, nb, total = fg.header_of(it.blob)
+        cap = max(len(it.blob) // 6, 1)
+        frame_at = np.zeros(cap, dtype=np.uint64)
+        sizes, ext, out_len = (np.zeros(cap, dtype=np.uint32) for _ in range(3))
+        got_nb, got_total = C.c_uint32(0), C.c_uint64(0)
+        rc = L.tsqa_walk_frames(it.blob, len(it.blob), cap, frame_at.ctypes.data, sizes.ctypes.data, ext.ctypes.data, out_len.ctypes.data,
+                                C.byref(got_nb), C.byref(got_total))
+        want = fg.walk_refuses(it.blob, nb, total)
+        assert rc == (fg.ERR_FORMAT if want else fg.OK), it.name
+        if want:
+            refused.append(it.name)
+        else:
+            assert got_total.value == total and got_nb.value == nb, it.name
+    assert len(refused) == 11 and len(batch) - len(refused) == 290
+    # (the two tight items are healthy containers: only a capacity refuses them)
+    assert sorted(refused) == sorted(it.name for it in batch if it.by_walk and it.klass != "tight")

@@ -311,3 +311,42 @@ def test_python_packed_batch_gives_item_statuses(codec, tsq, faults):
             assert v.cpu().numpy().tobytes() == it.want, it.name
     with pytest.raises(tsq.TsqError):
         pb.decompress()
+
+
+def test_batch_index_walks_every_item_without_a_capacity(codec, faults):
+    """tsqa_index_create_batch over the arena: the frame walk with the count each header states and no capacity refuses what
+    faultgen.walk_refuses refuses with those arguments, item for item, and indexes every other item"""
+    items, n = faults.items, len(faults.items)
+    heads = [fg.header_of(it.blob) for it in items]
+    refused = [fg.walk_refuses(it.blob, nb, total) for it, (_, nb, total) in zip(items, heads)]
+    assert sum(refused) == 11
+    h = C.c_void_p()
+    verdicts = (C.c_int32 * n)(*([-1] * n))
+    rc = codec.L.tsqa_index_create_batch(codec.h, faults.d_in.data_ptr(), faults.d_in.numel(),
+                                         _batch_array([(a, len(it.blob), 0, 0) for a, it in zip(faults.in_ats, items)]), n, C.byref(h), verdicts)
+    try:
+        assert rc == ERR_FORMAT and h, codec.last_error()
+        assert list(verdicts) == [ERR_FORMAT if r else OK for r in refused]
+        assert [int(codec.L.tsqa_index_item_total(h, i)) for i in range(n)] == [0 if r else total for r, (_, _, total) in zip(refused, heads)]
+        assert int(codec.L.tsqa_index_blocks(h)) == sum(nb for r, (_, nb, _) in zip(refused, heads) if not r)
+    finally:
+        codec.L.tsqa_index_destroy(h)
+
+
+def test_one_word_form_refuses_what_the_walk_refuses(codec, faults):
+    """every item that the frame walk refuses, the two that only their capacity refuses among them, between its two healthy
+    neighbours through tsqa_decompress_batch_async: the batch's word, no size, and nothing written to its range.  (Nothing is
+    asserted about the neighbours' bytes: the one-word form promises none after a refusal.)"""
+    import torch
+    walked = [k for k, it in enumerate(faults.items) if it.by_walk]
+    assert len(walked) == 13 and sum(faults.items[k].klass == "tight" for k in walked) == 2
+    for k in walked:
+        sub = faults.sub(k - 1, k + 2, 100 + k)
+        before, it, after = sub.items
+        out, d_sizes, _ = sub.fresh()
+        codec.decompress_batch_async(faults.d_in, sub.quads, sub.blocks, out, d_sizes)
+        torch.cuda.synchronize()
+        assert codec.status() == ERR_FORMAT, it.name
+        assert d_sizes.cpu().tolist() == [len(before.want), 0, len(after.want)], it.name
+        o = sub.outs[1]
+        assert np.array_equal(out[o:o + it.cap].cpu().numpy(), sub.guard[o:o + it.cap]), it.name

@@ -10,15 +10,39 @@ namespace tsq {
 
 // One item of a batch as the kernels see it, planned on the host (tsqa_plan_batch): its input and output ranges, relative to the
 // batch's input and output, its first block in the batch and its block count.  The dense decompress makes the table on the device
-// (batch_measure_kernel, batch_layout_kernel); only there is pad used: 1 marks an item that did not fit the caller's room.
-struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_t n_blocks, pad; };
+// (batch_measure_kernel, batch_layout_kernel); only there is unfit used: 1 marks an item that did not fit the caller's room.
+struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_t n_blocks, unfit; };
 
 constexpr uint64_t kNoFrame = ~0ull;      // frame_at of a block whose frame does not fit its item: batch_pack_copy_kernel skips it
 
-// After an encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0): one lane per item with blocks in the launch,
-// items [i0, i0 + ni).  An item's frame offsets run on from where its previous launch left them (run_at[i]); its header goes out
-// with its first block, its size and the capacity check with its last.  A frame is written only if it ends inside the item's
-// capacity: frame_at[b - b0] is its offset in the output, or kNoFrame.
+// The frames of item `it` in the encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0), for both pack scans.
+// The item's frame offsets run on from where its previous launch left them (*run_at; the caller stores what this returns), and its
+// header goes out with its first block.  write: the item's container starts at out + start, and a header or frame is written only
+// if it ends at or before out + limit: frame_at[b - b0] is the frame's offset in `out`, or kNoFrame.  !write: sizing only.
+__device__ __forceinline__ uint64_t batch_item_frames(const BatchItem& it, const uint64_t* run_at, uint64_t b0, uint32_t nb,
+                                                     const uint32_t* __restrict__ sizes, uint32_t ext, bool write, uint8_t* out,
+                                                     uint64_t start, uint64_t limit, uint64_t* frame_at)
+{
+    const uint64_t first = it.first_block, end = first + it.n_blocks, launch_end = b0 + nb;
+    const bool begins = first >= b0;
+    if (write && begins && start + kHeaderSize <= limit) write_header(out + start, it.n_blocks, it.in_len);
+    uint64_t at = begins ? kHeaderSize : *run_at;
+    for (uint64_t b = begins ? first : b0; b < end && b < launch_end; ++b) {
+        const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
+        const uint64_t next = at + kFrameWordSize + sz;
+        if (write) {
+            const bool fits = start + next <= limit;
+            if (fits) write_frame(out + start + at, sz, ext);
+            frame_at[k] = fits ? start + at : kNoFrame;
+        }
+        at = next;
+    }
+    return at;
+}
+
+// After an encode launch of the batch's blocks [b0, b0 + nb): one lane per item with blocks in the launch, items [i0, i0 + ni),
+// writes the item's frames into the caller's range for it (batch_item_frames; the planner has left room for the header and a minimal
+// frame per block: out_cap >= 16 + 6 * n_blocks).  The item's size and the capacity check go out with its last block.
 __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* __restrict__ items, uint32_t i0, uint32_t ni, uint64_t b0,
                                                               uint32_t nb, const uint32_t* __restrict__ sizes, uint32_t ext,
                                                               uint8_t* __restrict__ out, uint64_t* __restrict__ run_at,
@@ -29,40 +53,12 @@ __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* _
     if (j >= ni) return;
     const uint32_t i = i0 + j;
     const BatchItem it = items[i];
-    const uint64_t first = it.first_block, end = first + it.n_blocks, launch_end = b0 + nb;
-    uint8_t* const base = out + it.out_at;
-    // (the planner has left room for the header and a minimal frame per block: out_cap >= 16 + 6 * n_blocks)
-    if (first >= b0) write_header(base, it.n_blocks, it.in_len);
-    uint64_t at = first >= b0 ? kHeaderSize : run_at[i];
-    for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) {
-        const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
-        const uint64_t next = at + kFrameWordSize + sz;
-        if (next <= it.out_cap) { write_frame(base + at, sz, ext); frame_at[k] = it.out_at + at; }
-        else frame_at[k] = kNoFrame;
-        at = next;
-    }
+    const uint64_t at = batch_item_frames(it, run_at + i, b0, nb, sizes, ext, true, out, it.out_at, it.out_at + it.out_cap, frame_at);
     run_at[i] = at;
-    if (end <= launch_end) {
+    if (it.first_block + it.n_blocks <= b0 + nb) {
         d_sizes[i] = at;
         if (at > it.out_cap) atomicMax(status, kErrOverflow);
     }
-}
-
-// Exclusive sum of v over the 256 threads of a workgroup, for sums below 2^55 (a batch has at most 2^32 - 1 blocks, so every sum of
-// container sizes is): two 32-bit DPP scans per wavefront, of the low 24 bits and of the rest, then the four wavefront totals through
-// LDS.  *total = the workgroup's sum.  Every thread of the workgroup calls it (the DPP steps read the neighbouring lanes): the
-// workgroup is exactly 256 threads, four full wavefronts, and wave_scan_add is an inclusive sum over 64 active lanes.
-__device__ __forceinline__ uint64_t group_scan_excl64(uint64_t v, uint64_t* wave_sum /* LDS, 4 */, uint64_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint64_t incl = ((uint64_t)wave_scan_add((uint32_t)(v >> 24)) << 24) + wave_scan_add((uint32_t)v & 0xFFFFFFu);
-    __syncthreads();                                         // (the previous call's totals have been read)
-    if (lane == 63u) wave_sum[wid] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < 4u; ++w) { const uint64_t s = wave_sum[w]; if (w < wid) before += s; all += s; }
-    *total = all;
-    return before + incl - v;
 }
 
 // batch_pack_scan_kernel for a packed batch (tsqa_compress_batch_packed*): the items' places are made here, not taken from the
@@ -71,9 +67,9 @@ __device__ __forceinline__ uint64_t group_scan_excl64(uint64_t v, uint64_t* wave
 // but the last is complete in it, so their starts are offsets[i0] + an exclusive sum of round_up(size, align) over the launch's
 // items (offsets[i] is a multiple of align, so the rounding may be done per item).  offsets[] is the carry between launches: the
 // first launch writes offsets[0] = 0, an item that a launch completes writes its successor's start, and the next launch reads
-// offsets[i0] whether its first item continues (its start) or begins there (what the last complete item left).  An item that
-// continues keeps its running frame offset in run_at[i], as in batch_pack_scan_kernel.  A header or frame is written only if it ends
-// inside out_size; sizes[] and offsets[] are complete whatever fits.
+// offsets[i0] whether its first item continues (its start) or begins there (what the last complete item left).  Each item is sized
+// first (batch_item_frames without writing), and written once the scan has made its start; a header or frame is written only if it
+// ends inside out_size; sizes[] and offsets[] are complete whatever fits.
 __global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0,
                                                                      uint32_t ni, uint64_t b0, uint32_t nb,
                                                                      const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
@@ -83,35 +79,21 @@ __global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const Batch
                                                                      int32_t* __restrict__ status)
 {
     __shared__ uint64_t wave_sum[4];
-    const uint64_t launch_end = b0 + nb, mask = (uint64_t)align - 1u;
+    const uint64_t mask = (uint64_t)align - 1u;
     uint64_t base = b0 == 0 ? 0ull : d_offsets[i0];          // where the launch's first item starts
     if (b0 == 0 && threadIdx.x == 0) d_offsets[0] = 0;
     for (uint32_t j0 = 0; j0 < ni; j0 += 256u) {
         const uint32_t j = j0 + threadIdx.x, i = i0 + (j < ni ? j : 0u);
         const bool valid = j < ni;
-        uint64_t first = 0, end = 0, at0 = 0, at = 0, in_len = 0;
-        uint32_t n_blocks = 0;
-        if (valid) {
-            const BatchItem it = items[i];
-            first = it.first_block; end = first + it.n_blocks; in_len = it.in_len; n_blocks = it.n_blocks;
-            at0 = at = first >= b0 ? kHeaderSize : run_at[i];
-            for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) at += kFrameWordSize + sizes[(uint32_t)(b - b0)];
-        }
-        const bool complete = valid && end <= launch_end;    // (only the launch's last item can be incomplete: it adds nothing)
+        const BatchItem it = valid ? items[i] : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
+        const uint64_t at = valid ? batch_item_frames(it, run_at + i, b0, nb, sizes, ext, false, nullptr, 0, 0, nullptr) : 0ull;
+        const bool complete = valid && it.first_block + it.n_blocks <= b0 + nb;   // (only the launch's last item can be incomplete: it adds nothing)
         uint64_t total;
         const uint64_t start = base + group_scan_excl64(complete ? (at + mask) & ~mask : 0ull, wave_sum, &total);
         base += total;
         if (valid) {                                         // (no lane leaves the loop early: the scan above needs them all)
-            if (first >= b0 && start + kHeaderSize <= out_size) write_header(out + start, n_blocks, in_len);
-            uint64_t w = at0;
-            for (uint64_t b = first > b0 ? first : b0; b < end && b < launch_end; ++b) {
-                const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
-                const uint64_t next = w + kFrameWordSize + sz;
-                if (start + next <= out_size) { write_frame(out + start + w, sz, ext); frame_at[k] = start + w; }
-                else frame_at[k] = kNoFrame;
-                w = next;
-            }
-            run_at[i] = at;
+            batch_item_frames(it, run_at + i, b0, nb, sizes, ext, true, out, start, out_size, frame_at);
+            run_at[i] = at;                                  // (only now: the writing pass has read the carry that the sizing pass read)
         }
         if (complete) {
             const bool last = i + 1u == n_items;
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const Batch
     }
 }
 
-// Before batch_walk_kernel in tsqa_decompress_batch_packed_async: one lane per item takes its container's place from tables in
+// Before batch_walk_kernel in the packed decompress calls: one lane per item takes its container's place from tables in
 // device memory (what batch_pack_scan_packed_kernel wrote, or anything else: they are not trusted).  A place that does not lie
 // inside the arena, or that is too short for a header or for the item's block count, becomes an empty input range, which
 // batch_walk_kernel refuses (kErrFormat, d_sizes[i] = 0) without reading a byte of it.
@@ -169,8 +151,8 @@ constexpr uint64_t kDenseRoomMax = 1ull << 48;  // batch_layout_kernel looks at 
 // so the fitting items are a prefix of the accepted ones, and the kernel holds on to that: the first item that does not fit
 // (first_unfit) ends the prefix whatever the sums behind it say, so the sums that a verdict rests on are sums of items that fit --
 // at most cap_blocks blocks and kDenseRoomMax bytes -- and cannot wrap, whatever the headers claim.  An item that does not fit gets
-// kErrOverflow, an empty input range and no blocks (pad = 1 marks it for batch_overflow_kernel), so nothing of it is read or
-// written.  *live_blocks = the blocks of the fitting prefix: dec_dense_kernel's workgroups at or past it leave at once.
+// kErrOverflow, an empty input range and no blocks (unfit = 1 keeps that verdict through the walk), so nothing of it is read or
+// written.  *live_blocks = the blocks of the fitting prefix: dec_item_kernel's workgroups at or past it leave at once.
 // status != NULL (the measure-only call, which runs nothing behind this kernel): *status = the largest item status.
 __global__ __launch_bounds__(256) void batch_layout_kernel(BatchItem* __restrict__ items, uint32_t n_items, uint32_t align, uint64_t out_size,
                                                            uint32_t cap_blocks, uint64_t* __restrict__ d_out_offsets,
@@ -215,15 +197,6 @@ __global__ __launch_bounds__(256) void batch_layout_kernel(BatchItem* __restrict
     if (threadIdx.x == 0) *live_blocks = live;
 }
 
-// Behind batch_walk_items_kernel in the dense call: the walk refuses every item with an empty input range as a malformed container,
-// the items that did not fit among them; they get their own verdict back.
-__global__ __launch_bounds__(256) void batch_overflow_kernel(const BatchItem* __restrict__ items, uint32_t n_items, int32_t* __restrict__ item_status)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_items) return;
-    if (items[i].pad) item_status[i] = kErrOverflow;
-}
-
 // Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.
 // grid = (pieces, blocks of the launch).
 __global__ __launch_bounds__(256) void batch_pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,
@@ -237,75 +210,53 @@ __global__ __launch_bounds__(256) void batch_pack_copy_kernel(const uint8_t* __r
     pack_copy_piece(slots + (size_t)b * kSlotSize, size, out + at + kFrameWordSize, piece_at);
 }
 
-// One lane per item of a decompress batch: the item's container is walked and validated as frame_walk_kernel walks one (the
-// header, its block count against the caller's, its total against the item's capacity, every frame, lengths that add up to the
-// total).  Frame k of item i lands at frames[first_block_i + k], stream_at relative to the batch's input, out_at to its output.
-// A refused item gets d_sizes[i] = 0, *status kErrFormat, and descriptors with no stream, which every decoder refuses.
+constexpr uint64_t kItemRefused = ~0ull;  // sizes[i] of an item whose container batch_walk_kernel<kWalkIndex> refuses
+
+// What batch_walk_kernel checks besides the walk, and where a refusal goes:
+//   kWalkOneWord  tsqa_decompress_batch_async: the total against the item's capacity; *status = kErrFormat, sizes[i] = 0.
+//   kWalkPerItem  tsqa_decompress_batch_items_async and the dense call: the same checks; status[i] = kErrFormat, or kErrOverflow for
+//                 an item that batch_layout_kernel found no room for (unfit, an empty input range); sizes[i] = 0.  Every block of
+//                 every item learns its owner first: owner[first_block_i + k] = i, for a refused item too -- its workgroups are
+//                 launched like the others and find their item's word through the table in order to leave (dec_item_kernel).
+//                 status[] is zero before the kernel runs, apart from the verdicts of the dense call's own kernels, which it repeats.
+//   kWalkIndex    tsqa_index_create_batch: no capacity; n_blocks is the count the item's header states (0: the host has refused the
+//                 header already); sizes[i] = kItemRefused (its descriptors are then not to be used), status is not used.
+enum BatchWalkMode : int { kWalkOneWord, kWalkPerItem, kWalkIndex };
+
+// One lane per item of a batch: the item's container is walked and validated as frame_walk_kernel walks one (the header, its block
+// count against the caller's -- a count of 0 is refused in every mode, as no header states it --, the mode's checks, walk_frames).
+// Frame k of item i lands at frames[first_block_i + k], stream_at relative to the batch's input, out_at to its output (kWalkIndex:
+// the item's out_at is its start in the concatenation of the items' data).  sizes[i] = the item's total when it passes; a refused
+// item gets the mode's verdict and descriptors with no stream, which every decoder refuses.
+template <BatchWalkMode M>
 __global__ __launch_bounds__(256) void batch_walk_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
-                                                         FrameInfo* __restrict__ frames, uint64_t* __restrict__ d_sizes,
-                                                         int32_t* __restrict__ status)
+                                                         FrameInfo* __restrict__ frames, uint32_t* __restrict__ owner,
+                                                         uint64_t* __restrict__ sizes, int32_t* __restrict__ status)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_items) return;
     const BatchItem it = items[i];
     const uint8_t* const c = in + it.in_at;
-    const uint64_t n = it.in_len;
     FrameInfo* const fr = frames + it.first_block;
+    if constexpr (M == kWalkPerItem) for (uint32_t b = 0; b < it.n_blocks; ++b) owner[it.first_block + b] = i;
     uint32_t nb = 0;
-    uint64_t total = 0, at = kHeaderSize, oat = 0;
-    bool bad = read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks || total > it.out_cap;
-    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
-        FrameInfo f;
-        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
-        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
-        fr[b] = f;
-        oat += f.out_len;
-        at += kFrameWordSize + f.stream_len;
-    }
-    if (!bad && oat != total) bad = true;
-    d_sizes[i] = bad ? 0 : total;
-    if (!bad) return;
+    uint64_t total = 0;
+    const bool ok = it.n_blocks != 0u && read_header(c, it.in_len, &nb, &total) == kHeaderOk && nb == it.n_blocks &&
+                    (M == kWalkIndex || total <= it.out_cap) &&
+                    walk_frames(c, it.in_len, nb, total, [&](uint32_t b, uint64_t, FrameInfo f) {
+                        f.stream_at += it.in_at; f.out_at += it.out_at;
+                        fr[b] = f;
+                        return true;
+                    }) == kWalkOk;
+    sizes[i] = ok ? total : M == kWalkIndex ? kItemRefused : 0ull;
+    if (ok) return;
     for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
-    atomicMax(status, kErrFormat);
+    if constexpr (M == kWalkOneWord) atomicMax(status, kErrFormat);
+    if constexpr (M == kWalkPerItem) status[i] = it.unfit ? kErrOverflow : kErrFormat;
 }
 
-// batch_walk_kernel with a verdict per item (tsqa_decompress_batch_items_async): the same walk and the same validation, but a
-// refusal goes to item_status[i] (kErrFormat) and not to a word of the batch, and every block of every item learns its owner:
-// owner[first_block_i + k] = i, for a refused item too -- its workgroups are launched like the others and find their item's word
-// through the table in order to leave (dec_item_kernel).  d_sizes[i] = the item's total, 0 when it is refused here; the closing
-// kernel clears it for an item that a decoder refuses.  item_status is zero before this kernel runs and nothing else writes it yet.
-__global__ __launch_bounds__(256) void batch_walk_items_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items,
-                                                               uint32_t n_items, FrameInfo* __restrict__ frames, uint32_t* __restrict__ owner,
-                                                               uint64_t* __restrict__ d_sizes, int32_t* __restrict__ item_status)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_items) return;
-    const BatchItem it = items[i];
-    const uint8_t* const c = in + it.in_at;
-    const uint64_t n = it.in_len;
-    FrameInfo* const fr = frames + it.first_block;
-    uint32_t* const own = owner + it.first_block;
-    for (uint32_t b = 0; b < it.n_blocks; ++b) own[b] = i;
-    uint32_t nb = 0;
-    uint64_t total = 0, at = kHeaderSize, oat = 0;
-    bool bad = read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks || total > it.out_cap;
-    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
-        FrameInfo f;
-        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
-        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
-        fr[b] = f;
-        oat += f.out_len;
-        at += kFrameWordSize + f.stream_len;
-    }
-    if (!bad && oat != total) bad = true;
-    d_sizes[i] = bad ? 0 : total;
-    if (!bad) return;
-    for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
-    item_status[i] = kErrFormat;
-}
-
-// Behind the decode of tsqa_decompress_batch_items_async, one lane per item: an item that the walk or a decoder refused gives no
-// size, and the batch's word is the largest item status.  No other kernel of that path writes *status.
+// Behind the decode with a verdict per item, one lane per item: an item that the walk or a decoder refused gives no size, and the
+// batch's word is the largest item status.  No other kernel of that path writes *status.
 __global__ __launch_bounds__(256) void batch_close_items_kernel(uint32_t n_items, const int32_t* __restrict__ item_status,
                                                                 uint64_t* __restrict__ d_sizes, int32_t* __restrict__ status)
 {
@@ -315,38 +266,6 @@ __global__ __launch_bounds__(256) void batch_close_items_kernel(uint32_t n_items
     if (st == 0) return;
     d_sizes[i] = 0;
     atomicMax(status, st);
-}
-
-constexpr uint64_t kItemRefused = ~0ull;  // verdicts[i] of an item whose container batch_index_walk_kernel refuses
-
-// One lane per item of a batch index (tsqa_index_create_batch): batch_walk_kernel's walk with a verdict per item instead of one
-// for the batch, and no capacity.  n_blocks is the count the item's header states (0: the host has refused the header already);
-// frame k of item i lands at frames[first_block_i + k], stream_at relative to the batch's input, out_at = the item's out_at (its
-// start in the concatenation of the items' data) + the block's start in the item.  verdicts[i] = the item's total, or kItemRefused
-// (its descriptors are then not to be used).
-__global__ __launch_bounds__(256) void batch_index_walk_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
-                                                               FrameInfo* __restrict__ frames, uint64_t* __restrict__ verdicts)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_items) return;
-    const BatchItem it = items[i];
-    const uint8_t* const c = in + it.in_at;
-    const uint64_t n = it.in_len;
-    FrameInfo* const fr = frames + it.first_block;
-    uint32_t nb = 0;
-    uint64_t total = 0, at = kHeaderSize, oat = 0;
-    bool bad = it.n_blocks == 0u || read_header(c, n, &nb, &total) != kHeaderOk || nb != it.n_blocks;
-    for (uint32_t b = 0; b < it.n_blocks && !bad; ++b) {
-        FrameInfo f;
-        if (at + kMinFrameSize > n || !read_frame(c + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
-        f.stream_at = it.in_at + at + kFrameWordSize; f.out_at = it.out_at + oat;
-        fr[b] = f;
-        oat += f.out_len;
-        at += kFrameWordSize + f.stream_len;
-    }
-    if (!bad && oat != total) bad = true;
-    verdicts[i] = bad ? kItemRefused : total;
-    if (bad) for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
 }
 
 // The first 16 bytes of every item's container, zeros past a short one: the synchronous batch decompress reads every header with

@@ -6,36 +6,40 @@
 
 namespace tsq {
 
-// One workgroup: exclusive scan of (3 + size_b), header + frame bytes, total size.
-// Replaces compression_write_worker's serial frame emission (tsq_threads.cpp:192-275).
+// Exclusive sum of v over the 256 threads of a workgroup, for sums below 2^55 (a batch has at most 2^32 - 1 blocks, so every sum of
+// container sizes is): two 32-bit DPP scans per wavefront, of the low 24 bits and of the rest, then the four wavefront totals through
+// LDS.  *total = the workgroup's sum.  Every thread of the workgroup calls it (the DPP steps read the neighbouring lanes): the
+// workgroup is exactly 256 threads, four full wavefronts, and wave_scan_add is an inclusive sum over 64 active lanes.
+__device__ __forceinline__ uint64_t group_scan_excl64(uint64_t v, uint64_t* wave_sum /* LDS, 4 */, uint64_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint64_t incl = ((uint64_t)wave_scan_add((uint32_t)(v >> 24)) << 24) + wave_scan_add((uint32_t)v & 0xFFFFFFu);
+    __syncthreads();                                         // (the previous call's totals have been read)
+    if (lane == 63u) wave_sum[wid] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (uint32_t w = 0; w < 4u; ++w) { const uint64_t s = wave_sum[w]; if (w < wid) before += s; all += s; }
+    *total = all;
+    return before + incl - v;
+}
+
+// One workgroup of exactly 256 threads: exclusive scan of (3 + size_b), 256 blocks per pass with the running sum carried in a
+// register; header + frame bytes, total size.  Replaces compression_write_worker's serial frame emission (tsq_threads.cpp:192-275).
 __global__ __launch_bounds__(256) void pack_scan_kernel(const uint32_t* __restrict__ sizes, uint32_t n_blocks,
                                                         uint64_t n_total, uint32_t ext, uint8_t* __restrict__ container,
                                                         uint64_t out_cap, uint64_t* __restrict__ frame_at,
                                                         uint64_t* __restrict__ out_size, int32_t* __restrict__ status)
 {
     __shared__ uint64_t wave_sum[4];
-    __shared__ uint64_t carry;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
-    if (t == 0) carry = kHeaderSize;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_blocks; base += 256) {
-        uint32_t b = base + t;
-        uint64_t v = b < n_blocks ? kFrameWordSize + (uint64_t)sizes[b] : 0ull;
-        uint64_t incl = v;                                   // inclusive wave scan
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            uint64_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wid] = incl;
-        __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t w = 0; w < wid; ++w) before += wave_sum[w];
-        if (b < n_blocks) frame_at[b] = before + incl - v;
-        __syncthreads();
-        if (t == 255) carry = before + incl;
-        __syncthreads();
+    const uint32_t t = threadIdx.x;
+    uint64_t total = kHeaderSize;
+    for (uint32_t base = 0; base < n_blocks; base += 256) {  // (no thread leaves the loop early: the scan needs them all)
+        const uint32_t b = base + t;
+        uint64_t sum;
+        const uint64_t at = total + group_scan_excl64(b < n_blocks ? kFrameWordSize + (uint64_t)sizes[b] : 0ull, wave_sum, &sum);
+        if (b < n_blocks) frame_at[b] = at;
+        total += sum;
     }
-    const uint64_t total = carry;
     if (t == 0) {
         frame_at[n_blocks] = total;
         *out_size = total;
@@ -43,7 +47,7 @@ __global__ __launch_bounds__(256) void pack_scan_kernel(const uint32_t* __restri
     }
     if (total > out_cap) return;
     if (t == 0) write_header(container, n_blocks, n_total);
-    for (uint32_t b = t; b < n_blocks; b += 256) write_frame(container + frame_at[b], sizes[b], ext);
+    for (uint32_t b = t; b < n_blocks; b += 256) write_frame(container + frame_at[b], sizes[b], ext);   // (frame_at[b]: this thread's own)
 }
 
 // Copy each block stream from its slot to its place in the container.  Destination offsets are
@@ -84,27 +88,20 @@ __global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t* __restric
     pack_copy_piece(slots + (size_t)b * kSlotSize, size, container + frame_at[b] + 3, piece_at);
 }
 
-// Serial frame walk of a container (tsq_threads.cpp:444-543: block k starts at 16 + sum(3+size_j)).
-// One wavefront; lane 0 walks, since each frame position depends on the previous one.
+// The frame walk of one container (walk_frames), validated as the reader validates it: the header, its block count against the
+// caller's, its total against the capacity, every frame, lengths that add up to the total.  One wavefront; lane 0 walks.  A
+// refused container gets *out_size = 0 and *status kErrFormat; the descriptors written by then stay as they are.
 __global__ __launch_bounds__(64) void frame_walk_kernel(const uint8_t* __restrict__ container, uint64_t n, uint32_t n_blocks,
                                                         uint64_t out_cap, FrameInfo* __restrict__ frames,
                                                         uint64_t* __restrict__ out_size, int32_t* __restrict__ status)
 {
     if (threadIdx.x != 0) return;
     uint32_t nb = 0;
-    uint64_t total = 0, at = kHeaderSize, oat = 0;
-    bool bad = read_header(container, n, &nb, &total) != kHeaderOk || nb != n_blocks || total > out_cap;
-    for (uint32_t b = 0; b < n_blocks && !bad; ++b) {
-        FrameInfo f;
-        if (at + kMinFrameSize > n || !read_frame(container + at, at, n, &f) || oat + f.out_len > total) { bad = true; break; }
-        f.stream_at = at + kFrameWordSize; f.out_at = oat;
-        frames[b] = f;
-        oat += f.out_len;
-        at += kFrameWordSize + f.stream_len;
-    }
-    if (!bad && oat != total) bad = true;
-    *out_size = bad ? 0 : total;
-    if (bad) atomicMax(status, kErrFormat);
+    uint64_t total = 0;
+    const bool ok = read_header(container, n, &nb, &total) == kHeaderOk && nb == n_blocks && total <= out_cap &&
+                    walk_frames(container, n, nb, total, [&](uint32_t b, uint64_t, const FrameInfo& f) { frames[b] = f; return true; }) == kWalkOk;
+    *out_size = ok ? total : 0;
+    if (!ok) atomicMax(status, kErrFormat);
 }
 
 }  // namespace tsq

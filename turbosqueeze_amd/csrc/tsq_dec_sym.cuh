@@ -351,22 +351,15 @@ __global__ __launch_bounds__(1024) void dec_sym_kernel(const uint8_t* __restrict
 }
 
 // dec_sym_kernel with a status word per batch item (tsqa_decompress_batch_items_async): block blockIdx.x reads and reports into the
-// word of the item that owns it (owner[]: batch_walk_items_kernel), so a fault ends that item's remaining blocks and nobody else's.
+// word of the item that owns it (owner[]: batch_walk_kernel<kWalkPerItem>), so a fault ends that item's remaining blocks and nobody
+// else's.  live_blocks != NULL: a batch whose block count is made on the device (tsqa_decompress_batch_packed_dense_async): the launch
+// has as many workgroups as the caller has room for blocks, and those at or past *live_blocks (batch_layout_kernel) leave before
+// they touch a descriptor or an owner.  NULL: every workgroup is live.
 __global__ __launch_bounds__(1024) void dec_item_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
                                                         const uint32_t* __restrict__ owner, uint8_t* __restrict__ outbuf,
-                                                        int32_t* __restrict__ item_status)
+                                                        int32_t* __restrict__ item_status, const uint32_t* __restrict__ live_blocks)
 {
-    sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, item_status + owner[blockIdx.x]);
-}
-
-// dec_item_kernel for a batch whose block count is made on the device (tsqa_decompress_batch_packed_dense_async): the launch has as
-// many workgroups as the caller has room for blocks, and those at or past *live_blocks (batch_layout_kernel) leave before they touch
-// a descriptor or an owner.
-__global__ __launch_bounds__(1024) void dec_dense_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
-                                                         const uint32_t* __restrict__ owner, uint8_t* __restrict__ outbuf,
-                                                         int32_t* __restrict__ item_status, const uint32_t* __restrict__ live_blocks)
-{
-    if (blockIdx.x >= *live_blocks) return;
+    if (live_blocks && blockIdx.x >= *live_blocks) return;
     sym_decode_block<kDecWhole>(container, frames, 0u, nullptr, outbuf, item_status + owner[blockIdx.x]);
 }
 

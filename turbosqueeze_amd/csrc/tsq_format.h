@@ -65,4 +65,28 @@ __host__ __device__ inline bool read_frame(const uint8_t* six, uint64_t at, uint
     return stream_len_ok(f->stream_len) && at + kFrameWordSize + f->stream_len <= n && f->out_len <= kBlockSize;
 }
 
+// walk_frames' verdicts: every frame passed, a malformed or truncated frame, block sizes that do not add up to the header's total
+// (a block that runs past it, or a sum short of it), or a visitor that ended the walk.
+enum WalkVerdict : int { kWalkOk = 0, kWalkBadFrame, kWalkBadSum, kWalkEnded };
+
+// THE reader's frame walk (tsq_threads.cpp:444-543: block k starts at 16 + sum(3 + size_j)), for host and device: over the nb frames
+// of the container of n bytes at p, whose header read_header has accepted with that count and `total`.  Serial, since each frame's
+// place depends on the one before.  visit(b, at, f) per frame that passes -- `at`: its frame word; f: read_frame's fields, with
+// stream_at and out_at relative to the container and its data -- returns false to end the walk.
+template <class Visit>
+__host__ __device__ inline WalkVerdict walk_frames(const uint8_t* p, uint64_t n, uint32_t nb, uint64_t total, Visit&& visit)
+{
+    uint64_t at = kHeaderSize, oat = 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+        FrameInfo f;
+        if (at + kMinFrameSize > n || !read_frame(p + at, at, n, &f)) return kWalkBadFrame;
+        if (oat + f.out_len > total) return kWalkBadSum;
+        f.stream_at = at + kFrameWordSize; f.out_at = oat;
+        if (!visit(b, at, f)) return kWalkEnded;
+        oat += f.out_len;
+        at += kFrameWordSize + f.stream_len;
+    }
+    return oat == total ? kWalkOk : kWalkBadSum;
+}
+
 }  // namespace tsq

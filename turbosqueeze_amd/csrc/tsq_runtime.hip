@@ -593,24 +593,6 @@ extern "C" int tsqa_frame_offsets(const uint32_t* sizes, uint32_t n_blocks, uint
     return TSQA_OK;
 }
 
-// The reader's walk over the nb frames of a container of `size` bytes in host memory whose header read_header has accepted:
-// visit(b, at, f) per frame (`at`: its frame word; f: read_frame's fields) returns false to end the walk, having set *why.
-// TSQA_ERR_FORMAT for a malformed or truncated frame and for block sizes that do not add up to the header's total.
-template <class Visit>
-static int walk_host_frames(const uint8_t* p, size_t size, uint32_t nb, uint64_t total, const char** why, Visit&& visit)
-{
-    uint64_t at = kHeaderSize, sum = 0;
-    for (uint32_t b = 0; b < nb; ++b) {
-        FrameInfo f;
-        if (at + kMinFrameSize > size || !read_frame(p + at, at, size, &f)) { *why = "malformed or truncated frame"; return TSQA_ERR_FORMAT; }
-        if (!visit(b, at, f)) return TSQA_ERR_FORMAT;
-        sum += f.out_len;
-        at += kFrameWordSize + f.stream_len;
-    }
-    if (sum != total) { *why = "block sizes do not add up to the total"; return TSQA_ERR_FORMAT; }
-    return TSQA_OK;
-}
-
 extern "C" int tsqa_walk_frames(const void* container, size_t size, uint32_t cap_blocks, uint64_t* frame_at, uint32_t* sizes, uint32_t* ext,
                                 uint32_t* out_len, uint32_t* n_blocks, uint64_t* total)
 {
@@ -618,12 +600,11 @@ extern "C" int tsqa_walk_frames(const void* container, size_t size, uint32_t cap
     const uint8_t* p = static_cast<const uint8_t*>(container);
     uint32_t nb; uint64_t tot;
     if (read_header(p, size, &nb, &tot) != kHeaderOk || nb > cap_blocks) return TSQA_ERR_FORMAT;
-    const char* why;
-    const int rc = walk_host_frames(p, size, nb, tot, &why, [&](uint32_t b, uint64_t at, const FrameInfo& f) {
+    const WalkVerdict v = walk_frames(p, size, nb, tot, [&](uint32_t b, uint64_t at, const FrameInfo& f) {
         frame_at[b] = at; sizes[b] = f.stream_len; ext[b] = f.ext; out_len[b] = f.out_len;
         return true;
     });
-    if (rc) return rc;
+    if (v != kWalkOk) return TSQA_ERR_FORMAT;
     *n_blocks = nb; *total = tot;
     return TSQA_OK;
 }
@@ -683,17 +664,20 @@ extern "C" int tsqa_sharded_fetch_decode_async(tsqa_ctx* c, const void* host_con
     if ((uint64_t)n_local * kSlotSize > streams_cap) { c->set_error("sharded_fetch_decode: %u owned frames do not fit d_streams (%zu B)", n_local, streams_cap); return TSQA_ERR_FORMAT; }
     if (int rc = c->reserve(n_local ? n_local : 1, false, false, false, s)) return rc;
     if (int rc = c->reserve_host_frames(n_local ? n_local : 1)) return rc;
-    const char* why;
-    const int rc = walk_host_frames(p, container_size, nb, tot, &why, [&](uint32_t b, uint64_t at, FrameInfo f) {
+    const WalkVerdict v = walk_frames(p, container_size, nb, tot, [&](uint32_t b, uint64_t at, FrameInfo f) {
         if (b % world != rank) return true;
         const uint32_t k = b / world;
-        if ((uint64_t)k * kBlockSize + f.out_len > out_cap) { why = "an owned block does not fit d_out"; return false; }
+        if ((uint64_t)k * kBlockSize + f.out_len > out_cap) return false;
         f.stream_at = (uint64_t)k * kSlotSize; f.out_at = (uint64_t)k * kBlockSize;
         c->host_frames[k] = f;
         c->host_frame_src[k] = at + kFrameWordSize;
         return true;
     });
-    if (rc) { c->set_error("sharded_fetch_decode: %s", why); return rc; }
+    if (v != kWalkOk) {
+        c->set_error("sharded_fetch_decode: %s", v == kWalkBadFrame ? "malformed or truncated frame" :
+                                                 v == kWalkBadSum ? "block sizes do not add up to the total" : "an owned block does not fit d_out");
+        return TSQA_ERR_FORMAT;
+    }
     *total = tot;
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     if (n_local == 0) return TSQA_OK;
@@ -1220,35 +1204,50 @@ extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t 
     return finish_sync(c, s, "compress_batch_packed");
 }
 
+// What every batch decompress with host-planned items starts with (`who`: the caller, for the error texts): the plan, an upload slot
+// with the items, the scratch, zeroed status words (d_item_status may be NULL) and, for a packed batch (d_offsets != NULL), the items'
+// places, which batch_place_kernel reads from d_offsets and d_packed_sizes (items' in_at, in_len unused).  The caller launches what
+// reads up->dev<BatchItem>() and commits the slot behind it, however those launches went.
+static int stage_decompress_batch(tsqa_ctx* c, const char* who, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
+                                  uint32_t n_items, size_t out_size, int32_t* d_item_status, int32_t* d_status, hipStream_t s,
+                                  const uint64_t* d_offsets, const uint64_t* d_packed_sizes, tsqa_uploads::Slot* up, uint32_t* total_blocks)
+{
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, d_offsets ? kPlanPlaced : kPlanDecompress)) {
+        c->set_error("%s: %s", who, why);
+        return TSQA_ERR_ARG;
+    }
+    (void)hipSetDevice(c->device);
+    *total_blocks = (uint32_t)first[n_items];
+    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), up)) return rc;
+    if (int rc = c->reserve(*total_blocks, false, false, true)) return rc;
+    c->forget_sharded();                                 // the frame walk behind this overwrites c->frames
+    BatchItem* const hi = up->host<BatchItem>();
+    for (uint32_t i = 0; i < n_items; ++i)
+        hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
+    if (d_item_status) TSQ_HIP(c, hipMemsetAsync(d_item_status, 0, (size_t)n_items * sizeof(int32_t), s));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    TSQ_HIP(c, up->send((size_t)n_items * sizeof(BatchItem), s));
+    if (d_offsets)                       // (the one kernel that writes a slot's device copy: the items' places)
+        hipLaunchKernelGGL(batch_place_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, up->dev<BatchItem>(), n_items,
+                           d_offsets, d_packed_sizes, (uint64_t)in_size);
+    return TSQA_OK;
+}
+
 // (variant < 0: the context's decode variant; the synchronous form's retry after TSQA_ERR_STALL passes 4.  d_offsets != NULL: a
-//  packed batch, whose containers' places batch_place_kernel reads from d_offsets and d_packed_sizes; items' in_at, in_len unused)
+//  packed batch)
 static int decompress_batch_async_impl(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
                                        uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_status, hipStream_t s,
                                        int variant, const uint64_t* d_offsets = nullptr, const uint64_t* d_packed_sizes = nullptr)
 {
     if (!d_in || !d_out || !d_sizes || !d_status || !n_blocks) { c->set_error("decompress_batch: null pointer"); return TSQA_ERR_ARG; }
-    std::vector<uint64_t> first((size_t)n_items + 1);
-    const char* why;
-    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, d_offsets ? kPlanPlaced : kPlanDecompress)) {
-        c->set_error("decompress_batch: %s", why);
-        return TSQA_ERR_ARG;
-    }
-    (void)hipSetDevice(c->device);
-    const uint32_t total_blocks = (uint32_t)first[n_items];
     tsqa_uploads::Slot up;
-    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
-    if (int rc = c->reserve(total_blocks, false, false, true)) return rc;
-    c->forget_sharded();                                 // the frame walk below overwrites c->frames
-    BatchItem* const hi = up.host<BatchItem>();
-    for (uint32_t i = 0; i < n_items; ++i)
-        hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
-    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
-    if (d_offsets)                       // (the one kernel that writes a slot's device copy: the items' places)
-        hipLaunchKernelGGL(batch_place_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, up.dev<BatchItem>(), n_items,
-                           d_offsets, d_packed_sizes, (uint64_t)in_size);
-    hipLaunchKernelGGL(batch_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(),
-                       n_items, c->frames, d_sizes, d_status);
+    uint32_t total_blocks;
+    if (int rc = stage_decompress_batch(c, "decompress_batch", in_size, items, n_blocks, n_items, out_size, nullptr, d_status, s, d_offsets,
+                                        d_packed_sizes, &up, &total_blocks)) return rc;
+    hipLaunchKernelGGL(batch_walk_kernel<kWalkOneWord>, dim3((n_items + 255u) / 256u), dim3(256), 0, s, static_cast<const uint8_t*>(d_in),
+                       up.dev<BatchItem>(), n_items, c->frames, (uint32_t*)nullptr, d_sizes, d_status);
     // one decode over every frame of the batch (launch_decode_kernels picks the decoder by the block count, as for one container)
     const int rc = c->launch_decode_frames(d_in, c->frames, total_blocks, d_out, d_status, s, variant);
     TSQ_HIP(c, up.commit(s));
@@ -1275,47 +1274,43 @@ extern "C" int tsqa_decompress_batch_packed_async(tsqa_ctx* c, const void* d_are
                                        d_sizes);
 }
 
-// The batch decompress with a verdict per item (tsqa_decompress_batch_items_async; d_offsets != NULL: the packed form, as in
-// decompress_batch_async_impl): the same planning, upload slot and scratch rule; batch_walk_items_kernel, one dec_item_kernel
-// workgroup per block whatever the context's decode variant (it waits for nobody: no TSQA_ERR_STALL), batch_close_items_kernel.
+// The decode with a verdict per item, behind a table of n_items items in device memory: batch_walk_kernel with owners, one
+// dec_item_kernel workgroup per block whatever the context's decode variant (it waits for nobody: no TSQA_ERR_STALL) -- n_groups
+// of them; live_blocks as dec_item_kernel takes it --, batch_close_items_kernel.  The walk and the close are enqueued however the
+// decode launch went, and a caller with an upload slot commits it behind this call whatever it returns (a refused decode launch
+// returns before hipGetLastError is asked).
+static int decode_items_enqueue(tsqa_ctx* c, const uint8_t* in, const BatchItem* d_items, uint32_t n_items, uint32_t n_groups,
+                                const uint32_t* live_blocks, void* d_out, uint64_t* d_sizes, int32_t* d_item_status, int32_t* d_status, hipStream_t s)
+{
+    const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
+    hipLaunchKernelGGL(batch_walk_kernel<kWalkPerItem>, per_item, dim3(256), 0, s, in, d_items, n_items, c->frames, c->block_owner, d_sizes,
+                       d_item_status);
+    ProfSpan span(c, 1, s);
+    const int rc = launch_read_kernel<dec_item_kernel>(c, n_groups, s, in, static_cast<const FrameInfo*>(c->frames),
+                                                       static_cast<const uint32_t*>(c->block_owner), static_cast<uint8_t*>(d_out), d_item_status,
+                                                       live_blocks);
+    if (rc) span.cancel(); else span.end();
+    hipLaunchKernelGGL(batch_close_items_kernel, per_item, dim3(256), 0, s, n_items, static_cast<const int32_t*>(d_item_status), d_sizes, d_status);
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+// The batch decompress with a verdict per item (tsqa_decompress_batch_items_async; d_offsets != NULL: the packed form).
 static int decompress_batch_items_async_impl(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, const uint32_t* n_blocks,
                                              uint32_t n_items, void* d_out, size_t out_size, uint64_t* d_sizes, int32_t* d_item_status,
                                              int32_t* d_status, hipStream_t s, const uint64_t* d_offsets = nullptr,
                                              const uint64_t* d_packed_sizes = nullptr)
 {
     if (!d_in || !d_out || !d_sizes || !d_item_status || !d_status || !n_blocks) { c->set_error("decompress_batch_items: null pointer"); return TSQA_ERR_ARG; }
-    std::vector<uint64_t> first((size_t)n_items + 1);
-    const char* why;
-    if (plan_batch(items, n_items, in_size, out_size, n_blocks, first.data(), &why, d_offsets ? kPlanPlaced : kPlanDecompress)) {
-        c->set_error("decompress_batch_items: %s", why);
-        return TSQA_ERR_ARG;
-    }
-    (void)hipSetDevice(c->device);
-    const uint32_t total_blocks = (uint32_t)first[n_items];
     tsqa_uploads::Slot up;
-    if (int rc = c->batch_up.acquire(c, (size_t)n_items * sizeof(BatchItem), &up)) return rc;
-    if (int rc = c->reserve(total_blocks, false, false, true)) return rc;
-    c->forget_sharded();                                 // the frame walk below overwrites c->frames
-    BatchItem* const hi = up.host<BatchItem>();
-    for (uint32_t i = 0; i < n_items; ++i)
-        hi[i] = BatchItem{items[i].in_at, items[i].in_len, items[i].out_at, items[i].out_cap, first[i], n_blocks[i], 0u};
-    TSQ_HIP(c, hipMemsetAsync(d_item_status, 0, (size_t)n_items * sizeof(int32_t), s));
-    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
-    TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
-    const dim3 per_item((n_items + 255u) / 256u);
-    if (d_offsets)
-        hipLaunchKernelGGL(batch_place_kernel, per_item, dim3(256), 0, s, up.dev<BatchItem>(), n_items, d_offsets, d_packed_sizes, (uint64_t)in_size);
-    hipLaunchKernelGGL(batch_walk_items_kernel, per_item, dim3(256), 0, s, static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(), n_items,
-                       c->frames, c->block_owner, d_sizes, d_item_status);
-    ProfSpan span(c, 1, s);
-    int rc = launch_read_kernel<dec_item_kernel>(c, total_blocks, s, static_cast<const uint8_t*>(d_in), static_cast<const FrameInfo*>(c->frames),
-                                                 static_cast<const uint32_t*>(c->block_owner), static_cast<uint8_t*>(d_out), d_item_status);
-    if (rc) span.cancel(); else span.end();
-    hipLaunchKernelGGL(batch_close_items_kernel, per_item, dim3(256), 0, s, n_items, static_cast<const int32_t*>(d_item_status), d_sizes, d_status);
+    uint32_t total_blocks;
+    if (int rc = stage_decompress_batch(c, "decompress_batch_items", in_size, items, n_blocks, n_items, out_size, d_item_status, d_status, s,
+                                        d_offsets, d_packed_sizes, &up, &total_blocks)) return rc;
+    const int rc = decode_items_enqueue(c, static_cast<const uint8_t*>(d_in), up.dev<BatchItem>(), n_items, total_blocks, nullptr, d_out, d_sizes,
+                                        d_item_status, d_status, s);
     TSQ_HIP(c, up.commit(s));                            // (however the decode launch went: the walk has been enqueued)
-    if (rc) return rc;
-    TSQ_HIP(c, hipGetLastError());
-    return TSQA_OK;
+    return rc;
 }
 
 extern "C" int tsqa_decompress_batch_items_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items,
@@ -1394,18 +1389,8 @@ extern "C" int tsqa_decompress_batch_packed_dense_async(tsqa_ctx* c, const void*
     hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, (uint64_t)out_size, d_out ? cap_blocks : 0u,
                        d_out_offsets, d_out_sizes, d_first_block, d_item_status, c->batch_live, d_out ? nullptr : d_status);
     if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
-    hipLaunchKernelGGL(batch_walk_items_kernel, per_item, dim3(256), 0, s, in, static_cast<const BatchItem*>(c->batch_items), n_items, c->frames,
-                       c->block_owner, d_out_sizes, d_item_status);
-    hipLaunchKernelGGL(batch_overflow_kernel, per_item, dim3(256), 0, s, static_cast<const BatchItem*>(c->batch_items), n_items, d_item_status);
-    ProfSpan span(c, 1, s);
-    const int rc = launch_read_kernel<dec_dense_kernel>(c, cap_blocks, s, in, static_cast<const FrameInfo*>(c->frames),
-                                                        static_cast<const uint32_t*>(c->block_owner), static_cast<uint8_t*>(d_out), d_item_status,
-                                                        static_cast<const uint32_t*>(c->batch_live));
-    if (rc) span.cancel(); else span.end();
-    hipLaunchKernelGGL(batch_close_items_kernel, per_item, dim3(256), 0, s, n_items, static_cast<const int32_t*>(d_item_status), d_out_sizes, d_status);
-    if (rc) return rc;
-    TSQ_HIP(c, hipGetLastError());
-    return TSQA_OK;
+    return decode_items_enqueue(c, in, static_cast<const BatchItem*>(c->batch_items), n_items, cap_blocks, static_cast<const uint32_t*>(c->batch_live),
+                                d_out, d_out_sizes, d_item_status, d_status, s);
 }
 
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
@@ -1537,8 +1522,8 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
     // one frame walk over all items, one lane each, into the index's own descriptors; verdicts and descriptors come back together
     TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)(blocks ? blocks : 1) * sizeof(FrameInfo)));
     TSQ_HIP(c, up.send((size_t)n_items * sizeof(BatchItem), s));
-    hipLaunchKernelGGL(batch_index_walk_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, s, in, up.dev<BatchItem>(), n_items, idx->frames,
-                       c->batch_sizes);
+    hipLaunchKernelGGL(batch_walk_kernel<kWalkIndex>, dim3((n_items + 255u) / 256u), dim3(256), 0, s, in, up.dev<BatchItem>(), n_items, idx->frames,
+                       (uint32_t*)nullptr, c->batch_sizes, (int32_t*)nullptr);
     TSQ_HIP(c, hipGetLastError());
     TSQ_HIP(c, up.commit(s));
     TSQ_HIP(c, hipMemcpyAsync(verdicts.data(), c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
