@@ -436,6 +436,54 @@ int tsqa_decompress_batch_packed_dense_async(tsqa_ctx *ctx, const void *d_arena,
                                              uint64_t *d_first_block, int32_t *d_item_status, int32_t *d_status, void *hip_stream);
 
 /*
+ * Packed compress whose item table is made on the device: the mirror of the dense decompress.  Item i is bytes [in_offsets[i],
+ * in_offsets[i] + in_sizes[i]) of d_in, both tables in device memory (lengths a kernel has just computed, the d_out_offsets /
+ * d_out_sizes that the dense decompress leaves, the tables of an arena to be repacked); input ranges may overlap.  Nothing is
+ * uploaded and nothing in the tables is trusted.  Per item, on the device:
+ *   1. Place: in_sizes[i] >= 1, in_sizes[i] <= in_size, in_offsets[i] <= in_size - in_sizes[i], else TSQA_ERR_ARG: no blocks, and not
+ *      one byte of the item is read.  (tsqa_compress_batch_packed_async refuses the whole call for these; here they cost the item.)
+ *   2. Blocks: blocks_i = ceil(in_sizes[i] / TSQ_BLOCK_SZ), 0 for a refused item; first_block[0] = 0, first_block[i + 1] =
+ *      first_block[i] + blocks_i.  An accepted item fits when first_block[i] + blocks_i <= cap_blocks; the fitting items are a
+ *      prefix of the accepted ones (the first unfit item ends it, whatever would fit behind it).  An unfit item gets
+ *      TSQA_ERR_OVERFLOW and is not read.  d_first_block (n_items + 1) is complete whatever fits: first_block[n_items] is the
+ *      cap_blocks a retry needs.  The sums stay below 2^59 and cannot wrap (in_size <= 2^48).
+ *   3. Arena: every fitting item is encoded; its container is byte for byte tsqa_compress_device's for its bytes alone.  d_sizes[i]
+ *      = its size, 0 for a refused or unfit item; d_offsets (n_items + 1) = tsqa_plan_packed's rule applied to d_sizes, so an item
+ *      of size 0 takes no room.  A header or frame is written only if it ends at or before out_size; nothing at or past d_out +
+ *      out_size is written, padding never.  A fitting item with offsets[i] + sizes[i] > out_size gets TSQA_ERR_OVERFLOW; its size and
+ *      place are still correct, and a retry with offsets[n_items] bytes succeeds.
+ *   4. Bound: *d_bound (one word, may be NULL) = the sum over the accepted items of round_up(tsqa_batch_bound(in_sizes[i]), align):
+ *      room that always holds the arena.  Refused items add nothing: a lying size cannot inflate it.
+ *   5. Status: d_item_status[i] == 0 means that the item's container is complete and exact, whatever the other items are;
+ *      *d_status = the largest item status.
+ * cap_blocks: the blocks the call may encode.  It sizes the descriptor scratch (24 B each) and the encode launches, 2 x CUs blocks
+ * each, whose workgroups past the live blocks leave at once: a loose value costs empty launches, and -- the layout of the staged
+ * encoder follows the launch's workgroup count -- may pick the lean layout for few live blocks.  Pass a tight value
+ * (first_block[n_items] of a measuring call, or tsqa_plan_compress_tables).
+ * Measure only: d_out == NULL with out_size == 0 (cap_blocks is not looked at).  d_item_status, d_first_block and *d_bound are made,
+ * every accepted item reads TSQA_ERR_OVERFLOW, d_sizes and d_offsets are all 0, and no encoder is launched.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL table, input or status pointer, n_items == 0, a bad
+ * align, in_size > 2^48, a non-NULL d_out with out_size < 16 or cap_blocks == 0, a NULL d_out with out_size != 0, an encoder variant
+ * other than 0, 6 or 7.
+ * The item table, the block descriptors and the per-launch tables live in the context's scratch; the call returns at once and may
+ * be enqueued again on the same stream before the first has run (a call with more items or a larger cap_blocks than any before it
+ * first waits for the device, then grows the scratch).
+ *
+ * tsqa_plan_compress_tables: host only.  Rules 1, 2 and 4 from host copies of the tables -> first_block[n_items + 1],
+ *   item_status[n_items] (0, TSQA_ERR_ARG, or TSQA_ERR_OVERFLOW for an accepted item outside the fitting prefix), *bound, and *n_fit =
+ *   the index of the first accepted item that does not fit cap_blocks, n_items when all do.  TSQA_ERR_ARG for a NULL pointer,
+ *   n_items == 0, a bad align or in_size > 2^48.
+ */
+int tsqa_plan_compress_tables(const uint64_t *in_offsets, const uint64_t *in_sizes, uint32_t n_items, uint64_t in_size,
+                              uint32_t align, uint32_t cap_blocks, uint64_t *first_block, int32_t *item_status, uint64_t *bound,
+                              uint32_t *n_fit);
+int tsqa_compress_batch_packed_tables_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const uint64_t *d_in_offsets,
+                                            const uint64_t *d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
+                                            uint32_t align, void *d_out, size_t out_size, uint64_t *d_offsets, uint64_t *d_sizes,
+                                            uint64_t *d_first_block, uint64_t *d_bound, int32_t *d_item_status, int32_t *d_status,
+                                            void *hip_stream);
+
+/*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
  * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
  * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.

@@ -24,6 +24,7 @@ from .api import (  # noqa: F401
     lib,
     lib_path,
     plan_batch,
+    plan_compress_tables,
     plan_dense,
     plan_item_ranges,
     plan_packed,

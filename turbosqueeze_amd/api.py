@@ -197,6 +197,11 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_batch_packed_dense_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
                                                            vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_batch_packed_items_async.restype = C.c_int
+    L.tsqa_plan_compress_tables.restype = C.c_int
+    L.tsqa_plan_compress_tables.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.tsqa_compress_batch_packed_tables_async.restype = C.c_int
+    L.tsqa_compress_batch_packed_tables_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                                          C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_batch_packed_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
     L.tsqa_index_create_batch.restype = C.c_int
     L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
@@ -393,6 +398,22 @@ def plan_dense(totals, blocks, align: int = 16, out_size: int = 0, cap_blocks: i
     if rc:
         raise TsqError(rc, "tsqa_plan_dense refused the arguments")
     return [int(x) for x in offsets], [int(x) for x in first], int(n_fit.value)
+
+
+def plan_compress_tables(in_offsets, in_sizes, in_size: int, align: int = 16, cap_blocks: int = 0):
+    """tsqa_plan_compress_tables (host only): what DeviceCodec.compress_batch_packed_tables_async decides before it encodes, from
+    host copies of its tables -> (first_block, then the blocks needed; item_status: 0, 3 for a place outside the input, 6 for an
+    accepted item outside the prefix that fits cap_blocks; bound: the room that always holds the arena; n_fit)."""
+    import numpy as np
+    at = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+    sz = np.ascontiguousarray(in_sizes, dtype=np.uint64)
+    first, status = np.zeros(len(sz) + 1, dtype=np.uint64), np.zeros(len(sz), dtype=np.int32)
+    bound, n_fit = C.c_uint64(0), C.c_uint32(0)
+    rc = lib().tsqa_plan_compress_tables(at.ctypes.data, sz.ctypes.data, min(len(at), len(sz)), in_size, align, cap_blocks, first.ctypes.data,
+                                         status.ctypes.data, C.byref(bound), C.byref(n_fit))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_compress_tables refused the arguments")
+    return [int(x) for x in first], [int(x) for x in status], int(bound.value), int(n_fit.value)
 
 
 class ItemRange(C.Structure):
@@ -957,6 +978,56 @@ class DeviceCodec:
                                                              d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
+
+    def compress_batch_packed_tables_async(self, data, d_in_offsets, d_in_sizes, n_items: int, cap_blocks: int, ext: int, align: int, out,
+                                           d_offsets, d_sizes, d_first_block, d_bound, d_item_status) -> None:
+        """tsqa_compress_batch_packed_tables_async on the current stream, nothing waited for and nothing about the items taken from
+        the host: item i is data[d_in_offsets[i]:][:d_in_sizes[i]] (int64 CUDA tensors), its container lands packed in out at
+        d_offsets[i] with d_sizes[i] bytes (int64 CUDA tensors of n_items + 1 and n_items entries; d_first_block: n_items + 1;
+        d_bound: one entry or None; d_item_status: int32, n_items).  An item whose place lies outside data gets TSQA_ERR_ARG (3), one
+        that does not fit cap_blocks blocks or out TSQA_ERR_OVERFLOW (6), and the tables say what a retry needs.  out None: measure
+        only.  The largest item status lands in status()."""
+        rc = self.L.tsqa_compress_batch_packed_tables_async(self.h, data.data_ptr(), data.numel(), d_in_offsets.data_ptr(), d_in_sizes.data_ptr(),
+                                                            int(n_items), int(cap_blocks), int(ext), int(align),
+                                                            out.data_ptr() if out is not None else None, out.numel() if out is not None else 0,
+                                                            d_offsets.data_ptr(), d_sizes.data_ptr(), d_first_block.data_ptr(),
+                                                            d_bound.data_ptr() if d_bound is not None else None, d_item_status.data_ptr(),
+                                                            self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def compress_packed_tables(self, data, d_in_offsets, d_in_sizes, ext: int, align: int = 16, cap_blocks=None, out=None,
+                               item_status: bool = False):
+        """Compress the items data[d_in_offsets[i]:][:d_in_sizes[i]] (int64 CUDA tensors) into a dense arena.  With cap_blocks or out
+        missing the batch is measured on the device first and the two "needed" words come back with one copy: the block count, and
+        the room that always holds the arena, of which a new `out` is made (trimmed to the bytes used afterwards).  -> a PackedBatch
+        (PackedBatch.from_device); item_status=True: -> (batch, statuses), and a refused or unfit item -- status 3 or 6, size 0 --
+        does not raise; without it such an item raises TsqError with the largest item status and .item_status."""
+        torch = self.torch
+        n = int(d_in_sizes.numel())
+        d_offsets, d_sizes, d_first, d_status = self._dense_tables(n)
+        d_bound = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._join()
+        if cap_blocks is None or out is None:
+            self.compress_batch_packed_tables_async(data, d_in_offsets, d_in_sizes, n, 0, ext, align, None, d_offsets, d_sizes, d_first, d_bound,
+                                                    d_status)
+            self._join()
+            need_blocks, bound = torch.stack([d_first[n], d_bound[0]]).cpu().tolist()
+            if cap_blocks is None:
+                cap_blocks = max(need_blocks, 1)
+            if out is None:
+                out = torch.empty(max(bound, 16), dtype=torch.uint8, device=self.device)
+        self.compress_batch_packed_tables_async(data, d_in_offsets, d_in_sizes, n, cap_blocks, ext, align, out, d_offsets, d_sizes, d_first, d_bound,
+                                                d_status)
+        self._join()
+        status = d_status.cpu().tolist()
+        if any(status) and not item_status:
+            e = self._err(max(status))
+            e.item_status = status
+            raise e
+        used = int(d_offsets[n].item())
+        batch = PackedBatch.from_device(self, out[:min(used, out.numel())], d_offsets, d_sizes)
+        return (batch, status) if item_status else batch
 
     def decompress_packed(self, arena, d_offsets, d_sizes, align: int = 16, out=None, item_status: bool = False):
         """The items of a packed batch known only by its arena and device tables: measure on the device, read the two "needed" words

@@ -10,7 +10,9 @@ namespace tsq {
 
 // One item of a batch as the kernels see it, planned on the host (tsqa_plan_batch): its input and output ranges, relative to the
 // batch's input and output, its first block in the batch and its block count.  The dense decompress makes the table on the device
-// (batch_measure_kernel, batch_layout_kernel); only there is unfit used: 1 marks an item that did not fit the caller's room.
+// (batch_measure_kernel, batch_layout_kernel); only there is unfit used: 1 marks an item that did not fit the caller's room.  The
+// compress from device tables makes it there too (batch_measure_tables_kernel, batch_layout_tables_kernel): a refused or unfit item
+// is all zeros there, and an item without blocks has no container: size 0, nothing written.
 struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_t n_blocks, unfit; };
 
 constexpr uint64_t kNoFrame = ~0ull;      // frame_at of a block whose frame does not fit its item: batch_pack_copy_kernel skips it
@@ -23,6 +25,7 @@ __device__ __forceinline__ uint64_t batch_item_frames(const BatchItem& it, const
                                                      const uint32_t* __restrict__ sizes, uint32_t ext, bool write, uint8_t* out,
                                                      uint64_t start, uint64_t limit, uint64_t* frame_at)
 {
+    if (it.n_blocks == 0u) return 0;                         // (an item that batch_layout_tables_kernel left out: no header either)
     const uint64_t first = it.first_block, end = first + it.n_blocks, launch_end = b0 + nb;
     const bool begins = first >= b0;
     if (write && begins && start + kHeaderSize <= limit) write_header(out + start, it.n_blocks, it.in_len);
@@ -70,13 +73,15 @@ __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* _
 // offsets[i0] whether its first item continues (its start) or begins there (what the last complete item left).  Each item is sized
 // first (batch_item_frames without writing), and written once the scan has made its start; a header or frame is written only if it
 // ends inside out_size; sizes[] and offsets[] are complete whatever fits.
-__global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0,
-                                                                     uint32_t ni, uint64_t b0, uint32_t nb,
-                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
-                                                                     uint8_t* __restrict__ out, uint64_t out_size,
-                                                                     uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
-                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
-                                                                     int32_t* __restrict__ status)
+// The body serves both entries below.  item_status == NULL: the batch planned on the host, one word: the places only grow, so the
+// last item tells whether the arena was too small.  Else (the batch made from device tables, whose window may also hold any
+// number of items without blocks: they take no room) each item that ends past out_size gets kErrOverflow for itself.
+__device__ __forceinline__ void batch_pack_scan_packed_body(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0, uint32_t ni,
+                                                            uint64_t b0, uint32_t nb, const uint32_t* __restrict__ sizes, uint32_t ext,
+                                                            uint32_t align, uint8_t* __restrict__ out, uint64_t out_size,
+                                                            uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
+                                                            uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                            int32_t* __restrict__ item_status, int32_t* __restrict__ status)
 {
     __shared__ uint64_t wave_sum[4];
     const uint64_t mask = (uint64_t)align - 1u;
@@ -96,12 +101,55 @@ __global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const Batch
             run_at[i] = at;                                  // (only now: the writing pass has read the carry that the sizing pass read)
         }
         if (complete) {
-            const bool last = i + 1u == n_items;
+            const bool last = i + 1u == n_items, over = start + at > out_size;
             d_sizes[i] = at;
             d_offsets[i + 1u] = last ? start + at : start + ((at + mask) & ~mask);
-            if (last && start + at > out_size) atomicMax(status, kErrOverflow);
+            if (item_status ? over && it.n_blocks != 0u : over && last) atomicMax(status, kErrOverflow);
+            if (item_status && over && it.n_blocks != 0u) item_status[i] = kErrOverflow;
         }
     }
+}
+
+// The items [i0, i0 + ni) with blocks in the launch of the batch's blocks [b0, b0 + nb), found on the host.
+__global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0,
+                                                                     uint32_t ni, uint64_t b0, uint32_t nb,
+                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
+                                                                     uint8_t* __restrict__ out, uint64_t out_size,
+                                                                     uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
+                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                     int32_t* __restrict__ status)
+{
+    batch_pack_scan_packed_body(items, n_items, i0, ni, b0, nb, sizes, ext, align, out, out_size, run_at, frame_at, d_offsets, d_sizes, nullptr,
+                                status);
+}
+
+// batch_pack_scan_packed_kernel behind launch l (blocks [l * budget, (l + 1) * budget) of the batch) of a batch whose item table was
+// made on the device (tsqa_compress_batch_packed_tables_async): the launch's items are found here, not on the host.  The live blocks
+// of the launch end at min((l + 1) * budget, *live_blocks); a launch past them has nothing to do and leaves, and the sizes and
+// frame places of the dead blocks of a live launch are never looked at.  launch_item[l] (batch_enc_blocks_kernel) is the item that
+// holds the launch's first block.  The items without blocks -- refused, or unfit for cap_blocks -- get their size 0 and carry
+// offsets[] over them in the launch that completes the item with blocks in front of them: the window of launch l runs from the item
+// that holds its first block (launch 0: from item 0, and launch 0 is never dead: a batch without a live block has its tables
+// written there) to the item that holds the first block behind the launch, that item included only if it starts inside the
+// launch; behind the last live block it runs to the end of the table.  So the windows of the live launches cover every item, and
+// an item is complete in exactly one of them.  A fitting item that ends past out_size: item_status[i] = kErrOverflow.
+__global__ __launch_bounds__(256) void batch_pack_scan_tables_kernel(const BatchItem* __restrict__ items, uint32_t n_items,
+                                                                     const uint32_t* __restrict__ launch_item, uint32_t l, uint32_t budget,
+                                                                     const uint32_t* __restrict__ live_blocks,
+                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
+                                                                     uint8_t* __restrict__ out, uint64_t out_size,
+                                                                     uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
+                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                     int32_t* __restrict__ item_status, int32_t* __restrict__ status)
+{
+    const uint64_t live = *live_blocks, b0 = (uint64_t)l * budget;
+    if (l != 0u && b0 >= live) return;                       // (the whole workgroup, before any barrier)
+    const uint64_t end = b0 + budget < live ? b0 + budget : live;
+    const uint32_t i0 = l != 0u ? launch_item[l] : 0u;
+    uint32_t i1 = n_items;
+    if (end < live) { const uint32_t e = launch_item[l + 1u]; i1 = e + (items[e].first_block < end ? 1u : 0u); }
+    batch_pack_scan_packed_body(items, n_items, i0, i1 - i0, b0, (uint32_t)(end - b0), sizes, ext, align, out, out_size, run_at, frame_at,
+                                d_offsets, d_sizes, item_status, status);
 }
 
 // Before batch_walk_kernel in the packed decompress calls: one lane per item takes its container's place from tables in
@@ -197,12 +245,108 @@ __global__ __launch_bounds__(256) void batch_layout_kernel(BatchItem* __restrict
     if (threadIdx.x == 0) *live_blocks = live;
 }
 
+// First kernel of tsqa_compress_batch_packed_tables_async, which reads the items' places from tables in device memory: one lane per
+// item.  The tables are not trusted: an item must have at least one byte and lie inside the input (tsqa_plan_batch's checks, which
+// cost the whole call there and the item here).  An accepted item gets in_at, in_len, its block count and status 0; a refused one
+// is all zeros and kErrArg, and not one byte of it is read.  first_block is batch_layout_tables_kernel's.
+__global__ __launch_bounds__(256) void batch_measure_tables_kernel(BatchItem* __restrict__ items, uint32_t n_items,
+                                                                   const uint64_t* __restrict__ d_in_offsets,
+                                                                   const uint64_t* __restrict__ d_in_sizes, uint64_t in_size,
+                                                                   int32_t* __restrict__ item_status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_items) return;
+    const uint64_t at = d_in_offsets[i], n = d_in_sizes[i];
+    const bool ok = n >= 1u && n <= in_size && at <= in_size - n;
+    // (in_size <= 2^48, the call's own limit: at most 2^26 blocks per item)
+    items[i] = ok ? BatchItem{at, n, 0, 0, 0, (uint32_t)((n + kBlockSize - 1u) / kBlockSize), 0u} : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
+    item_status[i] = ok ? kOk : kErrArg;
+}
+
+// Behind batch_measure_tables_kernel: batch_layout_kernel for a compress, whose arena places exist only once the sizes do.  ONE
+// workgroup of exactly 256 threads, the same two sums per pass with both carries: block counts, and round_up(batch_bound(in_len),
+// align) of the accepted items -- *d_bound (may be NULL), the room that always holds the arena; a refused item adds nothing to
+// either, so a lying size cannot inflate them.  first_block[i + 1] = first_block[i] + blocks_i is complete whatever fits.  An
+// accepted item fits when first_block[i] + blocks_i <= cap_blocks; the fitting items are a prefix of the accepted ones, held as
+// batch_layout_kernel holds it (first_unfit), so a verdict rests on a sum of at most cap_blocks; the whole sums stay below 2^59
+// (2^32 items of at most 2^26 blocks) and cannot wrap.  An item that does not fit gets kErrOverflow and becomes all zeros: nothing
+// of it is read.  *live_blocks = the blocks of the fitting prefix; *status (zero before) = the largest verdict given here.
+// d_offsets != NULL: the measure-only call, which runs nothing behind this kernel (cap_blocks is 0: nothing fits): d_offsets and
+// d_sizes are written, all 0.
+__global__ __launch_bounds__(256) void batch_layout_tables_kernel(BatchItem* __restrict__ items, uint32_t n_items, uint32_t align,
+                                                                  uint32_t cap_blocks, uint64_t* __restrict__ d_offsets,
+                                                                  uint64_t* __restrict__ d_sizes, uint64_t* __restrict__ d_first_block,
+                                                                  uint64_t* __restrict__ d_bound, int32_t* __restrict__ item_status,
+                                                                  uint32_t* __restrict__ live_blocks, int32_t* __restrict__ status)
+{
+    __shared__ uint64_t wave_sum[4];
+    __shared__ uint32_t first_unfit, live;
+    const uint64_t mask = (uint64_t)align - 1u;
+    if (threadIdx.x == 0) { first_unfit = ~0u; live = 0u; d_first_block[0] = 0; if (d_offsets) d_offsets[0] = 0; }
+    uint64_t block_base = 0, bound_base = 0;
+    for (uint64_t i0 = 0; i0 < n_items; i0 += 256u) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool valid = i < n_items;
+        uint64_t len = 0;
+        uint32_t nb = 0;
+        int32_t st = kOk;
+        if (valid) { nb = items[i].n_blocks; len = items[i].in_len; st = item_status[i]; }
+        const bool accepted = valid && st == kOk;
+        uint64_t sum;
+        const uint64_t first = block_base + group_scan_excl64(nb, wave_sum, &sum);
+        block_base += sum;
+        group_scan_excl64(accepted ? (batch_bound(len) + mask) & ~mask : 0ull, wave_sum, &sum);
+        bound_base += sum;
+        const bool fits = accepted && first + nb <= cap_blocks;
+        if (accepted && !fits) atomicMin(&first_unfit, (uint32_t)i);
+        __syncthreads();                                     // (no lane leaves the loop early: the scans and this barrier need them all)
+        if (valid) {
+            const bool fit = fits && i < first_unfit, over = accepted && !fit;
+            if (fit) { items[i].first_block = first; atomicMax(&live, (uint32_t)(first + nb)); }
+            else items[i] = BatchItem{0, 0, 0, 0, 0, 0u, over ? 1u : 0u};
+            if (over) item_status[i] = kErrOverflow;
+            if (!fit) atomicMax(status, over ? kErrOverflow : st);
+            if (d_offsets) { d_sizes[i] = 0; d_offsets[i + 1u] = 0; }
+            d_first_block[i + 1u] = first + nb;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { *live_blocks = live; if (d_bound) *d_bound = bound_base; }
+}
+
+// Behind batch_layout_tables_kernel: one lane per live block b makes its EncBatchBlock, in slot b % budget of its launch.  The
+// block's item is the last one whose first_block is at or below b (the items without blocks in front of it share its first_block;
+// the ones behind it, and every unfit item, start past b), found by bisection in d_first_block; launch_item[l] = the item that
+// holds block l * budget, for batch_pack_scan_tables_kernel.  Lanes at or past *live_blocks leave: the descriptors and launch_item
+// entries of dead blocks are never written and never read.
+__global__ __launch_bounds__(256) void batch_enc_blocks_kernel(const BatchItem* __restrict__ items, uint32_t n_items,
+                                                               const uint64_t* __restrict__ d_first_block,
+                                                               const uint32_t* __restrict__ live_blocks, uint32_t budget,
+                                                               EncBatchBlock* __restrict__ blocks, uint32_t* __restrict__ launch_item)
+{
+    const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (b >= *live_blocks) return;
+    uint32_t lo = 0, hi = n_items;                           // first_block[lo] <= b < first_block[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (d_first_block[mid] <= b) lo = mid; else hi = mid;
+    }
+    const BatchItem it = items[lo];
+    const uint64_t off = (b - it.first_block) * kBlockSize, left = it.in_len - off;
+    blocks[b] = EncBatchBlock{it.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
+    if (b % budget == 0u) launch_item[b / budget] = lo;
+}
+
 // Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.
-// grid = (pieces, blocks of the launch).
+// grid = (pieces, blocks of the launch).  live_blocks != NULL (the batch made from device tables, its launch sized by cap_blocks;
+// b0: the launch's first block in the batch): a block at or past *live_blocks was never encoded, and its size and frame place are
+// stale: not read.
 __global__ __launch_bounds__(256) void batch_pack_copy_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes,
-                                                              const uint64_t* __restrict__ frame_at, uint8_t* __restrict__ out)
+                                                              const uint64_t* __restrict__ frame_at, uint8_t* __restrict__ out,
+                                                              uint32_t b0, const uint32_t* __restrict__ live_blocks)
 {
     const uint32_t b = blockIdx.y;
+    if (live_blocks && b0 + b >= *live_blocks) return;
     const uint32_t size = sizes[b];
     const uint32_t piece_at = blockIdx.x * kPackPiece;
     const uint64_t at = frame_at[b];

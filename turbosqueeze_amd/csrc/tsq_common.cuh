@@ -16,7 +16,7 @@ constexpr uint32_t kHashMask    = kHashEntries - 1u;
 constexpr uint32_t kWave        = 64;
 
 // status codes mirrored from include/turbosqueeze_amd.h
-constexpr int32_t kOk = 0, kErrFormat = 4, kErrStream = 5, kErrOverflow = 6, kErrStall = 7;
+constexpr int32_t kOk = 0, kErrArg = 3, kErrFormat = 4, kErrStream = 5, kErrOverflow = 6, kErrStall = 7;
 
 // Per-block frame description produced by the frame-walk kernel for the decoders.
 struct FrameInfo {
@@ -27,6 +27,11 @@ struct FrameInfo {
     uint32_t out_len;     // u24 header of the stream
     uint32_t pad;
 };
+
+// One block of a batch of independent items (tsqa_compress_batch_async), for enc_batch_kernel: where it starts in the batch's input,
+// the bytes of ITS item from there on (the look-ahead never reaches the next item), its length and its slot in the launch.  Made on
+// the host, or by batch_enc_blocks_kernel (tsq_batch.cuh).
+struct EncBatchBlock { uint64_t src_at, avail; uint32_t n, slot; };
 
 // ---- unaligned little-endian loads (gfx950 global memory handles them in hardware) ----
 __device__ __forceinline__ uint32_t ldu16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }

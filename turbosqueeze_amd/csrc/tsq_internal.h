@@ -9,7 +9,7 @@
 
 #include "../../include/turbosqueeze_amd.h"
 
-namespace tsq { struct FrameInfo; struct BatchItem; }
+namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; }
 
 struct tsqa_ctx;
 
@@ -83,6 +83,11 @@ struct tsqa_ctx {
     tsq::BatchItem* batch_items = nullptr;
     uint32_t* batch_live = nullptr;
     size_t cap_batch = 0;
+    // tsqa_compress_batch_packed_tables_async: the block descriptors it makes on the device (cap_blocks of them) and, per encode
+    // launch, the item that holds the launch's first block
+    tsq::EncBatchBlock* table_blocks = nullptr;
+    uint32_t* table_launch_item = nullptr;
+    size_t cap_table_blocks = 0, cap_table_launches = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     uint32_t* duo_ring = nullptr;      // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     uint32_t* duo_flags = nullptr;     // and their progress counters
@@ -107,6 +112,7 @@ struct tsqa_ctx {
     int reserve_duo(size_t n_blocks, hipStream_t s = nullptr);
     int reserve_host_frames(size_t n);
     int reserve_batch(size_t n_items);
+    int reserve_tables(size_t n_blocks, size_t n_launches);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]

@@ -88,13 +88,18 @@ inline int launch_encode_kernels(tsqa_ctx* c, const uint8_t* in, size_t n, size_
 }
 
 // Encode nb blocks of a batch (tsqa_compress_batch_async) from their descriptors: the staged encoder in the layout
-// launch_encode_kernels takes for nb blocks.  Encoder variants 0, 6 and 7 only.
+// launch_encode_kernels takes for nb blocks.  Encoder variants 0, 6 and 7 only.  live_blocks != NULL: descriptors made on the device
+// (blocks[0] is block b0 of the batch): enc_batch_live_kernel, whose workgroups at or past *live_blocks leave at once; the layout
+// follows nb all the same.
 inline int launch_batch_encode_kernels(tsqa_ctx* c, const uint8_t* in, const EncBatchBlock* blocks, uint32_t nb, uint32_t ext,
-                                       uint8_t* slots, uint32_t* sizes, int32_t* status, hipStream_t s)
+                                       uint8_t* slots, uint32_t* sizes, int32_t* status, hipStream_t s, uint32_t b0 = 0u,
+                                       const uint32_t* live_blocks = nullptr)
 {
     static StagedFamily<decltype(&enc_batch_kernel<true, true>)> staged = TSQ_STAGED_FAMILY(enc_batch_kernel, StageCfgT);
+    static StagedFamily<decltype(&enc_batch_live_kernel<true, true>)> staged_live = TSQ_STAGED_FAMILY(enc_batch_live_kernel, StageCfgT);
     const int v = c->enc_variant;
     if (v != 0 && v != 6 && v != 7) { c->set_error("kernel variant %d does not encode batches (0, 6 and 7 do)", v); return TSQA_ERR_ARG; }
+    if (live_blocks) return launch_staged(c, staged_live, ext, nb, s, in, blocks, slots, sizes, c->tables, status, b0, live_blocks);
     return launch_staged(c, staged, ext, nb, s, in, blocks, slots, sizes, c->tables, status);
 }
 

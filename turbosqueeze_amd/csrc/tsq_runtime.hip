@@ -143,6 +143,7 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     c->range_up.destroy(); c->batch_up.destroy();
     (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
     (void)hipFree(c->batch_status); (void)hipFree(c->batch_items); (void)hipFree(c->batch_live);
+    (void)hipFree(c->table_blocks); (void)hipFree(c->table_launch_item);
     delete c;
 }
 
@@ -268,6 +269,27 @@ int tsqa_ctx::reserve_batch(size_t n_items)
     TSQ_HIP(this, hipMalloc(&batch_items, want * sizeof(BatchItem)));
     TSQ_HIP(this, hipMalloc(&batch_live, sizeof(uint32_t)));
     cap_batch = want;
+    return TSQA_OK;
+}
+
+// Scratch of the compress from device tables (tsq_internal.h), grown on demand as reserve_batch grows its own.
+int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches)
+{
+    (void)hipSetDevice(device);
+    if (n_blocks <= cap_table_blocks && n_launches <= cap_table_launches) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch: a call enqueued on any stream may still be using them)
+    if (n_blocks > cap_table_blocks) {
+        (void)hipFree(table_blocks); table_blocks = nullptr; cap_table_blocks = 0;
+        size_t want = 256; while (want < n_blocks) want *= 2;
+        TSQ_HIP(this, hipMalloc(&table_blocks, want * sizeof(EncBatchBlock)));
+        cap_table_blocks = want;
+    }
+    if (n_launches > cap_table_launches) {
+        (void)hipFree(table_launch_item); table_launch_item = nullptr; cap_table_launches = 0;
+        size_t want = 16; while (want < n_launches) want *= 2;
+        TSQ_HIP(this, hipMalloc(&table_launch_item, want * sizeof(uint32_t)));
+        cap_table_launches = want;
+    }
     return TSQA_OK;
 }
 
@@ -1092,7 +1114,8 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
         else
             hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
                                c->batch_at, c->frame_at, d_sizes, d_status);
-        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out);
+        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out, 0u,
+                           (const uint32_t*)nullptr);
     }
     TSQ_HIP(c, up.commit(s));                            // (behind a partial batch too)
     if (rc) return rc;
@@ -1136,12 +1159,7 @@ extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size
 
 // ---- packed batches: the items' containers one after the other in a dense arena, their places made on the device ----
 
-extern "C" size_t tsqa_batch_bound(size_t n)
-{
-    // the header, then per block its frame word and a stream of at most every byte a literal of its own, never more than a slot
-    const size_t full = n / kBlockSize, rest = n % kBlockSize, worst = 11 + rest + (rest >> 3) + (rest >> 1);
-    return kHeaderSize + full * (kFrameWordSize + (size_t)kSlotSize) + (rest ? kFrameWordSize + (worst < kSlotSize ? worst : (size_t)kSlotSize) : 0);
-}
+extern "C" size_t tsqa_batch_bound(size_t n) { return (size_t)batch_bound(n); }
 
 static bool packed_align_ok(uint32_t align) { return align >= 1 && align <= 4096 && (align & (align - 1)) == 0; }
 
@@ -1202,6 +1220,97 @@ extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t 
     TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     return finish_sync(c, s, "compress_batch_packed");
+}
+
+// ---- packed compress whose item table is made on the device from tables in device memory ----
+
+constexpr uint64_t kTablesInMax = 1ull << 48;    // in_size above this is refused: the block sums then stay below 2^59
+
+extern "C" int tsqa_plan_compress_tables(const uint64_t* in_offsets, const uint64_t* in_sizes, uint32_t n_items, uint64_t in_size,
+                                         uint32_t align, uint32_t cap_blocks, uint64_t* first_block, int32_t* item_status, uint64_t* bound,
+                                         uint32_t* n_fit)
+{
+    if (!in_offsets || !in_sizes || !first_block || !item_status || !bound || !n_fit || n_items == 0 || !packed_align_ok(align) ||
+        in_size > kTablesInMax) return TSQA_ERR_ARG;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t fb = 0, room = 0;
+    uint32_t fit = n_items;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const uint64_t at = in_offsets[i], n = in_sizes[i];
+        const bool ok = n >= 1 && n <= in_size && at <= in_size - n;
+        const uint64_t nb = ok ? (n + kBlockSize - 1) / kBlockSize : 0;
+        first_block[i] = fb;
+        if (ok && fit == n_items && fb + nb > cap_blocks) fit = i;           // (the first unfit item ends the prefix)
+        item_status[i] = !ok ? TSQA_ERR_ARG : i >= fit ? TSQA_ERR_OVERFLOW : TSQA_OK;
+        fb += nb;
+        if (ok) room += (batch_bound(n) + mask) & ~mask;
+    }
+    first_block[n_items] = fb;
+    *bound = room;
+    *n_fit = fit;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
+                                                       const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
+                                                       uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                       uint64_t* d_first_block, uint64_t* d_bound, int32_t* d_item_status, int32_t* d_status,
+                                                       void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    const char* const who = "compress_batch_packed_tables";
+    if (!d_in || !d_in_offsets || !d_in_sizes || !d_offsets || !d_sizes || !d_first_block || !d_item_status || !d_status) {
+        c->set_error("%s: null pointer", who);
+        return TSQA_ERR_ARG;
+    }
+    if (n_items == 0) { c->set_error("%s: no items", who); return TSQA_ERR_ARG; }
+    if (!packed_align_ok(align)) { c->set_error("%s: align %u is not a power of two from 1 to 4096", who, align); return TSQA_ERR_ARG; }
+    if ((uint64_t)in_size > kTablesInMax) { c->set_error("%s: in_size above 2^48", who); return TSQA_ERR_ARG; }
+    if (d_out ? (out_size < kHeaderSize || cap_blocks == 0) : out_size != 0) {
+        c->set_error("%s: an arena needs out_size >= 16 and cap_blocks above 0; measuring takes d_out NULL and out_size 0", who);
+        return TSQA_ERR_ARG;
+    }
+    if (!batch_encoder_ok(c, who)) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    // the launches are sized by cap_blocks as compress_batch_enqueue sizes them by the planned count: at most 2 x n_cus blocks each
+    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    if (d_out) {
+        if (int rc = c->reserve(cap_blocks < budget ? cap_blocks : budget, true, true, true)) return rc;
+        if (int rc = c->reserve_tables(cap_blocks, ((size_t)cap_blocks + budget - 1) / budget)) return rc;
+    }
+    const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(batch_measure_tables_kernel, per_item, dim3(256), 0, s, c->batch_items, n_items, d_in_offsets, d_in_sizes,
+                       (uint64_t)in_size, d_item_status);
+    // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts.  Measuring: nothing fits, and the kernel
+    //  writes the two arena tables itself)
+    hipLaunchKernelGGL(batch_layout_tables_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, d_out ? cap_blocks : 0u,
+                       d_out ? (uint64_t*)nullptr : d_offsets, d_sizes, d_first_block, d_bound, d_item_status, c->batch_live, d_status);
+    if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
+    const BatchItem* const di = c->batch_items;
+    const uint32_t* const live = c->batch_live;
+    hipLaunchKernelGGL(batch_enc_blocks_kernel, dim3((uint32_t)(((uint64_t)cap_blocks + 255u) / 256u)), dim3(256), 0, s, di, n_items,
+                       static_cast<const uint64_t*>(d_first_block), live, budget, c->table_blocks, c->table_launch_item);
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
+    uint32_t l = 0;
+    for (uint64_t b0 = 0; b0 < cap_blocks; b0 += budget, ++l) {
+        const uint32_t nb = (uint32_t)(cap_blocks - b0 < budget ? cap_blocks - b0 : budget);
+        ProfSpan span(c, 0, s);
+        const int rc = launch_batch_encode_kernels(c, in, c->table_blocks + b0, nb, ext, c->slots, c->sizes, d_status, s, (uint32_t)b0, live);
+        if (rc) { span.cancel(); return rc; }
+        span.end();
+        hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
+                           l, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
+                           d_offsets, d_sizes, d_item_status, d_status);
+        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, static_cast<const uint8_t*>(c->slots),
+                           static_cast<const uint32_t*>(c->sizes), static_cast<const uint64_t*>(c->frame_at), out, (uint32_t)b0, live);
+    }
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
 }
 
 // What every batch decompress with host-planned items starts with (`who`: the caller, for the error texts): the plan, an upload slot
