@@ -132,7 +132,9 @@ int tsqa_decompress_device_async(tsqa_ctx *ctx, const void *d_in, size_t n, uint
  * tsqa_encode_blocks_async: block b of the call is read at d_in + b * stride; every block is TSQ_BLOCK_SZ long
  * except the last (last_len), and each is IMMEDIATELY followed by its look-ahead bytes (the first 128 bytes of
  * the block that follows it in the job; zeros after the job's last block) -- so stride = TSQ_BLOCK_SZ for one
- * contiguous buffer, TSQ_BLOCK_SZ + 128 for a shard that holds every N-th block.  Stream b lands at
+ * contiguous buffer, TSQ_BLOCK_SZ + 128 for a shard that holds every N-th block.  With a stride in between, the call's last block
+ * sees stride - TSQ_BLOCK_SZ look-ahead bytes, then zeros; with stride = TSQ_BLOCK_SZ it sees zeros, whatever follows the buffer.
+ * What lies behind those bytes changes no stream.  Stream b lands at
  * d_slots + b * TSQ_OUTPUT_SZ, its size in d_sizes[b] (both device memory).  Replaces tsqInit + tsqEncode per
  * owned block (tsq_threads.cpp:176-177).
  */
@@ -161,7 +163,9 @@ int tsqa_decode_blocks_async(tsqa_ctx *ctx, const void *d_streams, const tsqa_fr
 /* The gather / scatter that goes with them: one DMA per owned block between its slot in HBM (b * TSQ_OUTPUT_SZ) and
  * its frame in a container in HOST memory (pinned or hipHostRegister'ed for full DMA speed).  frame_at[b] is the
  * container offset of block b's three frame bytes (16 + sum over earlier blocks of 3 + size); sizes and frame_at are
- * host arrays.  to_host also writes the frame bytes (size | ext << 23, tsq_threads.cpp:218-219). */
+ * host arrays.  to_host also writes the frame bytes (size | ext << 23, tsq_threads.cpp:218-219).  Both check every size (3 to
+ * TSQ_OUTPUT_SZ) before the first byte is written or the first copy enqueued, as tsqa_sharded_place_async does: a refusal
+ * (TSQA_ERR_ARG from to_host, TSQA_ERR_FORMAT from from_host) leaves the host container and d_streams as they were. */
 int tsqa_frames_to_host_async(tsqa_ctx *ctx, const void *d_slots, const uint32_t *sizes, const uint64_t *frame_at,
                               uint32_t n_blocks, uint32_t ext, void *host_container, void *hip_stream);
 int tsqa_frames_from_host_async(tsqa_ctx *ctx, const void *host_container, const uint64_t *frame_at, const uint32_t *sizes,

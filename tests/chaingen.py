@@ -69,6 +69,15 @@ def refusal_code(stream):
     return ERR_FORMAT if len(stream) < 3 or int.from_bytes(stream[:3], "little") > BLOCK else ERR_STREAM
 
 
+def twin_name(v):
+    """the v-th choice among the catalogue's invalid twins that the library refuses with TSQA_ERR_STREAM, that are more than 100
+    bytes long and claim 1 to 20 000 bytes (Gen.twin's selection; tests/shardgen.py places the same twins in a sharded container)"""
+    names = sorted(n for n, (_, st) in streamgen.CATALOGUE.invalid.items()
+                   if refusal_code(st) == ERR_STREAM and len(st) > 100 and 0 < int.from_bytes(st[:3], "little") <= 20_000)
+    assert len(names) >= 8
+    return names[(5 * v + 1) % len(names)]
+
+
 class Link:
     """one call: `kind`, `shape`, `fail` (None, "twin", "room" or "count"), `want_status`, and the kind's own fields"""
 
@@ -136,10 +145,7 @@ class Gen:
         """a one-block container around an invalid twin of the catalogue that the library refuses with TSQA_ERR_STREAM -> (name,
         container, the size its header claims); the oracle refuses it too"""
         def make():
-            names = sorted(n for n, (_, st) in streamgen.CATALOGUE.invalid.items()
-                           if refusal_code(st) == ERR_STREAM and len(st) > 100 and 0 < int.from_bytes(st[:3], "little") <= 20_000)
-            assert len(names) >= 8
-            name = names[(5 * v + 1) % len(names)]
+            name = twin_name(v)
             ext, st = streamgen.CATALOGUE.invalid[name]
             blob = np.frombuffer(streamgen.bad_container(ext, st), dtype=np.uint8).copy()
             assert self.oracle.decompress(blob) is None, name

@@ -575,8 +575,10 @@ extern "C" int tsqa_frames_to_host_async(tsqa_ctx* c, const void* d_slots, const
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     uint8_t* base = static_cast<uint8_t*>(host_container);
-    for (uint32_t b = 0; b < n_blocks; ++b) {
+    // every size is checked before anything is written or enqueued (no partial container on an error)
+    for (uint32_t b = 0; b < n_blocks; ++b)
         if (!stream_len_ok(sizes[b])) { c->set_error("frames_to_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_ARG; }
+    for (uint32_t b = 0; b < n_blocks; ++b) {
         uint8_t* p = base + frame_at[b];
         write_frame(p, sizes[b], ext);
         TSQ_HIP(c, hipMemcpyAsync(p + kFrameWordSize, static_cast<const uint8_t*>(d_slots) + (size_t)b * kSlotSize, sizes[b], hipMemcpyDeviceToHost, s));
@@ -592,8 +594,10 @@ extern "C" int tsqa_frames_from_host_async(tsqa_ctx* c, const void* host_contain
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint8_t* base = static_cast<const uint8_t*>(host_container);
-    for (uint32_t b = 0; b < n_blocks; ++b) {
+    // every size is checked before a copy is enqueued (a refusal writes nothing to d_streams)
+    for (uint32_t b = 0; b < n_blocks; ++b)
         if (!stream_len_ok(sizes[b])) { c->set_error("frames_from_host: block %u has size %u", b, sizes[b]); return TSQA_ERR_FORMAT; }
+    for (uint32_t b = 0; b < n_blocks; ++b) {
         TSQ_HIP(c, hipMemcpyAsync(static_cast<uint8_t*>(d_streams) + (size_t)b * kSlotSize, base + frame_at[b] + kFrameWordSize, sizes[b], hipMemcpyHostToDevice, s));
     }
     return TSQA_OK;
