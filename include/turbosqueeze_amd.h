@@ -488,6 +488,59 @@ int tsqa_compress_batch_packed_tables_async(tsqa_ctx *ctx, const void *d_in, siz
                                             void *hip_stream);
 
 /*
+ * Short blocks: ONE container whose blocks are block_len bytes long instead of TSQ_BLOCK_SZ.  A job's speed follows its block
+ * count -- a block is one serial chain on one workgroup -- and tsqa_compress_device leaves a mid-size buffer with few: 64 MiB are 16
+ * blocks on a chip of 256 CUs.  The format allows any block length up to TSQ_BLOCK_SZ (block k starts where the blocks before it
+ * end), so every decode entry point of this library reads such a container: whole, batch, range and record reads, and
+ * tsqDecompress / tsqDecompress_MT.  The reference's readers append the blocks as they come and take it too (INTEGRATION.md,
+ * section 4, says what was tried).  The price is ratio: a block finds no match in the bytes before it (the table is there as well).
+ *
+ * tsqa_plan_split: host only.  block_len: a power of two from 2^12 to 2^22.  *n_blocks = ceil(n / block_len); *bound = the room
+ *   that always holds the container: 16, then per block of k bytes 3 + min(TSQ_OUTPUT_SZ, 11 + k + k/8 + k/2) (tsqa_batch_bound's
+ *   term per block; with block_len = TSQ_BLOCK_SZ, tsqa_batch_bound(n)).  TSQA_ERR_ARG for n == 0, a bad block_len, a block count
+ *   that does not fit 32 bits, or a NULL pointer.
+ *
+ * tsqa_compress_device_split_async: the container is the header (n_blocks, n), then block b = the bytes [b * block_len,
+ *   min(n, (b + 1) * block_len)), encoded as tsqa_compress_device encodes a block: its look-ahead runs on into the bytes that
+ *   follow it in the input and sees zeros past n.  So block_len = TSQ_BLOCK_SZ gives tsqa_compress_device's container byte for byte.
+ *   d_block_sizes (device, may be NULL): n_blocks words, word b = block b's stream length (what tsqa_decompress_device_sized*
+ *   takes); complete whatever fits.  A header or frame is written only if it ends at or before out_cap, and nothing at or past
+ *   d_out + out_cap is written; *d_out_size = the size needed, TSQA_ERR_OVERFLOW in *d_status when it exceeds out_cap, and a retry
+ *   with that much room succeeds.  TSQA_ERR_ARG, before anything is enqueued or written: tsqa_plan_split's refusals, a NULL
+ *   pointer other than d_block_sizes, out_cap < 16 + 6 * n_blocks, an encoder variant other than 0, 6 or 7.  The blocks are encoded
+ *   in launches of at most 2 x CUs, as a batch's are, with the block descriptors made on the device: nothing is uploaded, and the
+ *   scratch does not grow with n (it grows as in the batch calls: the call first waits for the device).
+ * tsqa_compress_device_split: the same, then waits; *out_size (host) = the size needed, behind TSQA_ERR_OVERFLOW too.
+ */
+int tsqa_plan_split(size_t n, uint32_t block_len, uint32_t *n_blocks, size_t *bound);
+int tsqa_compress_device_split_async(tsqa_ctx *ctx, const void *d_in, size_t n, uint32_t block_len, void *d_out, size_t out_cap,
+                                     uint64_t *d_out_size, uint32_t *d_block_sizes, int32_t *d_status, uint32_t ext, void *hip_stream);
+int tsqa_compress_device_split(tsqa_ctx *ctx, const void *d_in, size_t n, uint32_t block_len, void *d_out, size_t out_cap,
+                               size_t *out_size, uint32_t *d_block_sizes, uint32_t ext, void *hip_stream);
+
+/*
+ * tsqa_decompress_device_sized_async: tsqa_decompress_device_async with the frame walk made in parallel.  A frame carries no
+ *   marker, so the plain walk is one lane reading frame after frame (16 384 dependent loads for 1 GiB in 64 KiB blocks); with
+ *   d_block_sizes (device, n_blocks words: what the split compress left, or any table of the frames' stream lengths) every frame's
+ *   place is a prefix sum.  NOTHING in the table is trusted: each frame is looked up where the table puts it -- a size outside
+ *   [3, TSQ_OUTPUT_SZ] refuses the container and counts as 0, so no sum can wrap; the frame's six bytes must lie inside n before
+ *   one of them is read; the frame must pass the plain walk's checks; and the length in its frame word must be the table's.  Frame
+ *   0 is at 16 whatever the table says, so where every frame agrees, every place is the plain walk's.  For a true table, status,
+ *   size and output are tsqa_decompress_device_async's, for every container, valid or not; a false table gives TSQA_ERR_FORMAT
+ *   with *d_out_size = 0 and nothing decoded.  Nothing outside [d_out, d_out + out_cap) is ever written, and no byte at or past
+ *   d_in + n is ever read.  TSQA_ERR_STALL is reported as by tsqa_decompress_device_async.
+ *   The table is read as n_blocks words, the count the CALLER states, and only behind a header that states the same count: a
+ *   container never decides how far the table is read.
+ * tsqa_decompress_device_sized: the waiting form, as tsqa_decompress_device (it reads the header itself, and decodes again by
+ *   itself after TSQA_ERR_STALL).  n_blocks = the words d_block_sizes holds: a header that states another count is refused with
+ *   TSQA_ERR_FORMAT and *out_size = 0 before anything is enqueued, and n_blocks == 0 is TSQA_ERR_ARG.
+ */
+int tsqa_decompress_device_sized_async(tsqa_ctx *ctx, const void *d_in, size_t n, uint32_t n_blocks, const uint32_t *d_block_sizes,
+                                       void *d_out, size_t out_cap, uint64_t *d_out_size, int32_t *d_status, void *hip_stream);
+int tsqa_decompress_device_sized(tsqa_ctx *ctx, const void *d_in, size_t n, uint32_t n_blocks, const uint32_t *d_block_sizes, void *d_out,
+                                 size_t out_cap, size_t *out_size, void *hip_stream);
+
+/*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
  * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
  * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.

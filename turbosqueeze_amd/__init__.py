@@ -29,6 +29,7 @@ from .api import (  # noqa: F401
     plan_item_ranges,
     plan_packed,
     plan_ranges,
+    plan_split,
     source_fingerprint,
     tsq_compress_mt,
     tsq_decode,

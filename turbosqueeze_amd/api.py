@@ -203,6 +203,16 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_compress_batch_packed_tables_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
                                                           C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_batch_packed_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.tsqa_plan_split.restype = C.c_int
+    L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
+    L.tsqa_compress_device_split_async.restype = C.c_int
+    L.tsqa_compress_device_split_async.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp, C.c_uint32, vp]
+    L.tsqa_compress_device_split.restype = C.c_int
+    L.tsqa_compress_device_split.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, szp, vp, C.c_uint32, vp]
+    L.tsqa_decompress_device_sized_async.restype = C.c_int
+    L.tsqa_decompress_device_sized_async.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
+    L.tsqa_decompress_device_sized.restype = C.c_int
+    L.tsqa_decompress_device_sized.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, szp, vp]
     L.tsqa_index_create_batch.restype = C.c_int
     L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
     L.tsqa_index_items.restype = C.c_uint32
@@ -370,6 +380,18 @@ def batch_bound(n: int) -> int:
         cap += 3 + min(OUTPUT_SZ, 11 + k + (k >> 3) + (k >> 1))
         left -= k
     return cap
+
+
+def plan_split(n: int, block_len: int):
+    """tsqa_plan_split (host only): an input of n bytes cut into blocks of block_len, a power of two from 2^12 to 2^22 -> (the block
+    count, the room that always holds the container).  Raises TsqError(3) when refused."""
+    nb, bound = C.c_uint32(0), C.c_size_t(0)
+    if not 0 <= n < 1 << 64 or not 0 <= block_len < 1 << 32:
+        raise TsqError(3, "tsqa_plan_split refused the arguments")
+    rc = lib().tsqa_plan_split(n, block_len, C.byref(nb), C.byref(bound))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_split refused the arguments")
+    return int(nb.value), int(bound.value)
 
 
 def plan_packed(sizes, align: int = 16):
@@ -766,6 +788,73 @@ class DeviceCodec:
 
     def last_size_status(self):
         return int(self._size.item()), int(self._status.item())
+
+    # ---- short blocks: one container cut every block_len bytes, and the decompress that walks its frames from a size table ----
+    def compress_split(self, src, ext: int, block_len: int, out=None, block_sizes: bool = False):
+        """compress with blocks of block_len bytes (a power of two from 2^12 to 2^22) instead of 4 MiB: one .tsq container that
+        every decode entry point reads, made and read with as many workgroups as it has blocks.  -> the container (a view of `out`,
+        or of a new tensor of plan_split's bound); block_sizes=True: -> (container, the blocks' stream lengths: an int32 CUDA tensor,
+        one per block, for decompress_sized).  An `out` that is too small raises TsqError(6) with .needed = the bytes a retry needs."""
+        n = src.numel()
+        nb, bound = plan_split(n, block_len)
+        if out is None:
+            out = self.torch.empty(bound, dtype=self.torch.uint8, device=self.device)
+        table = self.torch.empty(nb, dtype=self.torch.int32, device=self.device) if block_sizes else None
+        sz = C.c_size_t(0)
+        rc = self.L.tsqa_compress_device_split(self.h, src.data_ptr(), n, int(block_len), out.data_ptr(), out.numel(), C.byref(sz),
+                                               table.data_ptr() if block_sizes else None, int(ext), self._stream())
+        if rc:
+            e = self._err(rc)
+            if rc == 6:
+                e.needed = int(sz.value)
+            raise e
+        return (out[: sz.value], table) if block_sizes else out[: sz.value]
+
+    def compress_split_async(self, src, ext: int, block_len: int, out, d_block_sizes=None) -> None:
+        """tsqa_compress_device_split_async on the current stream, nothing waited for: the container lands in out, its size and the
+        status where compress_async leaves them (last_size_status), the blocks' stream lengths in d_block_sizes (an int32 CUDA
+        tensor of plan_split's block count, or None)."""
+        if d_block_sizes is not None:
+            self._check_table(d_block_sizes, plan_split(src.numel(), block_len)[0], at_least=True)
+        rc = self.L.tsqa_compress_device_split_async(self.h, src.data_ptr(), src.numel(), int(block_len), out.data_ptr(), out.numel(),
+                                                     self._size.data_ptr(), d_block_sizes.data_ptr() if d_block_sizes is not None else None,
+                                                     self._status.data_ptr(), int(ext), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def decompress_sized(self, blob, block_sizes, out=None):
+        """decompress with the frame walk made in parallel from block_sizes (an int32 CUDA tensor: every block's stream length, as
+        compress_split(..., block_sizes=True) gives it).  The table is checked against the container: a false one raises
+        TsqError(4), and so does a container whose header states another block count than the table has entries."""
+        n = blob.numel()
+        self._check_table(block_sizes, None)
+        if out is None:
+            total = int.from_bytes(bytes(blob[8:16].cpu().numpy()), "little")
+            out = self.torch.empty(max(total, 1), dtype=self.torch.uint8, device=self.device)
+        sz = C.c_size_t(0)
+        rc = self.L.tsqa_decompress_device_sized(self.h, blob.data_ptr(), n, block_sizes.numel(), block_sizes.data_ptr(), out.data_ptr(),
+                                                 out.numel(), C.byref(sz), self._stream())
+        if rc:
+            raise self._err(rc)
+        return out[: sz.value]
+
+    def _check_table(self, table, n_blocks, at_least=False):
+        """a size table is a contiguous int32 tensor on the codec's device, of n_blocks entries where the count is stated (at_least:
+        of no fewer)"""
+        if (table.dtype != self.torch.int32 or not table.is_cuda or table.device != self.device or table.dim() != 1 or
+                not table.is_contiguous() or table.numel() == 0 or table.numel() >= 1 << 32):
+            raise TsqError(3, "block_sizes must be a contiguous 1-D int32 tensor on the codec's device")
+        if n_blocks is not None and (table.numel() < n_blocks if at_least else table.numel() != n_blocks):
+            raise TsqError(3, f"block_sizes holds {table.numel()} entries, not n_blocks = {n_blocks}")
+
+    def decompress_sized_async(self, blob, n_blocks: int, d_block_sizes, out) -> None:
+        """tsqa_decompress_device_sized_async on the current stream, nothing waited for: decompress_async with the table, which
+        must hold exactly n_blocks entries."""
+        self._check_table(d_block_sizes, n_blocks)
+        rc = self.L.tsqa_decompress_device_sized_async(self.h, blob.data_ptr(), blob.numel(), n_blocks, d_block_sizes.data_ptr(), out.data_ptr(),
+                                                       out.numel(), self._size.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
 
     def index(self, blob) -> RangeIndex:
         """An index of the .tsq container `blob` (uint8 CUDA tensor) for range reads: index(blob).read(offset, length)."""

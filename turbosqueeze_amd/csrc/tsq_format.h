@@ -35,13 +35,24 @@ __host__ __device__ inline void write_frame(uint8_t* p, uint32_t stream_len, uin
     store_le(p, stream_len | (ext ? kFrameExtBit : 0u), kFrameWordSize);
 }
 
-// Room that always holds the container of an n-byte item (tsqa_batch_bound): the header, then per block its frame word and a stream
-// of at most every byte a literal of its own, never more than a slot.
-__host__ __device__ inline uint64_t batch_bound(uint64_t n)
+// Room that always holds the frame of a block of k bytes: its frame word and a stream of at most every byte a literal of its own,
+// never more than a slot (a full block: 3 + TSQ_OUTPUT_SZ).
+__host__ __device__ inline uint64_t block_bound(uint64_t k)
 {
-    const uint64_t full = n / kBlockSize, rest = n % kBlockSize, worst = 11 + rest + (rest >> 3) + (rest >> 1);
-    return kHeaderSize + full * (kFrameWordSize + (uint64_t)kSlotSize) + (rest ? kFrameWordSize + (worst < kSlotSize ? worst : (uint64_t)kSlotSize) : 0);
+    const uint64_t worst = 11 + k + (k >> 3) + (k >> 1);
+    return kFrameWordSize + (worst < kSlotSize ? worst : (uint64_t)kSlotSize);
 }
+
+// Room that always holds the container of n bytes cut into blocks of block_len (tsqa_plan_split): the header, then block_bound
+// per block.
+__host__ __device__ inline uint64_t split_bound(uint64_t n, uint64_t block_len)
+{
+    const uint64_t full = n / block_len, rest = n % block_len;
+    return kHeaderSize + full * block_bound(block_len) + (rest ? block_bound(rest) : 0);
+}
+
+// Room that always holds the container of an n-byte item (tsqa_batch_bound).
+__host__ __device__ inline uint64_t batch_bound(uint64_t n) { return split_bound(n, kBlockSize); }
 
 // read_header's verdicts.  The first two are the reader's own refusals (tsq_threads.cpp:732-768); an implausible header has block
 // counts that a container of n bytes cannot hold: more blocks than 6-byte frames fit, or more output than they can make.

@@ -12,6 +12,7 @@
 #include "tsq_container.cuh"
 #include "tsq_format.h"
 #include "tsq_serial.cuh"
+#include "tsq_split.cuh"
 #include "tsq_launch.cuh"
 
 #include <algorithm>
@@ -477,12 +478,14 @@ extern "C" int tsqa_compress_device(tsqa_ctx* c, const void* d_in, size_t n, voi
     return status_to_rc(c, st, "compress");
 }
 
-// (variant < 0: the context's decode variant; the retry after TSQA_ERR_STALL passes 4 without touching the context's setting)
+// (variant < 0: the context's decode variant; the retry after TSQA_ERR_STALL passes 4 without touching the context's setting.
+//  sized: the frame walk is made in parallel from d_block_sizes, frame_walk_sized_kernel; else that table is not looked at.)
 static int decompress_device_async_impl(tsqa_ctx* c, const void* d_in, size_t n, uint32_t n_blocks, void* d_out,
-                                        size_t out_cap, uint64_t* d_out_size, int32_t* d_status, void* hip_stream, int variant)
+                                        size_t out_cap, uint64_t* d_out_size, int32_t* d_status, void* hip_stream, int variant,
+                                        bool sized = false, const uint32_t* d_block_sizes = nullptr)
 {
     if (!c) return TSQA_ERR_ARG;
-    if (!d_in || !d_out || !d_out_size || !d_status || n < 16 || n_blocks == 0) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
+    if (!d_in || !d_out || !d_out_size || !d_status || n < 16 || n_blocks == 0 || (sized && !d_block_sizes)) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     int rc = c->reserve(n_blocks, false, false, false, s);
@@ -490,8 +493,12 @@ static int decompress_device_async_impl(tsqa_ctx* c, const void* d_in, size_t n,
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     ProfSpan span(c, 3, s);
-    hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
-                       (uint64_t)out_cap, c->frames, d_out_size, d_status);
+    if (sized)                           // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+        hipLaunchKernelGGL(frame_walk_sized_kernel, dim3(1), dim3(256), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
+                           d_block_sizes, (uint64_t)out_cap, c->frames, d_out_size, d_status);
+    else
+        hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
+                           (uint64_t)out_cap, c->frames, d_out_size, d_status);
     rc = c->launch_decode(d_in, n_blocks, d_out, d_status, s, variant);
     span.end();
     return rc;
@@ -501,6 +508,12 @@ extern "C" int tsqa_decompress_device_async(tsqa_ctx* c, const void* d_in, size_
                                             size_t out_cap, uint64_t* d_out_size, int32_t* d_status, void* hip_stream)
 {
     return decompress_device_async_impl(c, d_in, n, n_blocks, d_out, out_cap, d_out_size, d_status, hip_stream, -1);
+}
+
+extern "C" int tsqa_decompress_device_sized_async(tsqa_ctx* c, const void* d_in, size_t n, uint32_t n_blocks, const uint32_t* d_block_sizes,
+                                                  void* d_out, size_t out_cap, uint64_t* d_out_size, int32_t* d_status, void* hip_stream)
+{
+    return decompress_device_async_impl(c, d_in, n, n_blocks, d_out, out_cap, d_out_size, d_status, hip_stream, -1, true, d_block_sizes);
 }
 
 // ---- sharded operation: a device owns some of a job's blocks ----
@@ -535,11 +548,12 @@ extern "C" int tsqa_decode_blocks_async(tsqa_ctx* c, const void* d_streams, cons
     return c->launch_decode_frames(d_streams, reinterpret_cast<const FrameInfo*>(d_frames), n_blocks, d_out, d_status, s);
 }
 
-extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, void* d_out, size_t out_cap,
-                                      size_t* out_size, void* hip_stream)
+// Both waiting forms (sized: tsqa_decompress_device_sized, the frame walk from the table_words words at d_block_sizes).
+static int decompress_device_wait(tsqa_ctx* c, const void* d_in, size_t n, void* d_out, size_t out_cap, size_t* out_size, void* hip_stream,
+                                  bool sized, uint32_t table_words, const uint32_t* d_block_sizes)
 {
     if (!c || !out_size) return TSQA_ERR_ARG;
-    if (!d_in || n < 16) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
+    if (!d_in || n < 16 || (sized && (!d_block_sizes || table_words == 0))) { c->set_error("decompress: bad argument"); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     uint8_t head[kHeaderSize];
@@ -551,17 +565,32 @@ extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, v
     if (total > out_cap) { c->set_error("decompress: output capacity %zu < %llu", out_cap, (unsigned long long)total); return TSQA_ERR_ARG; }
     // (an implausible header is refused with *out_size = 0, as the frame walk would refuse it)
     if (h != kHeaderOk) { *out_size = 0; c->set_error("decompress: more blocks or bytes than a container of %zu B can hold", n); return TSQA_ERR_FORMAT; }
+    // (the table holds as many words as the caller says, not as many as the container says: no kernel walks a table by a count
+    //  the caller has not vouched for)
+    if (sized && nb != table_words) { *out_size = 0; c->set_error("decompress: the header states %u blocks, the size table holds %u", nb, table_words); return TSQA_ERR_FORMAT; }
     uint64_t sz = 0; int32_t st = 0;
     // after TSQA_ERR_STALL -- a workgroup of a several-workgroups-per-block decode did not get onto the GPU in time (other work held
     // the CUs): the container is not at fault -- once more with one workgroup per block, which waits for nobody
     for (int variant : {-1, 4}) {
-        if (int rc = decompress_device_async_impl(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s, variant)) return rc;
+        if (int rc = decompress_device_async_impl(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s, variant, sized, d_block_sizes)) return rc;
         TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
         if (int rc = read_status(c, s, &st)) return rc;
         if (st != kErrStall) break;
     }
     *out_size = (size_t)sz;
     return status_to_rc(c, st, "decompress");
+}
+
+extern "C" int tsqa_decompress_device(tsqa_ctx* c, const void* d_in, size_t n, void* d_out, size_t out_cap,
+                                      size_t* out_size, void* hip_stream)
+{
+    return decompress_device_wait(c, d_in, n, d_out, out_cap, out_size, hip_stream, false, 0u, nullptr);
+}
+
+extern "C" int tsqa_decompress_device_sized(tsqa_ctx* c, const void* d_in, size_t n, uint32_t n_blocks, const uint32_t* d_block_sizes, void* d_out,
+                                            size_t out_cap, size_t* out_size, void* hip_stream)
+{
+    return decompress_device_wait(c, d_in, n, d_out, out_cap, out_size, hip_stream, true, n_blocks, d_block_sizes);
 }
 
 // Host gather / scatter of a shard's frames (what compression_write_worker and decompression_read_worker do with
@@ -1315,6 +1344,78 @@ extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* 
     }
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
+}
+
+// ---- one container of short blocks: the input cut every block_len bytes, encoded by the batch route ----
+
+extern "C" int tsqa_plan_split(size_t n, uint32_t block_len, uint32_t* n_blocks, size_t* bound)
+{
+    if (!n_blocks || !bound || n == 0 || block_len < 4096u || block_len > kBlockSize || (block_len & (block_len - 1u)) != 0u) return TSQA_ERR_ARG;
+    const uint64_t nb = (uint64_t)n / block_len + ((uint64_t)n % block_len != 0);
+    if (nb > 0xFFFFFFFFull) return TSQA_ERR_ARG;
+    *n_blocks = (uint32_t)nb;
+    *bound = (size_t)split_bound(n, block_len);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_device_split_async(tsqa_ctx* c, const void* d_in, size_t n, uint32_t block_len, void* d_out, size_t out_cap,
+                                                uint64_t* d_out_size, uint32_t* d_block_sizes, int32_t* d_status, uint32_t ext, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    uint32_t n_blocks = 0;
+    size_t bound = 0;
+    if (tsqa_plan_split(n, block_len, &n_blocks, &bound)) {
+        c->set_error("compress_split: no input, a block_len that is no power of two from 2^12 to 2^22, or more than 2^32 - 1 blocks");
+        return TSQA_ERR_ARG;
+    }
+    if (!d_in || !d_out || !d_out_size || !d_status) { c->set_error("compress_split: null pointer"); return TSQA_ERR_ARG; }
+    if (out_cap < kHeaderSize + (uint64_t)kMinFrameSize * n_blocks) { c->set_error("compress_split: output capacity too small"); return TSQA_ERR_ARG; }
+    if (!batch_encoder_ok(c, "compress_split")) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    // the launches are compress_batch_enqueue's: at most 2 x n_cus blocks each, block b in slot b % budget, so the scratch stays
+    // bounded whatever the block count; the descriptors are made on the device, and nothing is uploaded
+    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true, true, true)) return rc;
+    if (int rc = c->reserve_batch(1)) return rc;         // (batch_at[0]: the running frame offset between the launches)
+    if (int rc = c->reserve_tables(n_blocks, 0)) return rc;
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(split_blocks_kernel, dim3((uint32_t)(((uint64_t)n_blocks + 255u) / 256u)), dim3(256), 0, s, (uint64_t)n, block_len, n_blocks,
+                       budget, c->table_blocks);
+    // (no stream of these blocks is longer than block_bound says: short blocks need few copy pieces)
+    const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
+    const uint32_t pieces = (max_stream + kPackPiece - 1) / kPackPiece + 1u;
+    for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget) {
+        const uint32_t nb = (uint32_t)(n_blocks - b0 < budget ? n_blocks - b0 : budget);
+        ProfSpan span(c, 0, s);
+        const int rc = launch_batch_encode_kernels(c, in, c->table_blocks + b0, nb, ext, c->slots, c->sizes, d_status, s);
+        if (rc) { span.cancel(); return rc; }
+        span.end();
+        // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+        hipLaunchKernelGGL(split_pack_scan_kernel, dim3(1), dim3(256), 0, s, static_cast<const uint32_t*>(c->sizes), (uint32_t)b0, nb, n_blocks,
+                           (uint64_t)n, ext, max_stream, out, (uint64_t)out_cap, c->batch_at, c->frame_at, d_out_size, d_block_sizes, d_status);
+        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, static_cast<const uint8_t*>(c->slots),
+                           static_cast<const uint32_t*>(c->sizes), static_cast<const uint64_t*>(c->frame_at), out, 0u, (const uint32_t*)nullptr);
+    }
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_device_split(tsqa_ctx* c, const void* d_in, size_t n, uint32_t block_len, void* d_out, size_t out_cap,
+                                          size_t* out_size, uint32_t* d_block_sizes, uint32_t ext, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!out_size) { c->set_error("compress_split: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    int rc = tsqa_compress_device_split_async(c, d_in, n, block_len, d_out, out_cap, c->d_size, d_block_sizes, c->d_status, ext, s);
+    if (rc) return rc;
+    uint64_t sz = 0; int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
+    if (int rc = read_status(c, s, &st)) return rc;
+    *out_size = (size_t)sz;                              // (the size needed, behind TSQA_ERR_OVERFLOW too)
+    return status_to_rc(c, st, "compress_split");
 }
 
 // What every batch decompress with host-planned items starts with (`who`: the caller, for the error texts): the plan, an upload slot
