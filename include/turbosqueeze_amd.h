@@ -541,6 +541,40 @@ int tsqa_decompress_device_sized(tsqa_ctx *ctx, const void *d_in, size_t n, uint
                                  size_t out_cap, size_t *out_size, void *hip_stream);
 
 /*
+ * The index of a container of short blocks, made from its size table with no host wait.  tsqa_index_create reads the header to
+ * the host, walks the frames on one lane and copies every descriptor back; for a split container none of that is needed.  The
+ * caller knows n_total and block_len, so block b's output starts at b * block_len and the host plans every read from arithmetic
+ * alone; the device places the frames from the table (three plain launches, 256 frames per workgroup, no workgroup waiting for
+ * another) and proves that the container has that geometry.  So compress -> index -> read runs on one stream with no host read.
+ *
+ * tsqa_index_create_sized_async: n = the readable room at d_container, not necessarily the container's size (as
+ *   tsqa_decompress_device_sized_async takes it).  n_blocks = tsqa_plan_split(n_total, block_len)'s count, from the caller's
+ *   numbers and never from the container; d_block_sizes (device): n_blocks words, as tsqa_compress_device_split* leaves them.
+ *   TSQA_ERR_ARG, with nothing enqueued and *out = NULL: a NULL pointer, one of tsqa_plan_split's refusals, n < 16 + 6 * n_blocks.
+ *   Otherwise the call reads no device memory on the host and waits for no stream (it allocates the index's descriptors); it
+ *   enqueues on hip_stream a zero fill of the descriptors and the walk.  tsqa_index_blocks, tsqa_index_total and tsqa_index_items
+ *   answer from the caller's numbers (n_blocks, n_total, 1).
+ *   The verdict, made on the device with NOTHING trusted, is TSQA_ERR_FORMAT when: the header is refused for n, or states another
+ *   block count than n_blocks or another total than n_total; a table word is outside [3, TSQ_OUTPUT_SZ] (it counts as 0 in the
+ *   sums, so none can wrap); a frame's six bytes do not lie inside n (checked before one of them is read); the frame fails the
+ *   plain walk's checks; the length in its frame word is not the table's; or its block's size is not block_len (the last block:
+ *   n_total - (n_blocks - 1) * block_len).  Otherwise it is TSQA_OK, every descriptor is the one tsqa_index_create makes for
+ *   that container, and every read equals the same read through tsqa_index_create.  No byte at or past d_container + n is read.
+ *   tsqa_decompress_ranges* and tsqa_decompress_item_ranges* take the index unchanged (one item).  They must be ordered behind the
+ *   creation: the same stream, or an event.  On a refused index every read gives TSQA_ERR_FORMAT in *d_status and writes no
+ *   destination byte: a one-thread kernel in front of the read hands the verdict on, and the decoders leave when they find it.
+ * tsqa_index_create_sized: the same, then waits for hip_stream: TSQA_ERR_FORMAT and no index when the verdict refuses.
+ * tsqa_index_d_status: the device word that holds the verdict (to read it: order the read behind the creation); NULL for an index
+ *   made by tsqa_index_create or tsqa_index_create_batch, and for NULL.  It lives as long as the index.
+ * The index holds d_container and must be destroyed before it; d_block_sizes is not needed once the walk has run.
+ */
+int tsqa_index_create_sized_async(tsqa_ctx *ctx, const void *d_container, size_t n, uint64_t n_total, uint32_t block_len,
+                                  const uint32_t *d_block_sizes, tsqa_index **out, void *hip_stream);
+int tsqa_index_create_sized(tsqa_ctx *ctx, const void *d_container, size_t n, uint64_t n_total, uint32_t block_len,
+                            const uint32_t *d_block_sizes, tsqa_index **out, void *hip_stream);
+const int32_t *tsqa_index_d_status(const tsqa_index *idx);
+
+/*
  * Record reads from a batch: many short ranges out of many small containers (pages, records, tensors) that lie in one buffer in
  * HBM -- what tsqa_compress_batch makes.  One index covers the whole batch, a read names its item, and a block that several
  * ranges touch is decoded ONCE for all of them: the cost of a call follows the blocks touched, not the ranges asked for.

@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     Range,
     RangeIndex,
     RangeItem,
+    SizedIndex,
     TsqError,
     batch_bound,
     build_info,

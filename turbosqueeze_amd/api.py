@@ -213,6 +213,12 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_device_sized_async.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_device_sized.restype = C.c_int
     L.tsqa_decompress_device_sized.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, szp, vp]
+    L.tsqa_index_create_sized_async.restype = C.c_int
+    L.tsqa_index_create_sized_async.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint32, vp, C.POINTER(vp), vp]
+    L.tsqa_index_create_sized.restype = C.c_int
+    L.tsqa_index_create_sized.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint32, vp, C.POINTER(vp), vp]
+    L.tsqa_index_d_status.restype = vp
+    L.tsqa_index_d_status.argtypes = [vp]
     L.tsqa_index_create_batch.restype = C.c_int
     L.tsqa_index_create_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.POINTER(vp), vp]
     L.tsqa_index_items.restype = C.c_uint32
@@ -343,6 +349,34 @@ class RangeIndex:
         triples, out, views = self._packed(ranges, out)
         self.read_into(triples, out, sync=False)
         return out[:sum(int(ln) for _, ln in ranges)], views
+
+
+class SizedIndex(RangeIndex):
+    """The index of a container of short blocks, made on the device from its table of stream sizes (tsqa_index_create_sized*): the
+    caller states the geometry (total bytes cut every block_len), the device places the frames and proves it.  sync=False: made on
+    the current torch stream with nothing waited for, so compress_split_async -> index_sized -> read_many_async is one chain; a
+    container that is refused then shows in status(), and in the status of every read.  Holds references to the container and the
+    table, which must not change while the index is made or used."""
+
+    def __init__(self, codec: "DeviceCodec", blob, total: int, block_len: int, block_sizes, sync: bool = True):
+        self.codec, self.blob, self.table, self.L = codec, blob, block_sizes, codec.L
+        self.h = C.c_void_p()
+        codec._check_table(block_sizes, plan_split(total, block_len)[0], at_least=True)
+        make = self.L.tsqa_index_create_sized if sync else self.L.tsqa_index_create_sized_async
+        rc = make(codec.h, blob.data_ptr(), blob.numel(), int(total), int(block_len), block_sizes.data_ptr(), C.byref(self.h), codec._stream())
+        if rc:
+            raise codec._err(rc)
+        self.n_blocks = int(self.L.tsqa_index_blocks(self.h))
+        self.total = int(self.L.tsqa_index_total(self.h))
+        self.block_len = int(block_len)
+
+    def status(self) -> int:
+        """The walk's verdict (tsqa_index_d_status), 0 or 4, as a read of nothing on the current stream reports it: waits for
+        that stream."""
+        if not self.h or not self.L.tsqa_index_d_status(self.h):
+            raise TsqError(3, "the index is closed")
+        one = self.codec.torch.empty(1, dtype=self.codec.torch.uint8, device=self.codec.device)
+        return int(self.L.tsqa_decompress_ranges(self.codec.h, self.h, None, 0, one.data_ptr(), 1, self.codec._stream()))
 
 
 class BatchItem(C.Structure):
@@ -859,6 +893,13 @@ class DeviceCodec:
     def index(self, blob) -> RangeIndex:
         """An index of the .tsq container `blob` (uint8 CUDA tensor) for range reads: index(blob).read(offset, length)."""
         return RangeIndex(self, blob)
+
+    def index_sized(self, blob, total: int, block_len: int, block_sizes, sync: bool = True) -> SizedIndex:
+        """An index of the short-block container `blob` of `total` bytes cut every block_len, from block_sizes (an int32 CUDA
+        tensor: what compress_split(..., block_sizes=True) or compress_split_async leaves).  blob may be the whole room the container
+        was compressed into.  sync=True waits and raises TsqError(4) for a container that is not what the table and the geometry
+        say; sync=False runs on the current torch stream with nothing waited for."""
+        return SizedIndex(self, blob, total, block_len, block_sizes, sync)
 
     def index_batch(self, blobs) -> "BatchIndex":
         """One index over many .tsq containers (1-D uint8 CUDA tensors), made in one call: index_batch(blobs).read(item, offset,

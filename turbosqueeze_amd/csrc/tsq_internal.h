@@ -131,7 +131,9 @@ struct tsqa_ctx {
 
 // A container's frame table, kept for range reads (tsqa_index_create), or the frame table of a batch of containers in one buffer
 // (tsqa_index_create_batch): the healthy items' blocks one after the other, stream_at relative to the buffer.  The containers
-// themselves are the caller's.
+// themselves are the caller's.  Or the frame table of a container of short blocks, made on the device from its table of stream
+// sizes (tsqa_index_create_sized*): out_start is the caller's geometry, host_frames stays empty, and `verdict` says on the device
+// whether the container has that geometry.
 struct tsqa_index {
     int device = 0;
     const uint8_t* container = nullptr;
@@ -139,6 +141,10 @@ struct tsqa_index {
     uint32_t n_blocks = 0;
     uint64_t total = 0;
     tsq::FrameInfo* frames = nullptr;          // n_blocks descriptors on the device (frame_walk_kernel)
+    // a sized index only, in the allocation of `frames` behind the descriptors: the group sums of its walk (tsq_index.cuh), which
+    // is why two creations on one stream do not share them, and the walk's verdict, which gates every read (NULL otherwise)
+    uint64_t* group_sum = nullptr;
+    int32_t* verdict = nullptr;
     std::vector<tsqa_frame> host_frames;       // their host copy
     std::vector<uint64_t> out_start;           // n_blocks + 1: where each block's output starts, then the total
     // items (one for a single container): item i owns the blocks [item_first[i], item_first[i + 1]), none when it was refused

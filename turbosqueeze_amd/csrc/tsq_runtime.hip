@@ -13,6 +13,7 @@
 #include "tsq_format.h"
 #include "tsq_serial.cuh"
 #include "tsq_split.cuh"
+#include "tsq_index.cuh"
 #include "tsq_launch.cuh"
 
 #include <algorithm>
@@ -807,6 +808,77 @@ extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n,
     return TSQA_OK;
 }
 
+// The index of a container of short blocks from its table of stream sizes: the host plans from the caller's geometry alone, the
+// device places the frames and proves the geometry (tsq_index.cuh).  Nothing is read back and no stream is waited for.
+extern "C" int tsqa_index_create_sized_async(tsqa_ctx* c, const void* d_container, size_t n, uint64_t n_total, uint32_t block_len,
+                                             const uint32_t* d_block_sizes, tsqa_index** out, void* hip_stream)
+{
+    if (!out) return TSQA_ERR_ARG;
+    *out = nullptr;
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_container || !d_block_sizes) { c->set_error("index_create_sized: null pointer"); return TSQA_ERR_ARG; }
+    uint32_t nb = 0;
+    size_t bound = 0;
+    if (n_total > (uint64_t)SIZE_MAX || tsqa_plan_split((size_t)n_total, block_len, &nb, &bound)) {
+        c->set_error("index_create_sized: no data, a block_len that is no power of two from 2^12 to 2^22, or more than 2^32 - 1 blocks");
+        return TSQA_ERR_ARG;
+    }
+    if (n < kHeaderSize + (uint64_t)kMinFrameSize * nb) { c->set_error("index_create_sized: %zu B cannot hold %u frames", n, nb); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    IndexPtr idx(new (std::nothrow) tsqa_index());
+    if (!idx) { c->set_error("index_create_sized: out of host memory"); return TSQA_ERR_ARG; }
+    idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = n_total;
+    try {
+        idx->out_start.resize((size_t)nb + 1);
+        idx->item_first = {0ull, (uint64_t)nb};
+        idx->item_status = {TSQA_OK};
+    } catch (...) { c->set_error("index_create_sized: out of host memory"); return TSQA_ERR_ARG; }
+    for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = (uint64_t)b * block_len;
+    idx->out_start[nb] = n_total;
+    // one allocation: the descriptors, the group sums, the verdict; all zero in front of the walk
+    const uint32_t n_groups = (uint32_t)(((uint64_t)nb + kIndexGroup - 1u) / kIndexGroup);
+    const size_t frames_bytes = (size_t)nb * sizeof(FrameInfo), bytes = frames_bytes + ((size_t)n_groups + 1u) * sizeof(uint64_t);
+    TSQ_HIP(c, hipMalloc(&idx->frames, bytes));
+    idx->group_sum = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(idx->frames) + frames_bytes);
+    idx->verdict = reinterpret_cast<int32_t*>(idx->group_sum + n_groups);
+    TSQ_HIP(c, hipMemsetAsync(idx->frames, 0, bytes, s));
+    // (workgroups of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+    hipLaunchKernelGGL(index_sum_kernel, dim3(n_groups), dim3(256), 0, s, d_block_sizes, nb, idx->group_sum);
+    hipLaunchKernelGGL(index_scan_kernel, dim3(1), dim3(256), 0, s, idx->container, (uint64_t)n, nb, n_total, idx->group_sum, n_groups, idx->verdict);
+    hipLaunchKernelGGL(index_check_kernel, dim3(n_groups), dim3(256), 0, s, idx->container, (uint64_t)n, nb, n_total, block_len, d_block_sizes,
+                       static_cast<const uint64_t*>(idx->group_sum), idx->frames, idx->verdict);
+    TSQ_HIP(c, hipGetLastError());
+    *out = idx.release();
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_index_create_sized(tsqa_ctx* c, const void* d_container, size_t n, uint64_t n_total, uint32_t block_len,
+                                       const uint32_t* d_block_sizes, tsqa_index** out, void* hip_stream)
+{
+    if (!out) return TSQA_ERR_ARG;
+    tsqa_index* made = nullptr;
+    *out = nullptr;
+    if (int rc = tsqa_index_create_sized_async(c, d_container, n, n_total, block_len, d_block_sizes, &made, hip_stream)) return rc;
+    IndexPtr idx(made);
+    hipStream_t s = stream_of(c, hip_stream);
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, idx->verdict, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    if (st != 0) { c->set_error("index_create_sized: the container is not what the size table and the geometry say (status %d)", st); return TSQA_ERR_FORMAT; }
+    *out = idx.release();
+    return TSQA_OK;
+}
+
+extern "C" const int32_t* tsqa_index_d_status(const tsqa_index* idx) { return idx ? idx->verdict : nullptr; }
+
+// Behind the memset of a read's status word: an index made from a size table carries its walk's verdict, and a refused one
+// refuses the read (index_gate_kernel).  The other kinds of index launch nothing here.
+static void gate_read(const tsqa_index* idx, int32_t* d_status, hipStream_t s)
+{
+    if (idx->verdict) hipLaunchKernelGGL(index_gate_kernel, dim3(1), dim3(1), 0, s, static_cast<const int32_t*>(idx->verdict), d_status);
+}
+
 extern "C" void tsqa_index_destroy(tsqa_index* idx)
 {
     if (!idx) return;
@@ -910,6 +982,7 @@ extern "C" int tsqa_decompress_ranges_async(tsqa_ctx* c, const tsqa_index* idx, 
         return TSQA_ERR_ARG;
     }
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    gate_read(idx, d_status, s);
     if (n_items == 0) return TSQA_OK;
     TSQ_HIP(c, up.send((size_t)n_items * sizeof(tsqa_range_item), s));
     const int rc = launch_read_kernel<dec_range_kernel>(c, n_items, s, idx->container, idx->frames, idx->n_blocks, up.dev<RangeItem>(),
@@ -1017,6 +1090,7 @@ extern "C" int tsqa_decompress_item_ranges_async(tsqa_ctx* c, const tsqa_index* 
     tsqa_uploads::Slot up;
     if (int rc = c->range_up.acquire(c, bytes ? bytes : 16, &up)) return rc;
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    gate_read(idx, d_status, s);
     if (n_groups == 0) return TSQA_OK;
     memset(up.host<uint8_t>(), 0, bytes);
     std::copy(vi.begin(), vi.end(), up.host<tsqa_range_item>());

@@ -63,6 +63,14 @@ __global__ __launch_bounds__(256) void split_pack_scan_kernel(const uint32_t* __
     }
 }
 
+// What both walks from a size table (frame_walk_sized_kernel; index_check_kernel, tsq_index.cuh) ask of the frame that the table
+// puts at `at` with the stream length s (s_ok: stream_len_ok(s), and the lane has a frame at all): its six bytes lie inside n,
+// before one of them is read; read_frame accepts what lies there; and the frame word's length is s.  *f: read_frame's fields.
+__device__ __forceinline__ bool sized_frame_ok(const uint8_t* container, uint64_t n, uint64_t at, bool s_ok, uint32_t s, FrameInfo* f)
+{
+    return s_ok && at + kMinFrameSize <= n && read_frame(container + at, at, n, f) && f->stream_len == s;
+}
+
 // frame_walk_kernel from a table of stream sizes, which is not trusted.  ONE workgroup of exactly 256 threads, 256 frames per pass,
 // both running sums carried in registers.  The header is checked as frame_walk_kernel checks it.  Then lane b takes its frame's
 // place from the table alone, at_b = 16 + sum over j < b of (3 + s_j), and asks of it: stream_len_ok(s_b) -- a size that fails
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(256) void frame_walk_sized_kernel(const uint8_t* __
         const uint64_t at = at_base + group_scan_excl64(s_ok ? kFrameWordSize + (uint64_t)s : 0ull, wave_sum, &sum);
         at_base += sum;
         FrameInfo f{0, 0, 0, 0, 0, 0};
-        const bool f_ok = s_ok && at + kMinFrameSize <= n && read_frame(container + at, at, n, &f) && f.stream_len == s;
+        const bool f_ok = sized_frame_ok(container, n, at, s_ok, s, &f);
         const uint32_t out_len = f_ok ? f.out_len : 0u;
         const uint64_t oat = oat_base + group_scan_excl64(out_len, wave_sum, &sum);
         oat_base += sum;
