@@ -903,7 +903,7 @@ private:
                 good = good && hipMemcpyAsync(l.d_in, stage_in ? l.h_in : src.mem + at, cur, hipMemcpyHostToDevice, s) == hipSuccess;
                 good = good && hipMemcpyAsync(l.dev->frames, l.h_frames, bn * sizeof(FrameInfo), hipMemcpyHostToDevice, s) == hipSuccess;
                 good = good && hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s) == hipSuccess;
-                good = good && l.dev->launch_decode(l.d_in, bn, l.d_out, l.dev->d_status, s) == TSQA_OK;
+                good = good && l.dev->launch_decode_frames(l.d_in, l.dev->frames, bn, l.d_out, l.dev->d_status, s) == TSQA_OK;
                 if (good) {
                     (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
                     good = hipEventRecord(l.ev, s) == hipSuccess;
@@ -1098,7 +1098,7 @@ extern "C" void tsqDecode(uint8_t* inputBlock, uint8_t* outputBlock, uint32_t* o
     if (hipMemcpyAsync(l.d_in, l.h_in, inputSize, hipMemcpyHostToDevice, s) != hipSuccess) return;
     (void)hipMemcpyAsync(l.dev->frames, l.h_frames, sizeof(FrameInfo), hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s);
-    if (l.dev->launch_decode(l.d_in, 1, l.d_out, l.dev->d_status, s) != TSQA_OK) return;
+    if (l.dev->launch_decode_frames(l.d_in, l.dev->frames, 1, l.d_out, l.dev->d_status, s) != TSQA_OK) return;
     (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return;
     if (*l.h_status == tsq::kErrStall) {          // (a sibling workgroup did not get onto the GPU in time: once more on one workgroup)

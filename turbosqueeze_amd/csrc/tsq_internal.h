@@ -13,13 +13,28 @@ namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; }
 
 struct tsqa_ctx;
 
+// One scratch buffer in device memory: the pointer, which it reads as, and the capacity in elements.  grow() frees before it
+// allocates, so the peak does not double; the caller has waited for whatever may still use the old buffer.  A failed allocation is
+// reported through the context (TSQA_ERR_HIP) and leaves a null pointer and capacity 0: the next call tries again.  Freed with its owner.
+template <class T> struct tsqa_scratch {
+    T* p = nullptr;
+    size_t cap = 0;
+    tsqa_scratch() = default;
+    tsqa_scratch(const tsqa_scratch&) = delete;
+    tsqa_scratch& operator=(const tsqa_scratch&) = delete;
+    ~tsqa_scratch() { reset(); }
+    operator T*() const { return p; }
+    bool needs(size_t n) const { return n > cap; }
+    void reset() { (void)hipFree(p); p = nullptr; cap = 0; }
+    bool grow(tsqa_ctx* c, size_t n);          // to n elements where needs(n); false: refused, the error is set
+};
+
 // Descriptors a call plans on the host for its kernels (range-read items, batch descriptors): a ring of two slots, used in turn, each a
 // pinned host buffer and its copy on the device, grown by doubling.  A slot is reused once the call that used it has finished: two
 // calls can be in flight, the third waits for the first.
 class tsqa_uploads {
     void* host_[2] = {nullptr, nullptr};
-    void* dev_[2] = {nullptr, nullptr};
-    size_t cap_[2] = {0, 0};
+    tsqa_scratch<uint8_t> dev_[2];             // (the capacity of both copies, in bytes)
     hipEvent_t done_[2] = {nullptr, nullptr};
     bool pending_[2] = {false, false};
     int next_ = 0;
@@ -31,8 +46,8 @@ public:
         tsqa_uploads* u = nullptr;
         int k = 0;
         template <class T> T* host(size_t at = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(u->host_[k]) + at); }
-        template <class T> T* dev(size_t at = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(u->dev_[k]) + at); }
-        size_t cap() const { return u->cap_[k]; }
+        template <class T> T* dev(size_t at = 0) const { return reinterpret_cast<T*>(u->dev_[k] + at); }
+        size_t cap() const { return u->dev_[k].cap; }
         hipError_t send(size_t bytes, hipStream_t s) const { return hipMemcpyAsync(u->dev_[k], u->host_[k], bytes, hipMemcpyHostToDevice, s); }
         // Behind the LAST kernel of the call that reads the slot, however that launch went: neither copy of the descriptors is touched
         // again before the work that uses them has finished.
@@ -52,14 +67,13 @@ struct tsqa_ctx {
     int device = 0;
     int n_cus = 0;
     hipStream_t stream = nullptr;
-    // scratch in HBM
-    uint8_t* slots = nullptr;          // n_blocks x TSQ_OUTPUT_SZ encoded block streams
-    uint32_t* sizes = nullptr;         // n_blocks stream sizes
-    uint64_t* frame_at = nullptr;      // n_blocks + 1 frame offsets in the container
-    tsq::FrameInfo* frames = nullptr;  // n_blocks frame descriptors (decode)
-    uint32_t* block_owner = nullptr;   // n_blocks: the batch item each frame belongs to (tsqa_decompress_batch_items_async)
-    uint16_t* tables = nullptr;        // n_blocks x 2^17 u16 position tables of the encoders
-    size_t cap_blocks = 0, cap_tables = 0, cap_slots = 0;
+    // scratch in HBM (tsqa_scratch: each buffer knows its capacity and is freed with the context)
+    tsqa_scratch<uint8_t> slots;               // n_blocks x TSQ_OUTPUT_SZ encoded block streams, and 256 bytes
+    tsqa_scratch<uint32_t> sizes;              // n_blocks stream sizes
+    tsqa_scratch<uint64_t> frame_at;           // n_blocks + 1 frame offsets in the container
+    tsqa_scratch<tsq::FrameInfo> frames;       // n_blocks frame descriptors (decode)
+    tsqa_scratch<uint32_t> block_owner;        // n_blocks: the batch item each frame belongs to (tsqa_decompress_batch_items_async)
+    tsqa_scratch<uint16_t> tables;             // n_blocks x 2^17 u16 position tables of the encoders
     tsq::FrameInfo* host_frames = nullptr;     // frame descriptors built on the host (sharded fetch + decode): pinned
     size_t cap_host_frames = 0;
     std::vector<uint64_t> host_frame_src;      // where each owned frame's stream starts in the host container
@@ -74,26 +88,21 @@ struct tsqa_ctx {
     tsqa_uploads range_up, batch_up;           // range-read items; batch descriptors
     // batches: per item, the running frame offset of a compress batch across its launches, and the sizes, the offsets of a packed
     // batch (one more than items), the headers the synchronous forms read back and the item statuses of the synchronous decompress
-    int32_t* batch_status = nullptr;
-    uint64_t* batch_at = nullptr;
-    uint64_t* batch_sizes = nullptr;
-    uint64_t* batch_offsets = nullptr;
-    uint8_t* batch_heads = nullptr;
+    tsqa_scratch<int32_t> batch_status;
+    tsqa_scratch<uint64_t> batch_at, batch_sizes, batch_offsets;
+    tsqa_scratch<uint8_t> batch_heads;
     // the item table that tsqa_decompress_batch_packed_dense_async makes on the device, and the block count of its fitting items
-    tsq::BatchItem* batch_items = nullptr;
-    uint32_t* batch_live = nullptr;
-    size_t cap_batch = 0;
+    tsqa_scratch<tsq::BatchItem> batch_items;
+    tsqa_scratch<uint32_t> batch_live;
     // tsqa_compress_batch_packed_tables_async: the block descriptors it makes on the device (cap_blocks of them) and, per encode
     // launch, the item that holds the launch's first block
-    tsq::EncBatchBlock* table_blocks = nullptr;
-    uint32_t* table_launch_item = nullptr;
-    size_t cap_table_blocks = 0, cap_table_launches = 0;
+    tsqa_scratch<tsq::EncBatchBlock> table_blocks;
+    tsqa_scratch<uint32_t> table_launch_item;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
-    uint32_t* duo_ring = nullptr;      // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
-    uint32_t* duo_flags = nullptr;     // and their progress counters
-    size_t cap_duo = 0;
-    uint64_t* d_size = nullptr;        // result words of the synchronous entry points
-    int32_t* d_status = nullptr;
+    tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
+    tsqa_scratch<uint32_t> duo_flags;          // and their progress counters
+    tsqa_scratch<uint64_t> d_size;             // result words of the synchronous entry points
+    tsqa_scratch<int32_t> d_status;
     int enc_variant = 0, dec_variant = 0;
     uint32_t decode_wait_limit = 1u << 24;   // polls before a multi-workgroup decode gives up on a sibling workgroup (TSQA_ERR_STALL)
     char err[256] = {0};
@@ -126,8 +135,17 @@ struct tsqa_ctx {
     // nobody.
     int decode_again(const void* d_streams, const tsq::FrameInfo* d_frames, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s);
     int launch_pack(size_t n, uint32_t ext, void* d_out, size_t out_cap, uint64_t* d_out_size, int32_t* status, hipStream_t s);
-    int launch_decode(const void* d_container, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant = -1);
 };
+
+template <class T> bool tsqa_scratch<T>::grow(tsqa_ctx* c, size_t n)
+{
+    if (!needs(n)) return true;
+    reset();
+    const hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e != hipSuccess) { p = nullptr; c->set_error("hipMalloc of %zu B failed: %s", n * sizeof(T), hipGetErrorString(e)); return false; }
+    cap = n;
+    return true;
+}
 
 // A container's frame table, kept for range reads (tsqa_index_create), or the frame table of a batch of containers in one buffer
 // (tsqa_index_create_batch): the healthy items' blocks one after the other, stream_at relative to the buffer.  The containers

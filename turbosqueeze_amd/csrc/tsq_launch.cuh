@@ -53,8 +53,9 @@ template <class K> struct StagedFamily { K kernel[4]; uint32_t threads[2], lds[2
 // The staged pipeline (tsq_enc_stage.cuh) over nb blocks, one workgroup each.  More blocks than CUs: the lean layout (no input window
 // in LDS, candidate bytes from L2) lets several blocks share a CU; each is a little slower, together they are faster.  Variant 6
 // takes the lean layout at any count, variants 0 and 5 (the frozen generation) by the count, every other one the standard layout.
+// (`args` by reference: a scratch buffer of the context, which cannot be copied, becomes its pointer at the launch.)
 template <class K, class... Args>
-inline int launch_staged(tsqa_ctx* c, StagedFamily<K>& f, uint32_t ext, uint32_t nb, hipStream_t s, Args... args)
+inline int launch_staged(tsqa_ctx* c, StagedFamily<K>& f, uint32_t ext, uint32_t nb, hipStream_t s, const Args&... args)
 {
     if (int rc = raise_lds_limit(c, f.raised, {lds_need(f.kernel[0], f.lds[0]), lds_need(f.kernel[1], f.lds[0]), lds_need(f.kernel[2], f.lds[1]), lds_need(f.kernel[3], f.lds[1])})) return rc;
     const int v = c->enc_variant;

@@ -51,6 +51,9 @@ extern "C" size_t tsqa_container_bound(size_t n) { return 16 + tsqa_block_count(
 // What this library was compiled as (csrc/tsq_experiment.h): the product reports no timing-only switch and no instrumentation.
 #define TSQ_STR2(x) #x
 #define TSQ_STR(x) TSQ_STR2(x)
+#if !defined(TSQ_LM) || !defined(TSQ_LF) || !defined(TSQ_RECORDS)
+#error "tsqa_build_info stringifies TSQ_LM, TSQ_LF and TSQ_RECORDS: tsq_enc_stage.cuh (through tsq_launch.cuh) goes above it"
+#endif
 extern "C" const char* tsqa_build_info(void)
 {
     return "arch=gfx950 timing_only=" TSQ_STR(TSQ_TIMING_ONLY_BUILD) " instrumented=" TSQ_STR(TSQ_INSTRUMENTED_BUILD)
@@ -123,7 +126,7 @@ extern "C" int tsqa_create(int device, tsqa_ctx** out)
         delete c;
         return TSQA_ERR_HIP;
     }
-    if (hipMalloc(&c->d_size, sizeof(uint64_t)) != hipSuccess || hipMalloc(&c->d_status, sizeof(int32_t)) != hipSuccess) {
+    if (!c->d_size.grow(c, 1) || !c->d_status.grow(c, 1)) {
         tsqa_destroy(c);
         return TSQA_ERR_HIP;
     }
@@ -137,16 +140,10 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_pool) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(c->slots); (void)hipFree(c->tables); (void)hipFree(c->sizes); (void)hipFree(c->frame_at);
-    (void)hipFree(c->frames); (void)hipFree(c->block_owner); (void)hipFree(c->d_size); (void)hipFree(c->d_status);
-    (void)hipFree(c->duo_ring); (void)hipFree(c->duo_flags);
     if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
     c->range_up.destroy(); c->batch_up.destroy();
-    (void)hipFree(c->batch_at); (void)hipFree(c->batch_sizes); (void)hipFree(c->batch_offsets); (void)hipFree(c->batch_heads);
-    (void)hipFree(c->batch_status); (void)hipFree(c->batch_items); (void)hipFree(c->batch_live);
-    (void)hipFree(c->table_blocks); (void)hipFree(c->table_launch_item);
-    delete c;
+    delete c;                                            // (the scratch buffers free themselves)
 }
 
 extern "C" const char* tsqa_last_error(const tsqa_ctx* c) { return c ? c->err : "null context"; }
@@ -157,51 +154,40 @@ extern "C" void tsqa_set_decode_wait_limit(tsqa_ctx* c, uint32_t polls) { if (c)
 // Scratch in HBM, grown on demand and kept: slots (TSQ_OUTPUT_SZ per block, the reference's
 // per-block output buffer, tsq_context.cpp:89-143), per-block sizes, frame offsets, frame
 // descriptors with the batch item that owns each, and one 256 KiB position table per block for the encoders (want_tables).
-// Growing waits for the context's stream and for `s`, the stream the call was given (a call enqueued there before this one may still
-// be using what is freed), or (all_streams: the batch entry points) for the whole device.
+// Every reserve* says which buffers its call needs and how many elements of each, waits -- once, only where one of them must grow,
+// and before the first is freed -- for whatever may still be using them, and grows those that must (tsqa_scratch::grow).
+// Here the wait is for the context's stream and for `s`, the stream the call was given (a call enqueued there before this one may
+// still be using what is freed), or (all_streams: the batch entry points) for the whole device.
 int tsqa_ctx::reserve(size_t n_blocks, bool want_tables, bool want_slots, bool all_streams, hipStream_t s)
 {
     (void)hipSetDevice(device);
-    auto wait = [&] { if (all_streams) (void)hipDeviceSynchronize(); else wait_for(s); };
-    if (n_blocks > cap_blocks) {
-        size_t nb = n_blocks;
-        wait();
-        (void)hipFree(sizes); (void)hipFree(frame_at); (void)hipFree(frames); (void)hipFree(block_owner);
-        sizes = nullptr; frame_at = nullptr; frames = nullptr; block_owner = nullptr; cap_blocks = 0;
-        forget_sharded();                                // (the descriptors of a sharded decode went with `frames`)
-        TSQ_HIP(this, hipMalloc(&sizes, nb * sizeof(uint32_t)));
-        TSQ_HIP(this, hipMalloc(&frame_at, (nb + 1) * sizeof(uint64_t)));
-        TSQ_HIP(this, hipMalloc(&frames, nb * sizeof(FrameInfo)));
-        TSQ_HIP(this, hipMalloc(&block_owner, nb * sizeof(uint32_t)));
-        cap_blocks = nb;
-    }
-    if (want_slots && n_blocks > cap_slots) {        // (callers that bring their own slots -- the sharded block API -- never pay for these)
-        wait();
-        (void)hipFree(slots); slots = nullptr; cap_slots = 0;
-        TSQ_HIP(this, hipMalloc(&slots, n_blocks * (size_t)kSlotSize + 256));
-        cap_slots = n_blocks;
-    }
-    if (want_tables && n_blocks > cap_tables) {
-        wait();
-        (void)hipFree(tables); tables = nullptr; cap_tables = 0;
-        TSQ_HIP(this, hipMalloc(&tables, n_blocks * (size_t)kHashEntries * sizeof(uint16_t)));
-        cap_tables = n_blocks;
-    }
-    return TSQA_OK;
+    const size_t nb = n_blocks, n_at = nb ? nb + 1 : 0;
+    // (callers that bring their own slots -- the sharded block API -- never pay for these)
+    const size_t n_slots = want_slots && nb ? nb * (size_t)kSlotSize + 256 : 0, n_tables = want_tables ? nb * (size_t)kHashEntries : 0;
+    const bool descriptors = sizes.needs(nb) || frame_at.needs(n_at) || frames.needs(nb) || block_owner.needs(nb);
+    if (!descriptors && !slots.needs(n_slots) && !tables.needs(n_tables)) return TSQA_OK;
+    if (all_streams) (void)hipDeviceSynchronize(); else wait_for(s);
+    if (descriptors) forget_sharded();                   // (the descriptors of a sharded decode go with `frames`)
+    return sizes.grow(this, nb) && frame_at.grow(this, n_at) && frames.grow(this, nb) && block_owner.grow(this, nb) &&
+           slots.grow(this, n_slots) && tables.grow(this, n_tables) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
 // Scratch of the two-workgroup decoder (tsq_dec_duo.cuh): four chunk records and two counters per block.
 int tsqa_ctx::reserve_duo(size_t n_blocks, hipStream_t s)
 {
     (void)hipSetDevice(device);
-    if (n_blocks <= cap_duo) return TSQA_OK;
+    const size_t n_ring = n_blocks * (size_t)DuoCfg::SLOTS * DuoCfg::REC_WORDS, n_flags = n_blocks * (size_t)DuoCfg::FLAG_STRIDE;
+    if (!duo_ring.needs(n_ring) && !duo_flags.needs(n_flags)) return TSQA_OK;
     wait_for(s);                                         // (a multi-workgroup decode enqueued on `s` may still be using the ring)
-    (void)hipFree(duo_ring); (void)hipFree(duo_flags);
-    duo_ring = nullptr; duo_flags = nullptr; cap_duo = 0;
-    TSQ_HIP(this, hipMalloc(&duo_ring, n_blocks * (size_t)DuoCfg::SLOTS * DuoCfg::REC_WORDS * sizeof(uint32_t)));
-    TSQ_HIP(this, hipMalloc(&duo_flags, n_blocks * (size_t)DuoCfg::FLAG_STRIDE * sizeof(uint32_t)));
-    cap_duo = n_blocks;
-    return TSQA_OK;
+    return duo_ring.grow(this, n_ring) && duo_flags.grow(this, n_flags) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
+// What a buffer that grows by doubling from `from` holds once it takes n elements (nothing asked: nothing held).
+static size_t doubled(size_t from, size_t n)
+{
+    if (n == 0) return 0;
+    while (from < n) from *= 2;
+    return from;
 }
 
 // Frame descriptors built on the host (sharded fetch + decode): pinned, so that their copy to the device is a DMA ordered on the
@@ -214,7 +200,7 @@ int tsqa_ctx::reserve_host_frames(size_t n)
     if (n > cap_host_frames) {
         if (host_frames) (void)hipHostFree(host_frames);
         host_frames = nullptr; cap_host_frames = 0;
-        size_t want = 64; while (want < n) want *= 2;
+        const size_t want = doubled(64, n);
         TSQ_HIP(this, hipHostMalloc(reinterpret_cast<void**>(&host_frames), want * sizeof(FrameInfo), hipHostMallocDefault));
         cap_host_frames = want;
     }
@@ -229,14 +215,12 @@ int tsqa_uploads::acquire(tsqa_ctx* c, size_t bytes, Slot* slot)
     next_ ^= 1;
     if (pending_[k]) { (void)hipEventSynchronize(done_[k]); pending_[k] = false; }
     if (!done_[k]) TSQ_HIP(c, hipEventCreateWithFlags(&done_[k], hipEventDisableTiming));
-    if (bytes > cap_[k]) {
+    if (dev_[k].needs(bytes)) {
         if (host_[k]) (void)hipHostFree(host_[k]);
-        (void)hipFree(dev_[k]);
-        host_[k] = nullptr; dev_[k] = nullptr; cap_[k] = 0;
-        size_t want = 4096; while (want < bytes) want *= 2;
+        host_[k] = nullptr; dev_[k].reset();
+        const size_t want = doubled(4096, bytes);
         TSQ_HIP(c, hipHostMalloc(&host_[k], want, hipHostMallocDefault));
-        TSQ_HIP(c, hipMalloc(&dev_[k], want));
-        cap_[k] = want;
+        if (!dev_[k].grow(c, want)) return TSQA_ERR_HIP;
     }
     *slot = Slot{this, k};
     return TSQA_OK;
@@ -245,54 +229,34 @@ int tsqa_uploads::acquire(tsqa_ctx* c, size_t bytes, Slot* slot)
 void tsqa_uploads::destroy()
 {
     for (int k = 0; k < 2; ++k) {
-        (void)hipFree(dev_[k]);
         if (host_[k]) (void)hipHostFree(host_[k]);
         if (done_[k]) (void)hipEventDestroy(done_[k]);
     }
 }
 
-// Per-item scratch of the batch entry points (tsq_internal.h), grown on demand.
+// Per-item scratch of the batch entry points (tsq_internal.h), doubled from 256 items.
 int tsqa_ctx::reserve_batch(size_t n_items)
 {
     (void)hipSetDevice(device);
-    if (n_items <= cap_batch) return TSQA_OK;
+    const size_t want = doubled(256, n_items), one = want ? 1 : 0;
+    if (!batch_at.needs(want) && !batch_sizes.needs(want) && !batch_offsets.needs(want + one) && !batch_heads.needs(want * kHeaderSize) &&
+        !batch_status.needs(want) && !batch_items.needs(want) && !batch_live.needs(one)) return TSQA_OK;
     // (batch calls run on callers' streams too, and one enqueued there may still be using the tables that are freed below)
     (void)hipDeviceSynchronize();
-    (void)hipFree(batch_at); (void)hipFree(batch_sizes); (void)hipFree(batch_offsets); (void)hipFree(batch_heads); (void)hipFree(batch_status);
-    (void)hipFree(batch_items); (void)hipFree(batch_live);
-    batch_at = nullptr; batch_sizes = nullptr; batch_offsets = nullptr; batch_heads = nullptr; batch_status = nullptr; cap_batch = 0;
-    batch_items = nullptr; batch_live = nullptr;
-    size_t want = 256; while (want < n_items) want *= 2;
-    TSQ_HIP(this, hipMalloc(&batch_at, want * sizeof(uint64_t)));
-    TSQ_HIP(this, hipMalloc(&batch_sizes, want * sizeof(uint64_t)));
-    TSQ_HIP(this, hipMalloc(&batch_offsets, (want + 1) * sizeof(uint64_t)));
-    TSQ_HIP(this, hipMalloc(&batch_heads, want * kHeaderSize));
-    TSQ_HIP(this, hipMalloc(&batch_status, want * sizeof(int32_t)));
-    TSQ_HIP(this, hipMalloc(&batch_items, want * sizeof(BatchItem)));
-    TSQ_HIP(this, hipMalloc(&batch_live, sizeof(uint32_t)));
-    cap_batch = want;
-    return TSQA_OK;
+    return batch_at.grow(this, want) && batch_sizes.grow(this, want) && batch_offsets.grow(this, want + one) &&
+           batch_heads.grow(this, want * kHeaderSize) && batch_status.grow(this, want) && batch_items.grow(this, want) &&
+           batch_live.grow(this, one) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
-// Scratch of the compress from device tables (tsq_internal.h), grown on demand as reserve_batch grows its own.
+// Scratch of the compress from device tables (tsq_internal.h): the block descriptors doubled from 256, the launch table from 16,
+// each on its own.
 int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches)
 {
     (void)hipSetDevice(device);
-    if (n_blocks <= cap_table_blocks && n_launches <= cap_table_launches) return TSQA_OK;
+    const size_t blocks = doubled(256, n_blocks), launches = doubled(16, n_launches);
+    if (!table_blocks.needs(blocks) && !table_launch_item.needs(launches)) return TSQA_OK;
     (void)hipDeviceSynchronize();                        // (as in reserve_batch: a call enqueued on any stream may still be using them)
-    if (n_blocks > cap_table_blocks) {
-        (void)hipFree(table_blocks); table_blocks = nullptr; cap_table_blocks = 0;
-        size_t want = 256; while (want < n_blocks) want *= 2;
-        TSQ_HIP(this, hipMalloc(&table_blocks, want * sizeof(EncBatchBlock)));
-        cap_table_blocks = want;
-    }
-    if (n_launches > cap_table_launches) {
-        (void)hipFree(table_launch_item); table_launch_item = nullptr; cap_table_launches = 0;
-        size_t want = 16; while (want < n_launches) want *= 2;
-        TSQ_HIP(this, hipMalloc(&table_launch_item, want * sizeof(uint32_t)));
-        cap_table_launches = want;
-    }
-    return TSQA_OK;
+    return table_blocks.grow(this, blocks) && table_launch_item.grow(this, launches) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
 // ---- kernel timing ----
@@ -391,13 +355,18 @@ int tsqa_ctx::launch_encode(const void* d_in, size_t n, size_t readable, uint32_
     return launch_encode_to(d_in, n, readable, kBlockSize, ext, slots, sizes, status, s);
 }
 
+// Every scan in this file -- the pack scans, the sized frame walk, the batch layouts, the index scans -- is launched with workgroups of
+// exactly 256 threads: group_scan_excl64 sums four full wavefronts.
+
+// The copy pieces a block's stream takes when no stream is longer than max_stream.
+static uint32_t pack_pieces(uint32_t max_stream = kSlotSize) { return (max_stream + kPackPiece - 1) / kPackPiece + 1; }
+
 int tsqa_ctx::launch_pack(size_t n, uint32_t ext, void* d_out, size_t out_cap, uint64_t* d_out_size, int32_t* status, hipStream_t s)
 {
     const uint32_t nb = (uint32_t)tsqa_block_count(n);
     hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(256), 0, s, sizes, nb, (uint64_t)n, ext,
                        static_cast<uint8_t*>(d_out), (uint64_t)out_cap, frame_at, d_out_size, status);
-    const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
-    hipLaunchKernelGGL(pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, slots, sizes, frame_at,
+    hipLaunchKernelGGL(pack_copy_kernel, dim3(pack_pieces(), nb), dim3(256), 0, s, slots, sizes, frame_at,
                        static_cast<uint8_t*>(d_out), status);
     TSQ_HIP(this, hipGetLastError());
     return TSQA_OK;
@@ -411,11 +380,6 @@ int tsqa_ctx::launch_decode_frames(const void* d_streams, const FrameInfo* d_fra
     span.end();
     TSQ_HIP(this, hipGetLastError());
     return TSQA_OK;
-}
-
-int tsqa_ctx::launch_decode(const void* d_container, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s, int variant)
-{
-    return launch_decode_frames(d_container, frames, n_blocks, d_out, status, s, variant);
 }
 
 int tsqa_ctx::decode_again(const void* d_streams, const FrameInfo* d_frames, uint32_t n_blocks, void* d_out, int32_t* status, hipStream_t s)
@@ -451,17 +415,21 @@ static int status_to_rc(tsqa_ctx* c, int32_t st, const char* what)
 }
 
 // The tail of the synchronous entry points: the context's status word comes back behind whatever the caller has queued on `s`
-// (the call itself, copies of its sizes or offsets to the host), and the stream is waited for.
-static int read_status(tsqa_ctx* c, hipStream_t s, int32_t* st)
+// (the call itself, copies of its sizes or offsets to the host), and the stream is waited for.  out_size != NULL: the context's
+// size word comes back with it, and is stored before the status is judged.
+static int read_status(tsqa_ctx* c, hipStream_t s, int32_t* st, size_t* out_size = nullptr)
 {
+    uint64_t sz = 0;
+    if (out_size) TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipMemcpyAsync(st, c->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
+    if (out_size) *out_size = (size_t)sz;
     return TSQA_OK;
 }
-static int finish_sync(tsqa_ctx* c, hipStream_t s, const char* what)
+static int finish_sync(tsqa_ctx* c, hipStream_t s, const char* what, size_t* out_size = nullptr)
 {
     int32_t st = 0;
-    if (int rc = read_status(c, s, &st)) return rc;
+    if (int rc = read_status(c, s, &st, out_size)) return rc;
     return status_to_rc(c, st, what);
 }
 
@@ -472,11 +440,7 @@ extern "C" int tsqa_compress_device(tsqa_ctx* c, const void* d_in, size_t n, voi
     hipStream_t s = stream_of(c, hip_stream);
     int rc = tsqa_compress_device_async(c, d_in, n, d_out, out_cap, c->d_size, c->d_status, ext, s);
     if (rc) return rc;
-    uint64_t sz = 0; int32_t st = 0;
-    TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-    if (int rc = read_status(c, s, &st)) return rc;
-    *out_size = (size_t)sz;
-    return status_to_rc(c, st, "compress");
+    return finish_sync(c, s, "compress", out_size);
 }
 
 // (variant < 0: the context's decode variant; the retry after TSQA_ERR_STALL passes 4 without touching the context's setting.
@@ -494,13 +458,13 @@ static int decompress_device_async_impl(tsqa_ctx* c, const void* d_in, size_t n,
     c->forget_sharded();                                 // the frame walk below overwrites c->frames
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     ProfSpan span(c, 3, s);
-    if (sized)                           // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+    if (sized)
         hipLaunchKernelGGL(frame_walk_sized_kernel, dim3(1), dim3(256), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
                            d_block_sizes, (uint64_t)out_cap, c->frames, d_out_size, d_status);
     else
         hipLaunchKernelGGL(frame_walk_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_in), (uint64_t)n, n_blocks,
                            (uint64_t)out_cap, c->frames, d_out_size, d_status);
-    rc = c->launch_decode(d_in, n_blocks, d_out, d_status, s, variant);
+    rc = c->launch_decode_frames(d_in, c->frames, n_blocks, d_out, d_status, s, variant);
     span.end();
     return rc;
 }
@@ -569,16 +533,14 @@ static int decompress_device_wait(tsqa_ctx* c, const void* d_in, size_t n, void*
     // (the table holds as many words as the caller says, not as many as the container says: no kernel walks a table by a count
     //  the caller has not vouched for)
     if (sized && nb != table_words) { *out_size = 0; c->set_error("decompress: the header states %u blocks, the size table holds %u", nb, table_words); return TSQA_ERR_FORMAT; }
-    uint64_t sz = 0; int32_t st = 0;
+    int32_t st = 0;
     // after TSQA_ERR_STALL -- a workgroup of a several-workgroups-per-block decode did not get onto the GPU in time (other work held
     // the CUs): the container is not at fault -- once more with one workgroup per block, which waits for nobody
     for (int variant : {-1, 4}) {
         if (int rc = decompress_device_async_impl(c, d_in, n, nb, d_out, out_cap, c->d_size, c->d_status, s, variant, sized, d_block_sizes)) return rc;
-        TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-        if (int rc = read_status(c, s, &st)) return rc;
+        if (int rc = read_status(c, s, &st, out_size)) return rc;
         if (st != kErrStall) break;
     }
-    *out_size = (size_t)sz;
     return status_to_rc(c, st, "decompress");
 }
 
@@ -769,6 +731,25 @@ extern "C" int tsqa_sharded_decode_again_async(tsqa_ctx* c, const void* d_stream
 struct IndexDeleter { void operator()(tsqa_index* idx) const { tsqa_index_destroy(idx); } };
 using IndexPtr = std::unique_ptr<tsqa_index, IndexDeleter>;
 
+// A new index for `who` (the caller's name in the error text; null when the host has no memory for it).  one_item: of a single
+// container of nb blocks and `total` bytes, with out_start sized and, where host_copy, host_frames too; else the index of a batch,
+// whose tables are made behind its walk.
+static IndexPtr index_begin(tsqa_ctx* c, const char* who, const void* d_container, size_t n, uint32_t nb, uint64_t total, bool one_item, bool host_copy)
+{
+    IndexPtr idx(new (std::nothrow) tsqa_index());
+    try {
+        if (!idx) throw std::bad_alloc();
+        idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = total;
+        if (host_copy) idx->host_frames.resize(nb);
+        if (one_item) {
+            idx->out_start.resize((size_t)nb + 1);
+            idx->item_first = {0ull, (uint64_t)nb};
+            idx->item_status = {TSQA_OK};
+        }
+    } catch (...) { c->set_error("%s: out of host memory", who); idx.reset(); }
+    return idx;
+}
+
 extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n, tsqa_index** out)
 {
     if (!out) return TSQA_ERR_ARG;
@@ -783,15 +764,8 @@ extern "C" int tsqa_index_create(tsqa_ctx* c, const void* d_container, size_t n,
     TSQ_HIP(c, hipStreamSynchronize(s));
     uint32_t nb; uint64_t total;
     if (read_header(head, n, &nb, &total) != kHeaderOk) { c->set_error("index_create: bad header"); return TSQA_ERR_FORMAT; }
-    IndexPtr idx(new (std::nothrow) tsqa_index());
-    if (!idx) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
-    idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = total;
-    try {
-        idx->host_frames.resize(nb);
-        idx->out_start.resize((size_t)nb + 1);
-        idx->item_first = {0ull, (uint64_t)nb};
-        idx->item_status = {TSQA_OK};
-    } catch (...) { c->set_error("index_create: out of host memory"); return TSQA_ERR_ARG; }
+    IndexPtr idx = index_begin(c, "index_create", d_container, n, nb, total, true, true);
+    if (!idx) return TSQA_ERR_ARG;
     // the frame walk of a full decompress, into the index's own descriptors (the context's are left alone)
     int32_t st = 0;
     TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)nb * sizeof(FrameInfo)));
@@ -826,14 +800,8 @@ extern "C" int tsqa_index_create_sized_async(tsqa_ctx* c, const void* d_containe
     if (n < kHeaderSize + (uint64_t)kMinFrameSize * nb) { c->set_error("index_create_sized: %zu B cannot hold %u frames", n, nb); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
-    IndexPtr idx(new (std::nothrow) tsqa_index());
-    if (!idx) { c->set_error("index_create_sized: out of host memory"); return TSQA_ERR_ARG; }
-    idx->device = c->device; idx->container = static_cast<const uint8_t*>(d_container); idx->n = n; idx->n_blocks = nb; idx->total = n_total;
-    try {
-        idx->out_start.resize((size_t)nb + 1);
-        idx->item_first = {0ull, (uint64_t)nb};
-        idx->item_status = {TSQA_OK};
-    } catch (...) { c->set_error("index_create_sized: out of host memory"); return TSQA_ERR_ARG; }
+    IndexPtr idx = index_begin(c, "index_create_sized", d_container, n, nb, n_total, true, false);
+    if (!idx) return TSQA_ERR_ARG;
     for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = (uint64_t)b * block_len;
     idx->out_start[nb] = n_total;
     // one allocation: the descriptors, the group sums, the verdict; all zero in front of the walk
@@ -843,7 +811,6 @@ extern "C" int tsqa_index_create_sized_async(tsqa_ctx* c, const void* d_containe
     idx->group_sum = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(idx->frames) + frames_bytes);
     idx->verdict = reinterpret_cast<int32_t*>(idx->group_sum + n_groups);
     TSQ_HIP(c, hipMemsetAsync(idx->frames, 0, bytes, s));
-    // (workgroups of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
     hipLaunchKernelGGL(index_sum_kernel, dim3(n_groups), dim3(256), 0, s, d_block_sizes, nb, idx->group_sum);
     hipLaunchKernelGGL(index_scan_kernel, dim3(1), dim3(256), 0, s, idx->container, (uint64_t)n, nb, n_total, idx->group_sum, n_groups, idx->verdict);
     hipLaunchKernelGGL(index_check_kernel, dim3(n_groups), dim3(256), 0, s, idx->container, (uint64_t)n, nb, n_total, block_len, d_block_sizes,
@@ -1169,6 +1136,33 @@ extern "C" int tsqa_plan_batch(const tsqa_batch_item* items, uint32_t n_items, s
     return plan_batch(items, n_items, in_size, out_size, n_blocks, first_block, &why, n_blocks ? kPlanDecompress : kPlanCompress);
 }
 
+// The batch route: n_blocks blocks, each encoded from its descriptor into slot b % budget, in launches of at most `budget` = 2 x n_cus
+// blocks, the lean layout's chip-filling count, so that the scratch -- a slot and a position table per block -- stays bounded whatever
+// the count.  Items may span launches.  Its callers reserve min(n_blocks, budget) blocks with tables and slots for all streams.
+static uint32_t batch_budget(const tsqa_ctx* c) { return 2u * (uint32_t)c->n_cus; }
+
+// The launches of the batch route, in turn: the encode of blocks [b0, b0 + nb) (a kind-0 span), scan(b0, nb, launch) -- the caller's
+// pack scan, which places the launch's frames in c->frame_at --, the copy of the streams to `out` in `pieces` pieces each.  live !=
+// NULL: descriptors made on the device, of which *live are in use (launch_batch_encode_kernels); launches past them do nothing.
+// Ends at an encode launch that is refused, with its error.
+template <class Scan>
+static int batch_route_enqueue(tsqa_ctx* c, const uint8_t* in, const EncBatchBlock* blocks, uint64_t n_blocks, uint32_t ext, uint32_t pieces,
+                               uint8_t* out, const uint32_t* live, int32_t* d_status, hipStream_t s, Scan scan)
+{
+    const uint32_t budget = batch_budget(c);
+    uint32_t launch = 0;
+    for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget, ++launch) {
+        const uint32_t nb = (uint32_t)(n_blocks - b0 < budget ? n_blocks - b0 : budget), first = live ? (uint32_t)b0 : 0u;
+        ProfSpan span(c, 0, s);
+        const int rc = launch_batch_encode_kernels(c, in, blocks + b0, nb, ext, c->slots, c->sizes, d_status, s, first, live);
+        if (rc) { span.cancel(); return rc; }
+        span.end();
+        scan(b0, nb, launch);
+        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out, first, live);
+    }
+    return TSQA_OK;
+}
+
 // The launches of a compress batch whose arguments have been checked; first[] is its block plan (tsqa_plan_batch).  align == 0: the
 // caller's output ranges (tsqa_compress_batch_async).  align > 0: a packed batch (tsqa_compress_batch_packed_async): the items'
 // places are made on the device and land in d_offsets.
@@ -1179,9 +1173,7 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
     static_assert(sizeof(tsqa_batch_item) == 32 && sizeof(BatchItem) == 48 && sizeof(EncBatchBlock) == 24, "descriptor layouts");
     (void)hipSetDevice(c->device);
     const uint64_t n_blocks = first[n_items];
-    // A launch takes at most 2 x n_cus blocks, the lean layout's chip-filling count: the scratch -- a slot and a position table per
-    // block -- stays bounded whatever the batch holds.  Items may span launches.
-    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    const uint32_t budget = batch_budget(c);
     const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), bytes = item_bytes + n_blocks * sizeof(EncBatchBlock);
     tsqa_uploads::Slot up;
     if (int rc = c->batch_up.acquire(c, bytes, &up)) return rc;
@@ -1204,27 +1196,18 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
     uint8_t* const out = static_cast<uint8_t*>(d_out);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     TSQ_HIP(c, up.send(bytes, s));
-    const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
-    int rc = TSQA_OK;
-    for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget) {
-        const uint32_t nb = (uint32_t)(n_blocks - b0 < budget ? n_blocks - b0 : budget);
+    const int rc = batch_route_enqueue(c, in, db, n_blocks, ext, pack_pieces(), out, nullptr, d_status, s, [&](uint64_t b0, uint32_t nb, uint32_t) {
         // the items with blocks in this launch: from the one that holds block b0 to the last that starts before b0 + nb
         const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
         const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
-        ProfSpan span(c, 0, s);
-        rc = launch_batch_encode_kernels(c, in, db + b0, nb, ext, c->slots, c->sizes, d_status, s);
-        if (rc) { span.cancel(); break; }
-        span.end();
-        if (align)                       // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+        if (align)
             hipLaunchKernelGGL(batch_pack_scan_packed_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, c->sizes, ext, align, out,
                                (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_status);
         else
             hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
                                c->batch_at, c->frame_at, d_sizes, d_status);
-        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, c->slots, c->sizes, c->frame_at, out, 0u,
-                           (const uint32_t*)nullptr);
-    }
-    TSQ_HIP(c, up.commit(s));                            // (behind a partial batch too)
+    });
+    TSQ_HIP(c, up.commit(s));                            // (behind a refused launch too: those before it may still read the descriptors)
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
@@ -1380,8 +1363,7 @@ extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* 
     if (!batch_encoder_ok(c, who)) return TSQA_ERR_ARG;
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
-    // the launches are sized by cap_blocks as compress_batch_enqueue sizes them by the planned count: at most 2 x n_cus blocks each
-    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    const uint32_t budget = batch_budget(c);             // (the launches are sized by cap_blocks, not by a planned count)
     if (int rc = c->reserve_batch(n_items)) return rc;
     if (d_out) {
         if (int rc = c->reserve(cap_blocks < budget ? cap_blocks : budget, true, true, true)) return rc;
@@ -1391,8 +1373,7 @@ extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* 
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(batch_measure_tables_kernel, per_item, dim3(256), 0, s, c->batch_items, n_items, d_in_offsets, d_in_sizes,
                        (uint64_t)in_size, d_item_status);
-    // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts.  Measuring: nothing fits, and the kernel
-    //  writes the two arena tables itself)
+    // (measuring: nothing fits, and the kernel writes the two arena tables itself)
     hipLaunchKernelGGL(batch_layout_tables_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, d_out ? cap_blocks : 0u,
                        d_out ? (uint64_t*)nullptr : d_offsets, d_sizes, d_first_block, d_bound, d_item_status, c->batch_live, d_status);
     if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
@@ -1402,20 +1383,12 @@ extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* 
                        static_cast<const uint64_t*>(d_first_block), live, budget, c->table_blocks, c->table_launch_item);
     const uint8_t* const in = static_cast<const uint8_t*>(d_in);
     uint8_t* const out = static_cast<uint8_t*>(d_out);
-    const uint32_t pieces = (kSlotSize + kPackPiece - 1) / kPackPiece + 1;
-    uint32_t l = 0;
-    for (uint64_t b0 = 0; b0 < cap_blocks; b0 += budget, ++l) {
-        const uint32_t nb = (uint32_t)(cap_blocks - b0 < budget ? cap_blocks - b0 : budget);
-        ProfSpan span(c, 0, s);
-        const int rc = launch_batch_encode_kernels(c, in, c->table_blocks + b0, nb, ext, c->slots, c->sizes, d_status, s, (uint32_t)b0, live);
-        if (rc) { span.cancel(); return rc; }
-        span.end();
+    const int rc = batch_route_enqueue(c, in, c->table_blocks, cap_blocks, ext, pack_pieces(), out, live, d_status, s, [&](uint64_t, uint32_t, uint32_t launch) {
         hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
-                           l, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
+                           launch, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
                            d_offsets, d_sizes, d_item_status, d_status);
-        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, static_cast<const uint8_t*>(c->slots),
-                           static_cast<const uint32_t*>(c->sizes), static_cast<const uint64_t*>(c->frame_at), out, (uint32_t)b0, live);
-    }
+    });
+    if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
 }
@@ -1447,9 +1420,7 @@ extern "C" int tsqa_compress_device_split_async(tsqa_ctx* c, const void* d_in, s
     if (!batch_encoder_ok(c, "compress_split")) return TSQA_ERR_ARG;
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
-    // the launches are compress_batch_enqueue's: at most 2 x n_cus blocks each, block b in slot b % budget, so the scratch stays
-    // bounded whatever the block count; the descriptors are made on the device, and nothing is uploaded
-    const uint32_t budget = 2u * (uint32_t)c->n_cus;
+    const uint32_t budget = batch_budget(c);             // (the descriptors are made on the device, and nothing is uploaded)
     if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true, true, true)) return rc;
     if (int rc = c->reserve_batch(1)) return rc;         // (batch_at[0]: the running frame offset between the launches)
     if (int rc = c->reserve_tables(n_blocks, 0)) return rc;
@@ -1460,19 +1431,11 @@ extern "C" int tsqa_compress_device_split_async(tsqa_ctx* c, const void* d_in, s
                        budget, c->table_blocks);
     // (no stream of these blocks is longer than block_bound says: short blocks need few copy pieces)
     const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
-    const uint32_t pieces = (max_stream + kPackPiece - 1) / kPackPiece + 1u;
-    for (uint64_t b0 = 0; b0 < n_blocks; b0 += budget) {
-        const uint32_t nb = (uint32_t)(n_blocks - b0 < budget ? n_blocks - b0 : budget);
-        ProfSpan span(c, 0, s);
-        const int rc = launch_batch_encode_kernels(c, in, c->table_blocks + b0, nb, ext, c->slots, c->sizes, d_status, s);
-        if (rc) { span.cancel(); return rc; }
-        span.end();
-        // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts)
+    const int rc = batch_route_enqueue(c, in, c->table_blocks, n_blocks, ext, pack_pieces(max_stream), out, nullptr, d_status, s, [&](uint64_t b0, uint32_t nb, uint32_t) {
         hipLaunchKernelGGL(split_pack_scan_kernel, dim3(1), dim3(256), 0, s, static_cast<const uint32_t*>(c->sizes), (uint32_t)b0, nb, n_blocks,
                            (uint64_t)n, ext, max_stream, out, (uint64_t)out_cap, c->batch_at, c->frame_at, d_out_size, d_block_sizes, d_status);
-        hipLaunchKernelGGL(batch_pack_copy_kernel, dim3(pieces, nb), dim3(256), 0, s, static_cast<const uint8_t*>(c->slots),
-                           static_cast<const uint32_t*>(c->sizes), static_cast<const uint64_t*>(c->frame_at), out, 0u, (const uint32_t*)nullptr);
-    }
+    });
+    if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
 }
@@ -1485,11 +1448,7 @@ extern "C" int tsqa_compress_device_split(tsqa_ctx* c, const void* d_in, size_t 
     hipStream_t s = stream_of(c, hip_stream);
     int rc = tsqa_compress_device_split_async(c, d_in, n, block_len, d_out, out_cap, c->d_size, d_block_sizes, c->d_status, ext, s);
     if (rc) return rc;
-    uint64_t sz = 0; int32_t st = 0;
-    TSQ_HIP(c, hipMemcpyAsync(&sz, c->d_size, sizeof(sz), hipMemcpyDeviceToHost, s));
-    if (int rc = read_status(c, s, &st)) return rc;
-    *out_size = (size_t)sz;                              // (the size needed, behind TSQA_ERR_OVERFLOW too)
-    return status_to_rc(c, st, "compress_split");
+    return finish_sync(c, s, "compress_split", out_size);            // (the size needed, behind TSQA_ERR_OVERFLOW too)
 }
 
 // What every batch decompress with host-planned items starts with (`who`: the caller, for the error texts): the plan, an upload slot
@@ -1672,8 +1631,7 @@ extern "C" int tsqa_decompress_batch_packed_dense_async(tsqa_ctx* c, const void*
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(batch_measure_kernel, per_item, dim3(256), 0, s, in, c->batch_items, n_items, d_offsets, d_sizes, (uint64_t)arena_size,
                        d_item_status);
-    // (one workgroup of exactly 256 threads: group_scan_excl64 sums four full wavefronts.  Measuring: nothing fits, and the kernel
-    //  closes the batch's word itself)
+    // (measuring: nothing fits, and the kernel closes the batch's word itself)
     hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, (uint64_t)out_size, d_out ? cap_blocks : 0u,
                        d_out_offsets, d_out_sizes, d_first_block, d_item_status, c->batch_live, d_out ? nullptr : d_status);
     if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
@@ -1803,9 +1761,8 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
     }
     first[n_items] = blocks;
     if (blocks > 0xFFFFFFFFull) { c->set_error("index_create_batch: more than 2^32 - 1 blocks"); return TSQA_ERR_ARG; }
-    IndexPtr idx(new (std::nothrow) tsqa_index());
-    if (!idx) { c->set_error("index_create_batch: out of host memory"); return TSQA_ERR_ARG; }
-    idx->device = c->device; idx->container = in; idx->n = in_size;
+    IndexPtr idx = index_begin(c, "index_create_batch", d_in, in_size, 0u, 0ull, false, false);
+    if (!idx) return TSQA_ERR_ARG;
     std::vector<tsqa_frame> walked(blocks);
     // one frame walk over all items, one lane each, into the index's own descriptors; verdicts and descriptors come back together
     TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)(blocks ? blocks : 1) * sizeof(FrameInfo)));
