@@ -182,6 +182,8 @@ int tsqa_profile_read(tsqa_ctx *ctx, double *encode_ms, uint32_t *encode_launche
  * tsqa_decompress_device_async (frame walk + decode kernel). */
 int tsqa_profile_read_calls(tsqa_ctx *ctx, double *compress_ms, uint32_t *compress_calls,
                             double *decompress_ms, uint32_t *decompress_calls);
+/* The same for the copy kernel of tsqa_join_async alone (its other launches are short and lie outside the span). */
+int tsqa_profile_read_join(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launches);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -486,6 +488,62 @@ int tsqa_compress_batch_packed_tables_async(tsqa_ctx *ctx, const void *d_in, siz
                                             uint32_t align, void *d_out, size_t out_size, uint64_t *d_offsets, uint64_t *d_sizes,
                                             uint64_t *d_first_block, uint64_t *d_bound, int32_t *d_item_status, int32_t *d_status,
                                             void *hip_stream);
+
+/*
+ * Join: the containers of a packed batch into ONE container, at copy speed.  The batch calls leave N containers in device memory;
+ * tsqa_decompress_device*, tsqa_index_create, the range and record reads, tsq_cli, tsqDecompress* and the reference's readers take
+ * one.  The format permits the cheap way from the first to the second: a reader starts block k where the blocks before it end, and
+ * every frame carries its own ext bit, so the join of c_0 .. c_{N-1} is
+ *   "TSQ1" | u32 sum(n_blocks_i) | u64 sum(total_i) | body_0 | body_1 | ... | body_{N-1}
+ *   body_i = the bytes of c_i from 16 to the end of its last frame
+ * and decodes to the concatenation of the items' data.  Nothing is decoded and nothing is changed in place; an append is the join
+ * of the old container and the new one, and the same container listed twice gives its data twice.
+ *
+ * tsqa_plan_join: host only.  frame_bytes[i] = the bytes of container i from its start to the end of its last frame.
+ *   body_at[0] = 16, body_at[i + 1] = body_at[i] + frame_bytes[i] - 16; first_block = the prefix sum of blocks (both n_items + 1);
+ *   *n_blocks and *total = the joined header's fields, *size = body_at[n_items].  TSQA_ERR_ARG for a NULL pointer, n_items == 0,
+ *   blocks[i] == 0, frame_bytes[i] < 16 + 6 * blocks[i] or totals[i] > blocks[i] * TSQ_BLOCK_SZ; TSQA_ERR_OVERFLOW when the block sum
+ *   does not fit 32 bits (the tables are still filled).
+ *
+ * tsqa_join_async: the arguments of the dense decompress.  Container i is [d_offsets[i], d_offsets[i] + d_sizes[i]) of d_arena, the
+ * tables in device memory; nothing is uploaded, nothing in the tables or the arena is trusted, and ranges may overlap.  The call is
+ * all or nothing -- a join with an item left out would silently be other data -- and still leaves a verdict per item:
+ *   1. Place and header: rules 1 and 2 of the dense decompress, else TSQA_ERR_FORMAT in d_item_status[i]; the item counts as 0
+ *      blocks, and only its 16 header bytes have been read.
+ *   2. Blocks: d_first_block (n_items + 1) = the prefix sum of the accepted headers' counts, complete whatever fits:
+ *      first_block[n_items] is the cap_blocks a retry needs.  The items that fit cap_blocks are a prefix of the accepted ones (the
+ *      first unfit item ends it); an accepted item outside it gets TSQA_ERR_OVERFLOW and is not walked.
+ *   3. Walk: every fitting item is walked as tsqa_decompress_device_async walks a single container, without a capacity check;
+ *      a refusal is TSQA_ERR_FORMAT.  ONE lane walks one item, so an item of many short blocks costs its serial walk (262 144
+ *      blocks of 4 KiB: that many dependent loads on one lane, whatever the other items are).  Bytes of an item behind its last
+ *      frame are legal and are left out of the join.
+ *   4. Size: *d_status = the largest item status.  When every item is accepted and fits, *d_out_size = tsqa_plan_join's size, also
+ *      when that exceeds out_cap: then *d_status = TSQA_ERR_OVERFLOW, and a retry with that much room succeeds.  In every other
+ *      case *d_out_size = 0.
+ *   5. Emit: only while *d_status == 0: the header, the bodies at body_at, and -- d_block_sizes (device, may be NULL) -- the
+ *      first_block[n_items] stream lengths in joined order, the table tsqa_decompress_device_sized* takes.  On any nonzero status
+ *      not one byte of d_out and not one word of d_block_sizes is written.  Nothing at or past d_out + out_cap is ever written,
+ *      nothing past first_block[n_items] words of the table, and the copy reads no arena byte outside an accepted item's frames.
+ *   6. Measure only: d_out == NULL with out_cap == 0.  cap_blocks still bounds the walk; the tables, the verdicts and *d_out_size
+ *      are made, and *d_status = TSQA_ERR_OVERFLOW when every item passes.
+ * cap_blocks sizes the context's per-block descriptor scratch (48 B per block): pass a tight value.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL arena, table or status pointer (d_out and
+ * d_block_sizes may be NULL), n_items == 0, cap_blocks == 0, a non-NULL d_out with out_cap < 16, a NULL d_out with out_cap != 0,
+ * [d_out, d_out + out_cap) overlapping [d_arena, d_arena + arena_size).
+ * The item table, the frame descriptors and the body places live in the context's scratch; the call returns at once and may be
+ * enqueued again on the same stream before the first has run (a call with more items or blocks than any before it first waits
+ * for the device, then grows the scratch).
+ * tsqa_join: the same, then waits.  *out_size (host) = *d_out_size, *n_blocks = first_block[n_items] (saturated at 2^32 - 1): behind
+ *   TSQA_OK the joined container's size and block count, behind TSQA_ERR_OVERFLOW what a retry needs.  Returns the status.
+ */
+int tsqa_plan_join(const uint64_t *frame_bytes, const uint32_t *blocks, const uint64_t *totals, uint32_t n_items,
+                   uint64_t *body_at, uint64_t *first_block, uint32_t *n_blocks, uint64_t *total, uint64_t *size);
+int tsqa_join_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets, const uint64_t *d_sizes,
+                    uint32_t n_items, uint32_t cap_blocks, void *d_out, size_t out_cap, uint64_t *d_out_size,
+                    uint64_t *d_first_block, uint32_t *d_block_sizes, int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+int tsqa_join(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets, const uint64_t *d_sizes,
+              uint32_t n_items, uint32_t cap_blocks, void *d_out, size_t out_cap, size_t *out_size, uint32_t *n_blocks,
+              uint64_t *d_first_block, uint32_t *d_block_sizes, int32_t *d_item_status, void *hip_stream);
 
 /*
  * Short blocks: ONE container whose blocks are block_len bytes long instead of TSQ_BLOCK_SZ.  A job's speed follows its block

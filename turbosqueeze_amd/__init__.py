@@ -28,6 +28,7 @@ from .api import (  # noqa: F401
     plan_compress_tables,
     plan_dense,
     plan_item_ranges,
+    plan_join,
     plan_packed,
     plan_ranges,
     plan_split,

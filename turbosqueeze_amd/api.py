@@ -130,6 +130,8 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_async_cb.argtypes = [vp, vp, C.c_size_t, C.c_bool, u8pp, szp, C.c_bool, vp, vp, vp]
     L.tsqa_profile_read_calls.restype = C.c_int
     L.tsqa_profile_read_calls.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_profile_read_join.restype = C.c_int
+    L.tsqa_profile_read_join.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_encode_blocks_async.restype = C.c_int
     L.tsqa_encode_blocks_async.argtypes = [vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.tsqa_decode_blocks_async.restype = C.c_int
@@ -203,6 +205,12 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_compress_batch_packed_tables_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
                                                           C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_batch_packed_items_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.tsqa_plan_join.restype = C.c_int
+    L.tsqa_plan_join.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, u32p, u64p, u64p]
+    L.tsqa_join_async.restype = C.c_int
+    L.tsqa_join_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.tsqa_join.restype = C.c_int
+    L.tsqa_join.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, szp, u32p, vp, vp, vp, vp]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -472,6 +480,29 @@ def plan_compress_tables(in_offsets, in_sizes, in_size: int, align: int = 16, ca
     return [int(x) for x in first], [int(x) for x in status], int(bound.value), int(n_fit.value)
 
 
+def plan_join(frame_bytes, blocks, totals):
+    """tsqa_plan_join (host only): the join of containers with these frame bytes (from a container's start to the end of its last
+    frame), block counts and uncompressed sizes -> (body_at, then the joined size; first_block, then the block sum; the joined
+    header's block count and total; the joined size).  Raises TsqError(3) when refused, and TsqError(6) -- with .body_at and
+    .first_block, which are still made -- when the block sum does not fit 32 bits."""
+    import numpy as np
+    fb = np.ascontiguousarray(frame_bytes, dtype=np.uint64)
+    nb = np.ascontiguousarray(blocks, dtype=np.uint32)
+    tot = np.ascontiguousarray(totals, dtype=np.uint64)
+    n = min(len(fb), len(nb), len(tot))
+    body_at, first = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    n_blocks, total, size = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    rc = lib().tsqa_plan_join(fb.ctypes.data, nb.ctypes.data, tot.ctypes.data, n, body_at.ctypes.data, first.ctypes.data, C.byref(n_blocks),
+                              C.byref(total), C.byref(size))
+    if rc == 6:
+        e = TsqError(rc, "the joined block count does not fit 32 bits")
+        e.body_at, e.first_block = [int(x) for x in body_at], [int(x) for x in first]
+        raise e
+    if rc:
+        raise TsqError(rc, "tsqa_plan_join refused the arguments")
+    return [int(x) for x in body_at], [int(x) for x in first], int(n_blocks.value), int(total.value), int(size.value)
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -647,6 +678,12 @@ class PackedBatch:
         """One index over the dense arena, for record reads: index().read(item, offset, length)."""
         return BatchIndex(self.codec, self.arena, list(zip(self.offsets, self.sizes)))
 
+    def join(self, out=None, block_sizes: bool = False):
+        """The batch as ONE .tsq container whose data is the concatenation of the items' data (DeviceCodec.join of the views:
+        the arena is read in place, nothing is decoded).  -> the container trimmed to its size; block_sizes=True: -> (container,
+        the table of stream lengths that decompress_sized takes)."""
+        return self.codec.join(self.views, out=out, block_sizes=block_sizes)
+
 
 DONE_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_bool, C.c_void_p)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_double, C.c_void_p)
@@ -715,6 +752,12 @@ class DeviceCodec:
         em, dm, en, dn = C.c_double(0), C.c_double(0), C.c_uint32(0), C.c_uint32(0)
         self.L.tsqa_profile_read_calls(self.h, C.byref(em), C.byref(en), C.byref(dm), C.byref(dn))
         return em.value, en.value, dm.value, dn.value
+
+    def profile_read_join(self):
+        """-> (emit_ms_sum, launches): the copy kernel of join_async alone since the last read."""
+        ms, n = C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_join(self.h, C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
@@ -1108,6 +1151,61 @@ class DeviceCodec:
                                                              d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
+
+    def join_async(self, arena, d_offsets, d_sizes, n_items: int, cap_blocks: int, out, d_first_block, d_block_sizes, d_item_status) -> None:
+        """tsqa_join_async on the current stream, nothing waited for and nothing about the items taken from the host: the containers
+        arena[d_offsets[i]:][:d_sizes[i]] (int64 CUDA tensors) become one container in out, whose data is the concatenation of
+        theirs.  d_first_block: int64, n_items + 1; d_block_sizes: None, or an int32 CUDA tensor of at least cap_blocks entries that
+        gets the joined stream lengths (what decompress_sized_async takes); d_item_status: int32, n_items.  The size and the status
+        land where compress_async leaves them (last_size_status).  All or nothing: on any nonzero status out is untouched.  out
+        None: measure only."""
+        if d_block_sizes is not None:
+            self._check_table(d_block_sizes, cap_blocks, at_least=True)
+        rc = self.L.tsqa_join_async(self.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(), int(n_items), int(cap_blocks),
+                                    out.data_ptr() if out is not None else None, out.numel() if out is not None else 0, self._size.data_ptr(),
+                                    d_first_block.data_ptr(), d_block_sizes.data_ptr() if d_block_sizes is not None else None,
+                                    d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def join(self, blobs, out=None, block_sizes: bool = False):
+        """Join .tsq containers (1-D uint8 CUDA tensors; placement as in compress_batch: views of one storage are read in place)
+        into ONE container that decodes to the concatenation of their data, at copy speed: nothing is decoded.  The block count
+        is measured on the device first (one small read); a new `out` has room for every byte of the items.  -> the container, a
+        view of `out` trimmed to its size; block_sizes=True: -> (container, the stream lengths of its blocks: an int32 CUDA tensor
+        for decompress_sized).  A refused item raises TsqError(4) with .item_status (one TSQA_ERR_* or 0 per item) and nothing is
+        written; an `out` that is too small raises TsqError(6) with .needed = the bytes a retry needs."""
+        torch = self.torch
+        arena, offs = self._arena(blobs)
+        n = len(blobs)
+        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != self.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        places = torch.tensor([offs, [b.numel() for b in blobs]], dtype=torch.int64).to(self.device)
+        d_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        d_status = torch.empty(n, dtype=torch.int32, device=self.device)
+
+        def refuse(code):
+            e = self._err(code)
+            e.item_status = d_status.cpu().tolist()
+            if code == 6:
+                e.needed = int(self._size.item())
+            return e
+
+        self._join()
+        self.join_async(arena, places[0], places[1], n, 1, None, d_first, None, d_status)      # (the headers only: first_block is complete)
+        self._join()
+        need_blocks = int(d_first[n].item())
+        if need_blocks == 0 or need_blocks >= 1 << 32:
+            raise refuse(4 if need_blocks == 0 else 6)
+        if out is None:
+            out = torch.empty(16 + sum(max(b.numel() - 16, 0) for b in blobs), dtype=torch.uint8, device=self.device)
+        table = torch.empty(need_blocks, dtype=torch.int32, device=self.device) if block_sizes else None
+        self.join_async(arena, places[0], places[1], n, need_blocks, out, d_first, table, d_status)
+        self._join()
+        size, status = self.last_size_status()
+        if status:
+            raise refuse(status)
+        return (out[:size], table) if block_sizes else out[:size]
 
     def compress_batch_packed_tables_async(self, data, d_in_offsets, d_in_sizes, n_items: int, cap_blocks: int, ext: int, align: int, out,
                                            d_offsets, d_sizes, d_first_block, d_bound, d_item_status) -> None:

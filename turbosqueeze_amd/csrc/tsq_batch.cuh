@@ -365,7 +365,10 @@ constexpr uint64_t kItemRefused = ~0ull;  // sizes[i] of an item whose container
 //                 status[] is zero before the kernel runs, apart from the verdicts of the dense call's own kernels, which it repeats.
 //   kWalkIndex    tsqa_index_create_batch: no capacity; n_blocks is the count the item's header states (0: the host has refused the
 //                 header already); sizes[i] = kItemRefused (its descriptors are then not to be used), status is not used.
-enum BatchWalkMode : int { kWalkOneWord, kWalkPerItem, kWalkIndex };
+//   kWalkJoin     tsqa_join_async (tsq_join.cuh): no capacity; sizes[i] = the item's frame bytes, from its start to the end of its
+//                 last frame (what lies behind that is legal and is not part of the join), 0 for a refused item; status[i] as
+//                 kWalkPerItem, behind the verdicts of the join's own kernels; no owners.
+enum BatchWalkMode : int { kWalkOneWord, kWalkPerItem, kWalkIndex, kWalkJoin };
 
 // One lane per item of a batch: the item's container is walked and validated as frame_walk_kernel walks one (the header, its block
 // count against the caller's -- a count of 0 is refused in every mode, as no header states it --, the mode's checks, walk_frames).
@@ -384,19 +387,20 @@ __global__ __launch_bounds__(256) void batch_walk_kernel(const uint8_t* __restri
     FrameInfo* const fr = frames + it.first_block;
     if constexpr (M == kWalkPerItem) for (uint32_t b = 0; b < it.n_blocks; ++b) owner[it.first_block + b] = i;
     uint32_t nb = 0;
-    uint64_t total = 0;
+    uint64_t total = 0, end = kHeaderSize;
     const bool ok = it.n_blocks != 0u && read_header(c, it.in_len, &nb, &total) == kHeaderOk && nb == it.n_blocks &&
-                    (M == kWalkIndex || total <= it.out_cap) &&
+                    (M == kWalkIndex || M == kWalkJoin || total <= it.out_cap) &&
                     walk_frames(c, it.in_len, nb, total, [&](uint32_t b, uint64_t, FrameInfo f) {
+                        if constexpr (M == kWalkJoin) end = f.stream_at + f.stream_len;
                         f.stream_at += it.in_at; f.out_at += it.out_at;
                         fr[b] = f;
                         return true;
                     }) == kWalkOk;
-    sizes[i] = ok ? total : M == kWalkIndex ? kItemRefused : 0ull;
+    sizes[i] = ok ? (M == kWalkJoin ? end : total) : M == kWalkIndex ? kItemRefused : 0ull;
     if (ok) return;
     for (uint32_t b = 0; b < it.n_blocks; ++b) fr[b] = FrameInfo{0, 0, 0, 0, 0, 0};
     if constexpr (M == kWalkOneWord) atomicMax(status, kErrFormat);
-    if constexpr (M == kWalkPerItem) status[i] = it.unfit ? kErrOverflow : kErrFormat;
+    if constexpr (M == kWalkPerItem || M == kWalkJoin) status[i] = it.unfit ? kErrOverflow : kErrFormat;
 }
 
 // Behind the decode with a verdict per item, one lane per item: an item that the walk or a decoder refused gives no size, and the

@@ -14,6 +14,7 @@
 #include "tsq_serial.cuh"
 #include "tsq_split.cuh"
 #include "tsq_index.cuh"
+#include "tsq_join.cuh"
 #include "tsq_launch.cuh"
 
 #include <algorithm>
@@ -259,6 +260,16 @@ int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches)
     return table_blocks.grow(this, blocks) && table_launch_item.grow(this, launches) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the join (tsq_internal.h) beside the batch tables: the body places, doubled from 256 items like them.
+int tsqa_ctx::reserve_join(size_t n_items)
+{
+    if (int rc = reserve_batch(n_items)) return rc;
+    const size_t want = doubled(256, n_items) + 1;
+    if (!join_at.needs(want)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return join_at.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -329,6 +340,15 @@ extern "C" int tsqa_profile_read_calls(tsqa_ctx* c, double* comp_ms, uint32_t* c
     if (c->prof_pool.empty()) { if (comp_ms) *comp_ms = 0; if (comp_n) *comp_n = 0; if (decomp_ms) *decomp_ms = 0; if (decomp_n) *decomp_n = 0; return TSQA_OK; }
     drain_events(c, 2, comp_ms, comp_n);
     drain_events(c, 3, decomp_ms, decomp_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_join(tsqa_ctx* c, double* emit_ms, uint32_t* emit_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (emit_ms) *emit_ms = 0; if (emit_n) *emit_n = 0; return TSQA_OK; }
+    drain_events(c, 4, emit_ms, emit_n);
     return TSQA_OK;
 }
 
@@ -1637,6 +1657,99 @@ extern "C" int tsqa_decompress_batch_packed_dense_async(tsqa_ctx* c, const void*
     if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
     return decode_items_enqueue(c, in, static_cast<const BatchItem*>(c->batch_items), n_items, cap_blocks, static_cast<const uint32_t*>(c->batch_live),
                                 d_out, d_out_sizes, d_item_status, d_status, s);
+}
+
+// ---- join: the containers of a packed batch into one container, nothing decoded (tsq_join.cuh) ----
+
+extern "C" int tsqa_plan_join(const uint64_t* frame_bytes, const uint32_t* blocks, const uint64_t* totals, uint32_t n_items, uint64_t* body_at,
+                              uint64_t* first_block, uint32_t* n_blocks, uint64_t* total, uint64_t* size)
+{
+    if (!frame_bytes || !blocks || !totals || !body_at || !first_block || !n_blocks || !total || !size || n_items == 0) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (blocks[i] == 0 || frame_bytes[i] < kHeaderSize + (uint64_t)kMinFrameSize * blocks[i] || totals[i] > (uint64_t)blocks[i] * kBlockSize)
+            return TSQA_ERR_ARG;
+    uint64_t at = kHeaderSize, fb = 0, tot = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        body_at[i] = at; first_block[i] = fb;
+        at += frame_bytes[i] - kHeaderSize; fb += blocks[i]; tot += totals[i];
+    }
+    body_at[n_items] = at; first_block[n_items] = fb;
+    *n_blocks = (uint32_t)fb; *total = tot; *size = at;
+    return fb > 0xFFFFFFFFull ? TSQA_ERR_OVERFLOW : TSQA_OK;
+}
+
+// The workgroups of join_emit_kernel: one per piece of the room, at most eight per CU (they stride over the pieces).
+static uint32_t join_emit_groups(const tsqa_ctx* c, size_t out_cap)
+{
+    const uint64_t pieces = ((uint64_t)out_cap + 15u) / kJoinPiece + 1u, most = 8ull * (uint64_t)c->n_cus;
+    return (uint32_t)(pieces < most ? pieces : most);
+}
+
+extern "C" int tsqa_join_async(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                               uint32_t n_items, uint32_t cap_blocks, void* d_out, size_t out_cap, uint64_t* d_out_size, uint64_t* d_first_block,
+                               uint32_t* d_block_sizes, int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_arena || !d_offsets || !d_sizes || !d_out_size || !d_first_block || !d_item_status || !d_status) {
+        c->set_error("join: null pointer");
+        return TSQA_ERR_ARG;
+    }
+    if (n_items == 0) { c->set_error("join: no items"); return TSQA_ERR_ARG; }
+    if (cap_blocks == 0) { c->set_error("join: cap_blocks is 0"); return TSQA_ERR_ARG; }
+    if (d_out ? out_cap < kHeaderSize : out_cap != 0) {
+        c->set_error("join: an output needs out_cap of at least 16; measuring takes d_out NULL and out_cap 0");
+        return TSQA_ERR_ARG;
+    }
+    {
+        const uintptr_t a = (uintptr_t)d_arena, o = (uintptr_t)d_out;
+        if (d_out && o < a + arena_size && a < o + out_cap) { c->set_error("join: the output overlaps the arena"); return TSQA_ERR_ARG; }
+    }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_join(n_items)) return rc;
+    if (int rc = c->reserve(cap_blocks, false, false, true)) return rc;
+    c->forget_sharded();                                 // the frame walk below overwrites c->frames
+    const uint8_t* const in = static_cast<const uint8_t*>(d_arena);
+    const BatchItem* const items = c->batch_items;
+    const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(batch_measure_kernel, per_item, dim3(256), 0, s, in, c->batch_items, n_items, d_offsets, d_sizes, (uint64_t)arena_size,
+                       d_item_status);
+    hipLaunchKernelGGL(join_blocks_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, cap_blocks, d_first_block, d_item_status);
+    hipLaunchKernelGGL(batch_walk_kernel<kWalkJoin>, per_item, dim3(256), 0, s, in, items, n_items, c->frames, (uint32_t*)nullptr, c->batch_sizes,
+                       d_item_status);
+    hipLaunchKernelGGL(join_bodies_kernel, dim3(1), dim3(256), 0, s, items, n_items, static_cast<const uint64_t*>(c->batch_sizes),
+                       static_cast<const uint64_t*>(d_first_block), static_cast<const int32_t*>(d_item_status), static_cast<uint8_t*>(d_out),
+                       (uint64_t)out_cap, c->join_at, d_out_size, d_status);
+    if (d_out) {
+        ProfSpan span(c, 4, s);
+        hipLaunchKernelGGL(join_emit_kernel, dim3(join_emit_groups(c, out_cap)), dim3(256), 0, s, in, items, n_items,
+                           static_cast<const uint64_t*>(c->join_at), static_cast<uint8_t*>(d_out), static_cast<const uint64_t*>(d_out_size),
+                           static_cast<const int32_t*>(d_status));
+        span.end();
+        if (d_block_sizes)
+            hipLaunchKernelGGL(join_block_sizes_kernel, dim3((uint32_t)(((uint64_t)cap_blocks + 255u) / 256u)), dim3(256), 0, s,
+                               static_cast<const FrameInfo*>(c->frames), static_cast<const uint64_t*>(d_first_block), n_items, d_block_sizes,
+                               static_cast<const int32_t*>(d_status));
+    }
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_join(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets, const uint64_t* d_sizes, uint32_t n_items,
+                         uint32_t cap_blocks, void* d_out, size_t out_cap, size_t* out_size, uint32_t* n_blocks, uint64_t* d_first_block,
+                         uint32_t* d_block_sizes, int32_t* d_item_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!out_size || !n_blocks) { c->set_error("join: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_join_async(c, d_arena, arena_size, d_offsets, d_sizes, n_items, cap_blocks, d_out, out_cap, c->d_size, d_first_block,
+                                 d_block_sizes, d_item_status, c->d_status, s)) return rc;
+    uint64_t blocks = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&blocks, d_first_block + n_items, sizeof(blocks), hipMemcpyDeviceToHost, s));
+    const int rc = finish_sync(c, s, "join", out_size);
+    if (rc == TSQA_OK || rc == TSQA_ERR_FORMAT || rc == TSQA_ERR_OVERFLOW) *n_blocks = blocks > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)blocks;
+    return rc;
 }
 
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
