@@ -1,7 +1,8 @@
 """The scheduler behind the reference's own API (tsq_compat.hip: tsqDecompress_MT, tsqCompress_MT, the async forms, FILE* to FILE*) on
 the inputs of tests/mtgen.py: containers of uneven blocks and block counts around the ramped schedule down every source and sink,
 jobs that fail with batches in flight and the job after them on the same lanes, damaged and cut containers against the oracle,
-failures inside a queue of async jobs, and compress jobs whose look-ahead falls on a lane's leftovers.
+failures inside a queue of async jobs, compress jobs whose look-ahead falls on a lane's leftovers, and one context of each direction
+through jobs that change mode and size, so that every job meets the buffers the one before it left.
 
 Expected bytes are the builders' plain bytes or the oracle's output, never the output of a library entry point.  Everything runs in
 this process, on a few long-lived contexts; the environment is set before a context is allocated (TSQ_AMD_LANES, _BATCH_BLOCKS,
@@ -396,6 +397,57 @@ def test_lookahead_behind_the_input_is_zeros_on_a_reused_lane(tsq, oracle, tmp_p
         count("compress_failures")
 
 
+# ---------------------------------------------------------------- f. one lane's buffers across jobs that change mode and size
+
+# (which container, streamed file source, sink): on ONE context, so that each job meets the buffers the one before it left --
+# device buffers made without staging; staging wanted on both sides at an unchanged device capacity; device buffers that grow and
+# release their staging; staging made again at the new capacity; the small job once more, in buffers larger than it needs
+SEAM_JOBS = (("small", False, None), ("small", True, "map"), ("large", False, None), ("large", True, "pwrite"), ("small", True, None))
+
+
+@pytest.mark.parametrize("lanes", ["1", None])
+def test_one_context_through_jobs_that_change_mode_and_size(tsq, oracle, files, tmp_path, monkeypatch, lanes):
+    """The uneven unit and the largest valid container, decompressed by one context in the order of SEAM_JOBS: the builders' plain
+    bytes.  Then those plain bytes through one compression context in the same order and modes, with and without extensions: the
+    oracle's containers.  With one lane every job lands in the same buffers; then with the default lane count."""
+    for k in ("TSQ_AMD_LANES", "TSQ_AMD_BATCH_BLOCKS", "TSQ_AMD_FILE_BATCH_BLOCKS", "TSQ_AMD_DEVICES", "TSQ_AMD_NO_RAMP"):
+        monkeypatch.delenv(k, raising=False)
+    if lanes:
+        monkeypatch.setenv("TSQ_AMD_LANES", lanes)
+    by_name = {name: (name, blob, plain) for name, blob, plain, _ in valid_containers()}
+    which = {"small": by_name["uneven_unit"], "large": max(by_name.values(), key=lambda c: len(c[2]))}
+    assert mtgen.block_count(which["large"][1]) > mtgen.block_count(which["small"][1]) and len(which["large"][1]) > len(which["small"][1])
+    assert all(len(plain) < 12 << 20 for _, _, plain in which.values())
+    want = cached("seam_want", lambda: {(size, ext): oracle.compress(plain, ext, threads=2)
+                                        for size, (_, _, plain) in which.items() for ext in (0, 1)})
+    plain_files = {}
+    for size, (name, _, plain) in which.items():
+        plain_files[size] = tmp_path / f"{name}.bin"
+        plain_files[size].write_bytes(plain)
+    dst = tmp_path / "out.bin"
+
+    def run(ctx, src, streamed, sink, ext=0):
+        job_env(monkeypatch, streamed, sink or "")
+        if sink is None:
+            return ctx.run(src, ext=ext)
+        assert ctx.run(src, dst, ext=ext) is True
+        return dst.read_bytes()
+
+    with Context(tsq) as ctx:
+        for step, (size, streamed, sink) in enumerate(SEAM_JOBS):
+            name, blob, plain = which[size]
+            got = run(ctx, files[name] if streamed else blob, streamed, sink)
+            assert got is not None and len(got) == len(plain) and got == plain, (lanes, step, name)
+            count("seam_decompress")
+    with Context(tsq, compress=True) as ctx:
+        for step, (size, streamed, sink) in enumerate(SEAM_JOBS):
+            name, _, plain = which[size]
+            for ext in (0, 1):
+                got = run(ctx, plain_files[size] if streamed else plain, streamed, sink, ext)
+                assert got == want[(size, ext)], (lanes, step, name, ext)
+                count("seam_compress")
+
+
 # ---------------------------------------------------------------- no case was dropped
 
 def test_every_case_ran_down_every_path(oracle):
@@ -405,6 +457,6 @@ def test_every_case_ran_down_every_path(oracle):
     want = {path: n_valid for path in PATHS}
     want.update(progress=2, file_pointer_api=1, twins_mem_to_mem=n_twins, twins_streamed_to_mapped_file=n_twins,
                 damage_mem_to_mem=n_damaged, damage_streamed=(n_damaged + 2) // 3, fifo=30, chain=10, lookahead_memory=len(kept), lookahead_streamed=len(kept),
-                tiny_inputs=8, compress_failures=1)
+                tiny_inputs=8, compress_failures=1, seam_decompress=2 * len(SEAM_JOBS), seam_compress=4 * len(SEAM_JOBS))
     print("scheduler conformance counts:", dict(sorted(COUNTS.items())))
     assert {k: COUNTS.get(k, 0) for k in want} == want

@@ -79,14 +79,15 @@ size_t env_size(const char* name, size_t dflt)
 
 // TSQ_AMD_DEBUG=1: wall-clock marks of the scheduler's steps on stderr
 struct Marks {
+    const char* const who;                                   // the direction, in front of every mark
     const bool on = getenv("TSQ_AMD_DEBUG") != nullptr;
     double t0 = now();
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     void at(const char* what, int feeder = -1) {
         if (!on) return;
         const double t = now();
-        if (feeder < 0) fprintf(stderr, "turbosqueeze_amd: %8.2f ms  %s\n", (t - t0) * 1e3, what);
-        else fprintf(stderr, "turbosqueeze_amd: %8.2f ms  [feeder %d] %s\n", (t - t0) * 1e3, feeder, what);
+        if (feeder < 0) fprintf(stderr, "turbosqueeze_amd: %8.2f ms  %s: %s\n", (t - t0) * 1e3, who, what);
+        else fprintf(stderr, "turbosqueeze_amd: %8.2f ms  [feeder %d] %s: %s\n", (t - t0) * 1e3, feeder, who, what);
     }
 };
 
@@ -345,65 +346,70 @@ struct Sink {
     }
 };
 
-// ---- one pipeline lane ----
-struct Lane {
-    tsqa_ctx* dev = nullptr;
-    uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-    FrameInfo* h_frames = nullptr;
-    uint64_t* h_frame_at = nullptr;                            // pinned: frame offsets of a compressed batch (n_frames + 1)
-    size_t in_cap = 0, out_cap = 0, frames_cap = 0, h_in_cap = 0, h_out_cap = 0;
-    uint64_t* h_size = nullptr; int32_t* h_status = nullptr;   // pinned result words
-    hipEvent_t ev = nullptr;
+// "the lane's batch has been issued" (1) or could not be (2), set by the feeder, awaited by whoever drains the lane
+struct Issued {
+    std::mutex m;
+    std::condition_variable cv;
+    int state = 0;
+    void reset() { std::lock_guard<std::mutex> g(m); state = 0; }
+    void set(bool ok) { { std::lock_guard<std::mutex> g(m); state = ok ? 1 : 2; } cv.notify_all(); }
+    bool wait() { std::unique_lock<std::mutex> g(m); cv.wait(g, [this] { return state != 0; }); return state == 1; }
+};
 
-    bool init(int device) {
-        if (tsqa_create(device, &dev) != TSQA_OK) return false;
-        if (hipHostMalloc(&h_size, sizeof(uint64_t), hipHostMallocPortable) != hipSuccess) return false;
-        if (hipHostMalloc(&h_status, sizeof(int32_t), hipHostMallocPortable) != hipSuccess) return false;
-        return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-    }
-    // Device buffers always; pinned host staging only where a FILE* is on that side (memory-to-memory jobs copy
-    // straight between the caller's buffers and HBM: staging would cost a full extra pass over host memory).
-    bool reserve(size_t in_bytes, size_t out_bytes, size_t n_frames, bool stage_in, bool stage_out) {
-        (void)hipSetDevice(dev->device);
-        if (in_bytes > in_cap) {
-            (void)hipFree(d_in); d_in = nullptr; in_cap = 0;
-            (void)hipHostFree(h_in); h_in = nullptr; h_in_cap = 0;
-            if (hipMalloc(&d_in, in_bytes) != hipSuccess) return false;
-            in_cap = in_bytes;
-        }
-        if (stage_in && h_in_cap < in_cap) {
-            (void)hipHostFree(h_in); h_in = nullptr; h_in_cap = 0;
-            if (hipHostMalloc(&h_in, in_cap, hipHostMallocPortable) != hipSuccess) return false;
-            h_in_cap = in_cap;
-        }
-        if (out_bytes > out_cap) {
-            (void)hipFree(d_out); d_out = nullptr; out_cap = 0;
-            (void)hipHostFree(h_out); h_out = nullptr; h_out_cap = 0;
-            if (hipMalloc(&d_out, out_bytes) != hipSuccess) return false;
-            out_cap = out_bytes;
-        }
-        if (stage_out && h_out_cap < out_cap) {
-            (void)hipHostFree(h_out); h_out = nullptr; h_out_cap = 0;
-            if (hipHostMalloc(&h_out, out_cap, hipHostMallocPortable) != hipSuccess) return false;
-            h_out_cap = out_cap;
-        }
-        if (n_frames > frames_cap) {
-            (void)hipHostFree(h_frames); h_frames = nullptr; frames_cap = 0;
-            (void)hipHostFree(h_frame_at); h_frame_at = nullptr;
-            if (hipHostMalloc(&h_frames, n_frames * sizeof(FrameInfo), hipHostMallocPortable) != hipSuccess) return false;
-            if (hipHostMalloc(&h_frame_at, (n_frames + 1) * sizeof(uint64_t), hipHostMallocPortable) != hipSuccess) return false;
-            frames_cap = n_frames;
-        }
-        return true;
-    }
-    void destroy() {
+// ---- one pipeline lane ----
+// It owns what it holds and is never copied.  Members go in reverse order: the buffers are freed before the lane's context is destroyed.
+struct Lane {
+    struct Destroy { void operator()(tsqa_ctx* c) const { tsqa_destroy(c); } };
+    static constexpr unsigned kPortable = hipHostMallocPortable;   // (feeders and drainers copy with whatever device they have current)
+    std::unique_ptr<tsqa_ctx, Destroy> dev;
+    tsqa_scratch<uint8_t> d_in, d_out;
+    tsqa_pinned<uint8_t> h_in{kPortable}, h_out{kPortable};    // staging, at the device buffers' capacities
+    tsqa_pinned<FrameInfo> h_frames{kPortable};
+    tsqa_pinned<uint64_t> h_frame_at{kPortable};               // frame offsets of a compressed batch (n_frames + 1)
+    tsqa_pinned<uint64_t> h_size{kPortable};                   // result words
+    tsqa_pinned<int32_t> h_status{kPortable};
+    hipEvent_t ev = nullptr;
+    Issued issued;
+
+    ~Lane() {
         if (dev) (void)hipSetDevice(dev->device);
         if (ev) (void)hipEventDestroy(ev);
-        (void)hipHostFree(h_in); (void)hipHostFree(h_out); (void)hipHostFree(h_frames); (void)hipHostFree(h_frame_at);
-        (void)hipHostFree(h_size); (void)hipHostFree(h_status);
-        (void)hipFree(d_in); (void)hipFree(d_out);
-        tsqa_destroy(dev);
-        dev = nullptr;
+    }
+    bool init(int device) {
+        tsqa_ctx* c = nullptr;
+        if (tsqa_create(device, &c) != TSQA_OK) return false;
+        dev.reset(c);
+        return h_size.grow(1) == hipSuccess && h_status.grow(1) == hipSuccess &&
+               hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    }
+    // One side: the device buffer always; pinned host staging only where a FILE* is on that side (memory-to-memory jobs copy
+    // straight between the caller's buffers and HBM: staging would cost a full extra pass over host memory).  A device buffer that
+    // grows releases its staging buffer, and staging is made at the device buffer's capacity.
+    bool reserve_side(tsqa_scratch<uint8_t>& d, tsqa_pinned<uint8_t>& h, size_t bytes, bool staged) {
+        if (d.needs(bytes)) { h.reset(); if (!d.grow(dev.get(), bytes)) return false; }
+        return !staged || h.grow(d.cap) == hipSuccess;
+    }
+    bool reserve(size_t in_bytes, size_t out_bytes, size_t n_frames, bool stage_in, bool stage_out) {
+        (void)hipSetDevice(dev->device);
+        return reserve_side(d_in, h_in, in_bytes, stage_in) && reserve_side(d_out, h_out, out_bytes, stage_out) &&
+               h_frames.grow(n_frames) == hipSuccess && h_frame_at.grow(n_frames + 1) == hipSuccess;
+    }
+    // Decode enqueue: the bn frames that h_frames describes, their streams one slice of `len` bytes at `streams` (host memory).
+    bool enqueue_decode(const uint8_t* streams, size_t len, uint32_t bn) {
+        hipStream_t s = dev->stream;
+        return dev->reserve(bn, false, false) == TSQA_OK &&
+               hipMemcpyAsync(d_in, streams, len, hipMemcpyHostToDevice, s) == hipSuccess &&
+               hipMemcpyAsync(dev->frames, h_frames, bn * sizeof(FrameInfo), hipMemcpyHostToDevice, s) == hipSuccess &&
+               hipMemsetAsync(dev->d_status, 0, sizeof(int32_t), s) == hipSuccess &&
+               dev->launch_decode_frames(d_in, dev->frames, bn, d_out, dev->d_status, s) == TSQA_OK;
+    }
+    // The status word came back kErrStall: a sibling workgroup of a several-workgroups-per-block decode did not get onto the GPU in
+    // time.  The batch is still on the device -- once more with one workgroup per block, and the new status word is waited for.
+    bool decode_again(uint32_t bn) {
+        hipStream_t s = dev->stream;
+        return dev->decode_again(d_in, dev->frames, bn, d_out, dev->d_status, s) == TSQA_OK &&
+               hipMemcpyAsync(h_status, dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess &&
+               hipStreamSynchronize(s) == hipSuccess;
     }
 };
 
@@ -417,7 +423,42 @@ struct Job {
     std::function<void(uint32_t, double)> progress;
 };
 
-struct InFlight { size_t lane; uint32_t first_block, n_blocks; size_t out_bytes; };
+struct InFlight { size_t lane; uint32_t n_blocks; size_t out_bytes; };
+
+// A job of either direction while it runs.  (Members go in reverse order: the prefault stops before the sink closes.)
+struct Run {
+    Job& j;
+    Marks mk;
+    Source src;
+    Sink sink;
+    Prefault touch;
+    std::atomic<bool> ok{true};
+    uint32_t nb = 0, done_blocks = 0;
+    bool stage_in = false, stage_out = false;
+    Run(Job& job, const char* who) : j(job), mk{who} {}
+
+    // The sink at its bound: a file, or the malloc()ed result (tsq_threads.cpp:339,795).  From here on it is known which sides are staged
+    // (a mapped output file takes its bytes through pinned staging and a CPU copy: a device copy straight into file-backed pages runs at
+    // a fraction of the link's rate), and the marks count from here.
+    bool open_sink(size_t bound) {
+        if (j.outfile ? !sink.open_file_buffered(j.out_path.c_str(), bound) : !sink.open_mem(bound)) return false;
+        stage_in = src.mem == nullptr; stage_out = sink.mem == nullptr || sink.mapped;
+        mk.t0 = Marks::now(); mk.at("buffers opened");
+        return true;
+    }
+    // The n bytes the job may write are made resident beside the kernels: allocated ahead of the cursor (a mapped file) or touched.
+    void start_prefault(size_t n) {
+        if (sink.mapped) touch.start_mapped([this](size_t upto) { return sink.ensure_allocated(upto, true); }, [this] { return sink.cursor.load(); }, n);
+        else if (!stage_out) touch.start(sink.mem, n);
+    }
+    // (a mapped file is populated from its start while the batches land: nothing to wait for; a malloc'ed buffer is touched in
+    //  stripes and the batch's must be complete)
+    void wait_for_pages(size_t batch_bytes) {
+        if (stage_out) return;
+        touch.wait_front(sink.at + batch_bytes);
+        mk.at("output pages touched");
+    }
+};
 
 // One thread per listed device: it issues that device's batches (file read, copy to the device, launches).  A copy from pageable
 // memory holds the issuing thread for its whole duration; with one issuing thread for all devices the feeds would queue behind each
@@ -446,15 +487,6 @@ struct Feeder {
     void push(std::function<void()> fn) { { std::lock_guard<std::mutex> g(m); q.push_back(std::move(fn)); } cv.notify_one(); }
     void stop() { { std::lock_guard<std::mutex> g(m); quit = true; } cv.notify_all(); if (th.joinable()) th.join(); }
 };
-// "the lane's batch has been issued" (1) or could not be (2), set by the feeder, awaited by whoever drains the lane
-struct Issued {
-    std::mutex m;
-    std::condition_variable cv;
-    int state = 0;
-    void reset() { std::lock_guard<std::mutex> g(m); state = 0; }
-    void set(bool ok) { { std::lock_guard<std::mutex> g(m); state = ok ? 1 : 2; } cv.notify_all(); }
-    bool wait() { std::unique_lock<std::mutex> g(m); cv.wait(g, [this] { return state != 0; }); return state == 1; }
-};
 
 class Scheduler {
 public:
@@ -465,10 +497,8 @@ public:
         n_devices_ = (uint32_t)devs.size();
         size_t per_dev = env_size("TSQ_AMD_LANES", 4);
         for (size_t k = 0; k < per_dev * devs.size(); ++k) {
-            Lane l;
-            if (!l.init(devs[k % devs.size()])) { l.destroy(); for (auto& x : lanes_) x.destroy(); lanes_.clear(); return false; }
-            lanes_.push_back(l);
-            issued_.emplace_back(new Issued());
+            lanes_.emplace_back(new Lane());
+            if (!lanes_.back()->init(devs[k % devs.size()])) { lanes_.clear(); return false; }
         }
         for (size_t d = 0; d < devs.size(); ++d) { feeders_.emplace_back(new Feeder()); feeders_.back()->start(); }
         // one batch should fill the device: a block is one workgroup for its whole (serial) parse, and two of them share a CU
@@ -478,7 +508,7 @@ public:
         thread_ = std::thread([this] { loop(); });
         return true;
     }
-    uint32_t n_cus() const { return lanes_.empty() ? 0 : (uint32_t)lanes_[0].dev->n_cus; }
+    uint32_t n_cus() const { return lanes_.empty() ? 0 : (uint32_t)lanes_[0]->dev->n_cus; }
 
     uint32_t submit(Job&& j) {
         std::lock_guard<std::mutex> g(m_);
@@ -500,7 +530,6 @@ public:
         if (thread_.joinable()) thread_.join();
         for (auto& f : feeders_) f->stop();
         feeders_.clear();
-        for (auto& l : lanes_) l.destroy();
         lanes_.clear();
     }
 
@@ -613,148 +642,165 @@ private:
         }
     }
 
-    // ------------------------------------------------------------------ compression
-    bool run_compress(Job& j) {
-        Source src;
-        if (!src.open(j.in, j.szin, j.infile) || src.size == 0) {
-            if (verbose_ && j.infile) printf("Error: could not open input file.\n");          // tsq_threads.cpp:298-301
-            return false;
-        }
-        const size_t total = src.size;
-        const uint32_t nb = (uint32_t)tsqa_block_count(total);       // tsq_threads.cpp:313
-        Sink sink;
-        if (j.outfile) {
-            if (!sink.open_file_buffered(j.out_path.c_str(), tsqa_container_bound(total))) {
-                if (verbose_) printf("Error: could not open output file.\n");                   // tsq_threads.cpp:323-326
-                return false;
-            }
-        } else if (!sink.open_mem(tsqa_container_bound(total))) {                               // tsq_threads.cpp:339
-            if (verbose_) printf("Error: could not allocate output buffer.\n");                 // tsq_threads.cpp:343-346
-            return false;
-        }
-
-        uint8_t header[tsq::kHeaderSize];                            // tsq_threads.cpp:333-335,355-359
-        tsq::write_header(header, nb, total);
-        sink.write(header, sizeof(header));
-
-        bool ok = true;
-        std::deque<InFlight> fly;
-        uint32_t done_blocks = 0;
-        // (a mapped output file takes its bytes through pinned staging and a CPU copy: a device copy straight into file-backed pages
-        //  runs at a fraction of the link's rate)
-        const bool stage_in = src.mem == nullptr, stage_out = sink.mem == nullptr || sink.mapped;
-        const std::vector<uint32_t> sizes = job_batches(nb, stage_in || stage_out, true);
-        Marks mk; mk.at("compress: buffers opened");
-        Prefault touch;
-        if (sink.mapped) touch.start_mapped([&sink](size_t upto) { return sink.ensure_allocated(upto, true); }, [&sink] { return sink.cursor.load(); }, sink.cap);
-        else if (!stage_out) touch.start(sink.mem, sink.cap < total ? sink.cap : total);
-        auto drain_one = [&]() {
-            InFlight f = fly.front(); fly.pop_front();
-            Lane& l = lanes_[f.lane];
-            if (!issued_[f.lane]->wait()) { ok = false; return; }     // the lane's feeder has issued the batch (or failed to)
+    // ------------------------------------------------------------------ what both directions do with a batch
+    // Issue.  The lane's device feeder runs `enqueue` -- the direction's read (file sources), copies and launches on the lane's
+    // stream -- and behind it the status word's copy back and the lane's event; the lane's flag then says how that went.
+    template <class Enqueue>   // bool(Lane&, int feeder)
+    void issue(size_t lane_i, Enqueue enqueue) {
+        Lane& l = *lanes_[lane_i];
+        l.issued.reset();
+        const int feeder = (int)(lane_i % feeders_.size());
+        feeders_[feeder]->push([&l, feeder, enqueue] {
             (void)hipSetDevice(l.dev->device);
-            if (hipEventSynchronize(l.ev) != hipSuccess || *l.h_status != 0) { ok = false; return; }
-            size_t sz = (size_t)*l.h_size;                            // batch container: 16-byte header + frames
-            mk.at("compress: kernels done");
-            if (sz < 16 || sz > l.out_cap) { ok = false; return; }
-            // (a mapped file is populated from its start while the batches land: nothing to wait for; a malloc'ed buffer is touched in
-            //  one share per thread and must be complete)
-            if (!stage_out) { touch.wait_front(sink.at + sz); mk.at("compress: output pages touched"); }
-            // The frames come back in pieces of a few blocks, in block order, and every block reports progress as soon as
-            // its bytes have landed (tsq_threads.cpp:226-254: the writer emits a frame, then calls progress_cb).
-            const uint64_t* fat = l.h_frame_at;                       // frame offsets inside the batch container
-            const uint32_t piece = progress_piece(f.n_blocks, stage_out);
-            // (through staging the next piece is copied to pinned memory while this one is written)
-            auto fetch = [&](uint32_t p0) -> bool {
-                const uint32_t p1 = p0 + piece < f.n_blocks ? p0 + piece : f.n_blocks;
-                const size_t from = (size_t)fat[p0], len = (size_t)fat[p1] - from;
-                if (from < 16 || from + len > sz) return false;
-                return hipMemcpyAsync(l.h_out + from, l.d_out + from, len, hipMemcpyDeviceToHost, l.dev->stream) == hipSuccess;
-            };
-            if (stage_out && !fetch(0)) { ok = false; return; }
-            for (uint32_t p0 = 0; p0 < f.n_blocks && ok; p0 += piece) {
-                const uint32_t p1 = p0 + piece < f.n_blocks ? p0 + piece : f.n_blocks;
-                const size_t from = (size_t)fat[p0], len = (size_t)fat[p1] - from;
-                if (from < 16 || from + len > sz) { ok = false; return; }
-                if (stage_out) {
-                    if (hipStreamSynchronize(l.dev->stream) != hipSuccess) { ok = false; return; }
-                    if (p1 < f.n_blocks && !fetch(p1)) { ok = false; return; }
-                    sink.write(l.h_out + from, len);
-                } else {
-                    uint8_t* dst = sink.claim(len);                   // frames land in the caller's buffer directly
-                    if (!dst || hipMemcpyAsync(dst, l.d_out + from, len, hipMemcpyDeviceToHost, l.dev->stream) != hipSuccess ||
-                        hipStreamSynchronize(l.dev->stream) != hipSuccess) { ok = false; return; }
-                }
-                for (uint32_t b = p0; b < p1; ++b) {                  // tsq_threads.cpp:248-254
-                    done_blocks++;
-                    if (j.progress) j.progress(j.id, (double)done_blocks / (double)nb);
-                }
+            bool good = enqueue(l, feeder);
+            if (good) {
+                (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, l.dev->stream);
+                good = hipEventRecord(l.ev, l.dev->stream) == hipSuccess;
             }
-            mk.at("compress: D2H done");
-        };
-
-        for (uint32_t b0 = 0, k = 0; b0 < nb && ok; b0 += sizes[k], ++k) {
-            const uint32_t bn = sizes[k];
-            const size_t lane_i = k % lanes_.size();
-            while (ok && fly.size() >= lanes_.size()) drain_one();
-            if (!ok) break;
-            Lane& l = lanes_[lane_i];
-            const size_t at = (size_t)b0 * kBlockSize;
-            const size_t want = (size_t)bn * kBlockSize;
-            const size_t n = total - at < want ? total - at : want;
-            if (!l.reserve(want + kHalo, tsqa_container_bound(want), bn, stage_in, stage_out)) { ok = false; break; }
-            // the batch is issued by the lane's device feeder: read (file sources), copy to the device, kernels, result words
-            Issued* flag = issued_[lane_i].get();
-            flag->reset();
-            const int feeder = (int)(lane_i % feeders_.size());
-            const uint32_t ext = j.ext ? 1u : 0u;
-            feeders_[feeder]->push([&src, &mk, &l, flag, at, n, total, bn, stage_in, ext, feeder] {
-                bool good = true;
-                (void)hipSetDevice(l.dev->device);
-                hipStream_t s = l.dev->stream;
-                // the batch plus the first bytes of the next one: block k's look-ahead reads block k+1
-                size_t got = total - at < n + kHalo ? total - at : n + kHalo;
-                if (stage_in) {
-                    got = src.read_at(at, n + kHalo, l.h_in);
-                    mk.at("compress: batch read", feeder);
-                    good = got >= n && hipMemcpyAsync(l.d_in, l.h_in, got, hipMemcpyHostToDevice, s) == hipSuccess;
-                } else good = hipMemcpyAsync(l.d_in, src.mem + at, got, hipMemcpyHostToDevice, s) == hipSuccess;
-                mk.at("compress: H2D issued", feeder);
-                good = good && hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s) == hipSuccess;
-                good = good && l.dev->launch_encode(l.d_in, n, got, ext, l.dev->d_status, s) == TSQA_OK;
-                good = good && l.dev->launch_pack(n, ext, l.d_out, l.out_cap, l.dev->d_size, l.dev->d_status, s) == TSQA_OK;
-                if (good) {
-                    (void)hipMemcpyAsync(l.h_size, l.dev->d_size, sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-                    (void)hipMemcpyAsync(l.h_frame_at, l.dev->frame_at, (bn + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-                    (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                    good = hipEventRecord(l.ev, s) == hipSuccess;
-                }
-                flag->set(good);
-            });
-            fly.push_back({lane_i, b0, bn, 0});
+            l.issued.set(good);
+        });
+    }
+    // Drain head.  The lane's feeder has issued the batch (or failed to), its kernels have run, and the status word is 0 -- for a
+    // decode (retry_stall), after a second attempt where the first one stalled.
+    bool kernels_done(Run& r, const InFlight& f, bool retry_stall) {
+        Lane& l = *lanes_[f.lane];
+        if (!l.issued.wait()) return false;
+        (void)hipSetDevice(l.dev->device);
+        if (hipEventSynchronize(l.ev) != hipSuccess) return false;
+        if (retry_stall && *l.h_status == tsq::kErrStall) {
+            const bool good = l.decode_again(f.n_blocks);
+            r.mk.at("batch decoded again (stall)");
+            if (!good) return false;
         }
-        while (ok && !fly.empty()) drain_one();
-        for (const InFlight& f : fly) (void)issued_[f.lane]->wait();    // (after a failure: no feeder may still be working on this job's buffers)
-        for (auto& l : lanes_) { (void)hipSetDevice(l.dev->device); (void)hipStreamSynchronize(l.dev->stream); }
-        touch.cancel();                                               // nobody may still be touching (or allocating behind) the buffer when it is freed
-        if (!sink.finish()) ok = false;
-        if (!j.outfile) {
-            if (ok) { *j.out = sink.mem; *j.szout = sink.at; }       // tsq_threads.cpp:375-379; caller free()s
-            else { free(sink.mem); }
+        if (*l.h_status != 0) return false;
+        r.mk.at("kernels done");
+        return true;
+    }
+    // Piece loop.  A batch comes back in pieces of a few blocks, in block order, to its place in the result or -- a staged sink --
+    // through the lane's pinned buffer, from where it is written; the next piece's copy is in flight meanwhile.  Every block reports
+    // progress once its bytes have landed (tsq_threads.cpp:226-254,648-655: the writer emits a block, then calls progress_cb).
+    // where(p0, p1, from, len): the bytes of blocks p0 .. p1-1 in the lane's output buffer; false refuses offsets that do not fit.
+    template <class Where>
+    bool fetch_pieces(Run& r, Lane& l, uint32_t n_blocks, Where where) {
+        const uint32_t piece = progress_piece(n_blocks, r.stage_out);
+        hipStream_t s = l.dev->stream;
+        struct { uint8_t* at; size_t len; } cur = {nullptr, 0}, next = {nullptr, 0};      // where a piece lands on the host
+        auto fetch = [&](uint32_t p0) {
+            size_t from = 0;
+            if (!where(p0, p0 + piece < n_blocks ? p0 + piece : n_blocks, from, next.len)) return false;
+            next.at = r.stage_out ? l.h_out + from : r.sink.claim(next.len);
+            return next.at && hipMemcpyAsync(next.at, l.d_out + from, next.len, hipMemcpyDeviceToHost, s) == hipSuccess;
+        };
+        if (!fetch(0)) return false;
+        for (uint32_t p0 = 0; p0 < n_blocks && r.ok; p0 += piece) {
+            const uint32_t p1 = p0 + piece < n_blocks ? p0 + piece : n_blocks;
+            cur = next;
+            if (hipStreamSynchronize(s) != hipSuccess) return false;
+            if (p1 < n_blocks && !fetch(p1)) return false;
+            if (r.stage_out) r.sink.write(cur.at, cur.len);
+            for (uint32_t b = p0; b < p1; ++b) {
+                r.done_blocks++;
+                if (r.j.progress) r.j.progress(r.j.id, (double)r.done_blocks / (double)r.nb);
+            }
+        }
+        r.mk.at("D2H done");
+        return true;
+    }
+    // Job tail.  No feeder may still be working on this job's buffers and no stream either, and nobody may still be touching (or
+    // allocating behind) the result when it is handed over (tsq_threads.cpp:375-379; the caller free()s) or freed.
+    bool finish(Run& r, const std::deque<InFlight>& fly, bool ok) {
+        for (const InFlight& f : fly) (void)lanes_[f.lane]->issued.wait();
+        for (auto& l : lanes_) { (void)hipSetDevice(l->dev->device); (void)hipStreamSynchronize(l->dev->stream); }
+        r.touch.cancel();
+        if (!r.sink.finish()) ok = false;
+        if (!r.j.outfile) {
+            if (ok) { *r.j.out = r.sink.mem; *r.j.szout = r.sink.at; }
+            else { free(r.sink.mem); }
         }
         return ok;
     }
 
+    // ------------------------------------------------------------------ compression
+    bool run_compress(Job& j) {
+        Run r(j, "compress");
+        if (!r.src.open(j.in, j.szin, j.infile) || r.src.size == 0) {
+            if (verbose_ && j.infile) printf("Error: could not open input file.\n");          // tsq_threads.cpp:298-301
+            return false;
+        }
+        const size_t total = r.src.size;
+        r.nb = (uint32_t)tsqa_block_count(total);                    // tsq_threads.cpp:313
+        if (!r.open_sink(tsqa_container_bound(total))) {             // tsq_threads.cpp:323-326,343-346
+            if (verbose_) printf(j.outfile ? "Error: could not open output file.\n" : "Error: could not allocate output buffer.\n");
+            return false;
+        }
+        uint8_t header[tsq::kHeaderSize];                            // tsq_threads.cpp:333-335,355-359
+        tsq::write_header(header, r.nb, total);
+        r.sink.write(header, sizeof(header));
+
+        std::deque<InFlight> fly;
+        const std::vector<uint32_t> sizes = job_batches(r.nb, r.stage_in || r.stage_out, true);
+        r.start_prefault(r.sink.mapped ? r.sink.cap : total);
+        // compression drains on this thread: the oldest lane, before its turn comes again
+        auto drain_one = [&]() {
+            const InFlight f = fly.front(); fly.pop_front();
+            Lane& l = *lanes_[f.lane];
+            if (!kernels_done(r, f, false)) return false;
+            const size_t sz = (size_t)*l.h_size;                      // batch container: 16-byte header + frames
+            if (sz < 16 || sz > l.d_out.cap) return false;
+            r.wait_for_pages(sz);
+            const uint64_t* fat = l.h_frame_at;                       // frame offsets inside the batch container, made on the device
+            return fetch_pieces(r, l, f.n_blocks, [fat, sz](uint32_t p0, uint32_t p1, size_t& from, size_t& len) {
+                from = (size_t)fat[p0]; len = (size_t)fat[p1] - from;
+                return from >= 16 && from + len <= sz;
+            });
+        };
+        for (uint32_t b0 = 0, k = 0; b0 < r.nb && r.ok; b0 += sizes[k], ++k) {
+            const uint32_t bn = sizes[k];
+            const size_t lane_i = k % lanes_.size();
+            while (r.ok && fly.size() >= lanes_.size()) r.ok = drain_one();
+            if (!r.ok) break;
+            const size_t at = (size_t)b0 * kBlockSize;
+            const size_t want = (size_t)bn * kBlockSize;
+            const size_t n = total - at < want ? total - at : want;
+            if (!lanes_[lane_i]->reserve(want + kHalo, tsqa_container_bound(want), bn, r.stage_in, r.stage_out)) { r.ok = false; break; }
+            const uint32_t ext = j.ext ? 1u : 0u;
+            issue(lane_i, [&r, at, n, total, bn, ext](Lane& l, int feeder) {
+                hipStream_t s = l.dev->stream;
+                // the batch plus the first bytes of the next one: block k's look-ahead reads block k+1
+                size_t got = total - at < n + kHalo ? total - at : n + kHalo;
+                bool good;
+                if (r.stage_in) {
+                    got = r.src.read_at(at, n + kHalo, l.h_in);
+                    r.mk.at("batch read", feeder);
+                    good = got >= n && hipMemcpyAsync(l.d_in, l.h_in, got, hipMemcpyHostToDevice, s) == hipSuccess;
+                } else good = hipMemcpyAsync(l.d_in, r.src.mem + at, got, hipMemcpyHostToDevice, s) == hipSuccess;
+                r.mk.at("H2D issued", feeder);
+                good = good && hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s) == hipSuccess;
+                good = good && l.dev->launch_encode(l.d_in, n, got, ext, l.dev->d_status, s) == TSQA_OK;
+                good = good && l.dev->launch_pack(n, ext, l.d_out, l.d_out.cap, l.dev->d_size, l.dev->d_status, s) == TSQA_OK;
+                if (good) {
+                    (void)hipMemcpyAsync(l.h_size, l.dev->d_size, sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+                    (void)hipMemcpyAsync(l.h_frame_at, l.dev->frame_at, (bn + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+                }
+                return good;
+            });
+            fly.push_back({lane_i, bn, 0});
+        }
+        while (r.ok && !fly.empty()) r.ok = drain_one();
+        return finish(r, fly, r.ok);
+    }
+
     // ------------------------------------------------------------------ decompression
     bool run_decompress(Job& j) {
-        Source src;
-        if (!src.open(j.in, j.szin, j.infile)) {
+        Run r(j, "decompress");
+        if (!r.src.open(j.in, j.szin, j.infile)) {
             if (verbose_ && j.infile) printf("Error opening input file: %s\n", reinterpret_cast<const char*>(j.in));   // tsq_threads.cpp:714-717
             return false;
         }
+        Source& src = r.src;
         uint8_t header[tsq::kHeaderSize];
-        uint32_t nb = 0; uint64_t total = 0;
-        const int h = src.read_at(0, sizeof(header), header) == sizeof(header) ? tsq::read_header(header, src.size, &nb, &total) : tsq::kHeaderBadMagic;
+        uint64_t total = 0;
+        const int h = src.read_at(0, sizeof(header), header) == sizeof(header) ? tsq::read_header(header, src.size, &r.nb, &total) : tsq::kHeaderBadMagic;
         if (h == tsq::kHeaderBadMagic) {                                                       // tsq_threads.cpp:732-752
             if (verbose_) printf("Error: signature mismatch (expected TSQ1).\n");
             return false;
@@ -766,69 +812,26 @@ private:
         // The header is not trusted with an allocation before it has been held against the container (read_header's bounds), and
         // no stream expands more than 64x (eight 64-byte copies per 13-byte group).
         if (h != tsq::kHeaderOk || total / 64 > src.size) return false;
-        Sink sink;
-        if (j.outfile) { if (!sink.open_file_buffered(j.out_path.c_str(), (size_t)total + 128)) return false; }
-        else if (!sink.open_mem((size_t)total + 128)) return false;                            // tsq_threads.cpp:795
+        if (!r.open_sink((size_t)total + 128)) return false;
+        const uint32_t nb = r.nb;
 
-        Marks mk; mk.at("decompress: buffers opened");
-        std::atomic<bool> ok{true};
         std::deque<InFlight> fly;
         std::mutex fly_m;
         std::condition_variable fly_cv;
         bool fly_closed = false;
-        uint32_t done_blocks = 0;
-        const bool stage_in = src.mem == nullptr, stage_out = sink.mem == nullptr || sink.mapped;
-        const uint32_t batch = job_batch(nb, stage_in || stage_out);
-        const std::vector<uint32_t> sizes = job_batches(nb, stage_in || stage_out, false);
-        Prefault touch;
+        const uint32_t batch = job_batch(nb, r.stage_in || r.stage_out);
+        const std::vector<uint32_t> sizes = job_batches(nb, r.stage_in || r.stage_out, false);
         bool touching = false;
         auto drain = [&](const InFlight& f) {
-            Lane& l = lanes_[f.lane];
-            if (!issued_[f.lane]->wait()) { ok = false; return; }     // the lane's feeder has issued the batch (or failed to)
-            (void)hipSetDevice(l.dev->device);
-            if (hipEventSynchronize(l.ev) != hipSuccess) { ok = false; return; }
-            if (*l.h_status == tsq::kErrStall) {
-                // a sibling workgroup of a several-workgroups-per-block decode did not get onto the GPU in time: the batch is still on
-                // the device -- once more with one workgroup per block
-                hipStream_t s = l.dev->stream;
-                bool good = l.dev->decode_again(l.d_in, l.dev->frames, f.n_blocks, l.d_out, l.dev->d_status, s) == TSQA_OK;
-                good = good && hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
-                good = good && hipStreamSynchronize(s) == hipSuccess;
-                mk.at("decompress: batch decoded again (stall)");
-                if (!good) { ok = false; return; }
-            }
-            if (*l.h_status != 0) { ok = false; return; }
-            mk.at("decompress: kernels done");
-            // the blocks come back in pieces of a few blocks, in order; each block reports progress once it has landed
-            // (tsq_threads.cpp:648-655: the writer copies a block out, then calls progress_cb)
-            uint8_t* dst = stage_out ? nullptr : sink.claim(f.out_bytes);
-            if (!stage_out && dst) { touch.wait_front((size_t)(dst - sink.mem) + f.out_bytes); mk.at("decompress: output pages touched"); }
-            if (!stage_out && !dst) { ok = false; return; }
+            Lane& l = *lanes_[f.lane];
+            if (!kernels_done(r, f, true)) return false;
+            r.wait_for_pages(f.out_bytes);
             const FrameInfo* fr = l.h_frames;
-            const uint32_t piece = progress_piece(f.n_blocks, stage_out);
-            auto piece_span = [&](uint32_t p0, size_t& from, size_t& len) {
-                const uint32_t p1 = p0 + piece < f.n_blocks ? p0 + piece : f.n_blocks;
+            return fetch_pieces(r, l, f.n_blocks, [fr](uint32_t p0, uint32_t p1, size_t& from, size_t& len) {
                 from = (size_t)fr[p0].out_at;
                 len = (size_t)(fr[p1 - 1].out_at + fr[p1 - 1].out_len) - from;
-            };
-            auto fetch = [&](uint32_t p0) {      // piece p0.. to its place in the caller's buffer, or in the pinned staging buffer
-                size_t from, len; piece_span(p0, from, len);
-                return hipMemcpyAsync(stage_out ? l.h_out + from : dst + from, l.d_out + from, len, hipMemcpyDeviceToHost, l.dev->stream) == hipSuccess;
-            };
-            if (!fetch(0)) { ok = false; return; }
-            for (uint32_t p0 = 0; p0 < f.n_blocks && ok; p0 += piece) {
-                const uint32_t p1 = p0 + piece < f.n_blocks ? p0 + piece : f.n_blocks;
-                size_t from, len; piece_span(p0, from, len);
-                if (hipStreamSynchronize(l.dev->stream) != hipSuccess) { ok = false; return; }
-                if (stage_out && p1 < f.n_blocks && !fetch(p1)) { ok = false; return; }      // the next piece comes in while this one is written
-                if (stage_out) sink.write(l.h_out + from, len);
-                else if (p1 < f.n_blocks && !fetch(p1)) { ok = false; return; }
-                for (uint32_t b = p0; b < p1; ++b) {
-                    done_blocks++;
-                    if (j.progress) j.progress(j.id, (double)done_blocks / (double)nb);
-                }
-            }
-            mk.at("decompress: D2H done");
+                return true;
+            });
         };
 
         // The copies back run on their own thread (the reference's writer thread, tsq_threads.cpp:604-676): a copy from or to the
@@ -843,7 +846,8 @@ private:
                     if (fly.empty()) return;
                     f = fly.front();
                 }
-                if (ok) drain(f); else (void)issued_[f.lane]->wait();  // (after a failure: the feeder must be done with the lane all the same)
+                if (!r.ok) (void)lanes_[f.lane]->issued.wait();       // (after a failure: the feeder must be done with the lane all the same)
+                else if (!drain(f)) r.ok = false;
                 {
                     std::lock_guard<std::mutex> g(fly_m);
                     fly.pop_front();                                  // only now may the lane be used again
@@ -851,88 +855,68 @@ private:
                 fly_cv.notify_all();
             }
         });
-        auto close_drainer = [&]() {
-            { std::lock_guard<std::mutex> g(fly_m); fly_closed = true; }
-            fly_cv.notify_all();
-            if (drainer.joinable()) drainer.join();
-        };
         size_t at = tsq::kHeaderSize;         // container cursor: the frame walk is serial (tsq_threads.cpp:513-524)
         uint64_t produced = 0;
-        for (uint32_t b0 = 0, k = 0; b0 < nb && ok; ++k) {
+        for (uint32_t b0 = 0, k = 0; b0 < nb && r.ok; ++k) {
             const size_t lane_i = k % lanes_.size();
             {
                 std::unique_lock<std::mutex> g(fly_m);
                 fly_cv.wait(g, [&] { return fly.size() < lanes_.size(); });
             }
-            if (!ok) break;
-            Lane& l = lanes_[lane_i];
+            if (!r.ok) break;
+            Lane& l = *lanes_[lane_i];
             // sized by what is left of the job, not by the configured batch (a one-block container must not reserve gigabytes)
             const uint32_t sched = k < sizes.size() ? sizes[k] : batch;
             const uint32_t want_blocks = nb - b0 < sched ? nb - b0 : sched;
             size_t in_budget = (size_t)want_blocks * (tsq::kFrameWordSize + kSlotSize);
             if (in_budget > src.size - at) in_budget = src.size - at;
-            if (!l.reserve(in_budget + 16, (size_t)want_blocks * kBlockSize + 256, want_blocks, stage_in, stage_out)) { ok = false; break; }
+            if (!l.reserve(in_budget + 16, (size_t)want_blocks * kBlockSize + 256, want_blocks, r.stage_in, r.stage_out)) { r.ok = false; break; }
             // walk whole frames until the batch is full; the frames of a batch are one contiguous slice of the container
             size_t cur = 0; uint32_t bn = 0; size_t out_bytes = 0;
             while (b0 + bn < nb && bn < want_blocks) {
                 uint8_t fh[tsq::kMinFrameSize];
                 if (src.read_at(at + cur, sizeof(fh), fh) != sizeof(fh)) break;
                 FrameInfo& fi = l.h_frames[bn];
-                if (!tsq::read_frame(fh, at + cur, src.size, &fi)) { ok = false; break; }      // tsq_threads.cpp:513-531
+                if (!tsq::read_frame(fh, at + cur, src.size, &fi)) { r.ok = false; break; }    // tsq_threads.cpp:513-531
                 const size_t frame_bytes = tsq::kFrameWordSize + fi.stream_len;
-                if (cur + frame_bytes > l.in_cap) break;
-                if (produced + out_bytes + fi.out_len > total) { ok = false; break; }
+                if (cur + frame_bytes > l.d_in.cap) break;
+                if (produced + out_bytes + fi.out_len > total) { r.ok = false; break; }
                 fi.stream_at = cur + tsq::kFrameWordSize; fi.out_at = out_bytes;
                 out_bytes += fi.out_len; cur += frame_bytes; bn++;
             }
-            if (!ok) break;
-            if (bn == 0) { ok = false; break; }                        // truncated container
+            if (!r.ok) break;
+            if (bn == 0) { r.ok = false; break; }                      // truncated container
             // the result buffer is made resident only now that a first batch of frames has been found well formed
-            if (!touching && sink.mapped) { touch.start_mapped([&sink](size_t upto) { return sink.ensure_allocated(upto, true); }, [&sink] { return sink.cursor.load(); }, (size_t)total); touching = true; }
-            if (!touching && !stage_out) { touch.start(sink.mem, (size_t)total); touching = true; }
+            if (!touching) { r.start_prefault((size_t)total); touching = true; }
             // the batch's frames are one contiguous slice of the container: the lane's device feeder reads it (file sources), copies
             // it to the device and launches the kernels
-            Issued* flag = issued_[lane_i].get();
-            flag->reset();
-            const int feeder = (int)(lane_i % feeders_.size());
-            feeders_[feeder]->push([&src, &mk, &l, flag, at, cur, bn, stage_in, feeder] {
-                (void)hipSetDevice(l.dev->device);
-                hipStream_t s = l.dev->stream;
-                bool good = l.dev->reserve(bn, false, false) == TSQA_OK;
-                if (good && stage_in) { good = src.read_at(at, cur, l.h_in) == cur; mk.at("decompress: batch read", feeder); }
-                good = good && hipMemcpyAsync(l.d_in, stage_in ? l.h_in : src.mem + at, cur, hipMemcpyHostToDevice, s) == hipSuccess;
-                good = good && hipMemcpyAsync(l.dev->frames, l.h_frames, bn * sizeof(FrameInfo), hipMemcpyHostToDevice, s) == hipSuccess;
-                good = good && hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s) == hipSuccess;
-                good = good && l.dev->launch_decode_frames(l.d_in, l.dev->frames, bn, l.d_out, l.dev->d_status, s) == TSQA_OK;
-                if (good) {
-                    (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                    good = hipEventRecord(l.ev, s) == hipSuccess;
+            issue(lane_i, [&r, at, cur, bn](Lane& l, int feeder) {
+                if (r.stage_in) {
+                    const bool got = r.src.read_at(at, cur, l.h_in) == cur;
+                    r.mk.at("batch read", feeder);
+                    if (!got) return false;
                 }
-                mk.at("decompress: H2D + kernels issued", feeder);
-                flag->set(good);
+                const bool good = l.enqueue_decode(r.stage_in ? l.h_in : r.src.mem + at, cur, bn);
+                r.mk.at("H2D + kernels issued", feeder);
+                return good;
             });
             {
                 std::lock_guard<std::mutex> g(fly_m);
-                fly.push_back({lane_i, b0, bn, out_bytes});
+                fly.push_back({lane_i, bn, out_bytes});
             }
             fly_cv.notify_all();
             produced += out_bytes; at += cur; b0 += bn;
         }
-        close_drainer();                                              // (drains what is in flight first)
-        for (auto& l : lanes_) { (void)hipSetDevice(l.dev->device); (void)hipStreamSynchronize(l.dev->stream); }
-        touch.cancel();                                               // nobody may still be touching (or allocating behind) the buffer when it is freed
-        if (ok && produced != total) ok = false;
-        if (!sink.finish()) ok = false;
-        if (!j.outfile) {
-            if (ok) { *j.out = sink.mem; *j.szout = (size_t)total; }
-            else { free(sink.mem); }
+        {   // the drainer drains what is in flight first
+            { std::lock_guard<std::mutex> g(fly_m); fly_closed = true; }
+            fly_cv.notify_all();
+            drainer.join();
         }
-        return ok;
+        return finish(r, fly, r.ok && produced == total);
     }
 
     const bool compress_, verbose_;
-    std::vector<Lane> lanes_;                          // lane k works on device k % n_devices_ and is fed by feeder k % n_devices_
-    std::vector<std::unique_ptr<Issued>> issued_;      // one per lane
+    std::vector<std::unique_ptr<Lane>> lanes_;         // lane k works on device k % n_devices_ and is fed by feeder k % n_devices_
     std::vector<std::unique_ptr<Feeder>> feeders_;     // one per listed device
     uint32_t batch_blocks_ = 512, file_batch_blocks_ = 64, n_devices_ = 1;
     std::thread thread_;
@@ -984,16 +968,18 @@ bool run_sync(Scheduler* s, uint8_t* in, size_t szin, bool infile, uint8_t** out
 }
 
 // ---- single-block codec used by tsqEncode / tsqDecode ----
+// (deliberately leaked: nothing of it is destroyed at process exit, when the HIP runtime may be gone)
 struct BlockCodec {
     std::mutex m;
-    Lane lane;
-    bool tried = false, ready = false;
+    std::unique_ptr<Lane> lane;                        // made at the first call; a lane that could not be made whole is not kept
+    bool tried = false;
     bool ensure() {
-        if (tried) return ready;
+        if (tried) return lane != nullptr;
         tried = true;
-        ready = lane.init(device_list()[0]) && lane.reserve(kBlockSize + kHalo + kSlotSize, kSlotSize + 256, 1, true, true);
-        if (!ready) { complain_once("no usable gfx950 device (or HIP initialisation failed)"); }
-        return ready;
+        std::unique_ptr<Lane> l(new Lane());
+        if (l->init(device_list()[0]) && l->reserve(kBlockSize + kHalo + kSlotSize, kSlotSize + 256, 1, true, true)) lane = std::move(l);
+        else complain_once("no usable gfx950 device (or HIP initialisation failed)");
+        return lane != nullptr;
     }
 };
 BlockCodec& block_codec() { static BlockCodec* c = new BlockCodec(); return *c; }
@@ -1038,7 +1024,7 @@ extern "C" void tsqEncode(struct TSQCompressionContext* ctx, uint8_t* inputBlock
     BlockCodec& bc = block_codec();
     std::lock_guard<std::mutex> g(bc.m);
     if (!bc.ensure()) return;
-    Lane& l = bc.lane;
+    Lane& l = *bc.lane;
     (void)hipSetDevice(l.dev->device);
     hipStream_t s = l.dev->stream;
     memcpy(l.h_in, inputBlock, inputSize);
@@ -1088,24 +1074,16 @@ extern "C" void tsqDecode(uint8_t* inputBlock, uint8_t* outputBlock, uint32_t* o
     BlockCodec& bc = block_codec();
     std::lock_guard<std::mutex> g(bc.m);
     if (!bc.ensure()) return;
-    Lane& l = bc.lane;
+    Lane& l = *bc.lane;
     (void)hipSetDevice(l.dev->device);
     hipStream_t s = l.dev->stream;
-    if (l.dev->reserve(1, false, false) != TSQA_OK) return;
     memcpy(l.h_in, inputBlock, inputSize);
     FrameInfo& fi = l.h_frames[0];
     fi.stream_at = 0; fi.out_at = 0; fi.stream_len = inputSize; fi.ext = withExtensions ? 1u : 0u; fi.out_len = usize; fi.pad = 0;
-    if (hipMemcpyAsync(l.d_in, l.h_in, inputSize, hipMemcpyHostToDevice, s) != hipSuccess) return;
-    (void)hipMemcpyAsync(l.dev->frames, l.h_frames, sizeof(FrameInfo), hipMemcpyHostToDevice, s);
-    (void)hipMemsetAsync(l.dev->d_status, 0, sizeof(int32_t), s);
-    if (l.dev->launch_decode_frames(l.d_in, l.dev->frames, 1, l.d_out, l.dev->d_status, s) != TSQA_OK) return;
+    if (!l.enqueue_decode(l.h_in, inputSize, 1)) return;
     (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return;
-    if (*l.h_status == tsq::kErrStall) {          // (a sibling workgroup did not get onto the GPU in time: once more on one workgroup)
-        if (l.dev->decode_again(l.d_in, l.dev->frames, 1, l.d_out, l.dev->d_status, s) != TSQA_OK) return;
-        (void)hipMemcpyAsync(l.h_status, l.dev->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return;
-    }
+    if (*l.h_status == tsq::kErrStall && !l.decode_again(1)) return;
     if (*l.h_status != 0) return;
     (void)hipMemcpyAsync(l.h_out, l.d_out, usize, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return;
@@ -1113,17 +1091,15 @@ extern "C" void tsqDecode(uint8_t* inputBlock, uint8_t* outputBlock, uint32_t* o
     *outputSize = usize;
 }
 
-// ---- _MT contexts ----
+// ---- _MT contexts: {num_cores, the scheduler} ----
 
-extern "C" struct TSQCompressionContext_MT* tsqAllocateContextCompression_MT(bool verbose)
+namespace {
+template <class Ctx> Ctx* allocate_mt(bool compress, bool verbose)
 {
-    Scheduler* s = make_scheduler(true, verbose);
-    if (!s) return nullptr;
-    auto* c = new TSQCompressionContext_MT{s->n_cus(), s};
-    return c;
+    Scheduler* s = make_scheduler(compress, verbose);
+    return s ? new Ctx{s->n_cus(), s} : nullptr;
 }
-
-extern "C" void tsqDeallocateContextCompression_MT(struct TSQCompressionContext_MT* ctx)
+template <class Ctx> void deallocate_mt(Ctx* ctx)
 {
     if (!ctx) return;
     auto* s = static_cast<Scheduler*>(ctx->impl);
@@ -1131,23 +1107,12 @@ extern "C" void tsqDeallocateContextCompression_MT(struct TSQCompressionContext_
     delete s;
     delete ctx;
 }
+}  // namespace
 
-extern "C" struct TSQDecompressionContext_MT* tsqAllocateContextDecompression_MT(bool verbose)
-{
-    Scheduler* s = make_scheduler(false, verbose);
-    if (!s) return nullptr;
-    auto* c = new TSQDecompressionContext_MT{s->n_cus(), s};
-    return c;
-}
-
-extern "C" void tsqDeallocateContextDecompression_MT(struct TSQDecompressionContext_MT* ctx)
-{
-    if (!ctx) return;
-    auto* s = static_cast<Scheduler*>(ctx->impl);
-    s->stop();
-    delete s;
-    delete ctx;
-}
+extern "C" struct TSQCompressionContext_MT* tsqAllocateContextCompression_MT(bool verbose) { return allocate_mt<TSQCompressionContext_MT>(true, verbose); }
+extern "C" void tsqDeallocateContextCompression_MT(struct TSQCompressionContext_MT* ctx) { deallocate_mt(ctx); }
+extern "C" struct TSQDecompressionContext_MT* tsqAllocateContextDecompression_MT(bool verbose) { return allocate_mt<TSQDecompressionContext_MT>(false, verbose); }
+extern "C" void tsqDeallocateContextDecompression_MT(struct TSQDecompressionContext_MT* ctx) { deallocate_mt(ctx); }
 
 extern "C" bool tsqCompress_MT(struct TSQCompressionContext_MT* ctx, uint8_t* in, size_t szin, bool infile, uint8_t** out,
                                size_t* szout, bool outfile, bool useextensions, uint32_t level)
@@ -1181,26 +1146,30 @@ extern "C" uint32_t tsqDecompressAsync_MT(TSQDecompressionContext_MT* ctx, uint8
                       std::move(done), std::move(progress));
 }
 
-extern "C" uint32_t tsqa_compress_async_cb(struct TSQCompressionContext_MT* ctx, uint8_t* in, size_t szin, bool infile, uint8_t** out,
-                                           size_t* szout, bool outfile, bool useextensions, uint32_t level, tsqa_done_fn done,
-                                           tsqa_progress_fn progress, void* user)
+// the C callbacks (a function pointer each, either may be NULL, and one user pointer) as the std::function pair of the async forms
+static std::pair<std::function<void(uint32_t, bool)>, std::function<void(uint32_t, double)>> callbacks(tsqa_done_fn done, tsqa_progress_fn progress, void* user)
 {
     std::function<void(uint32_t, bool)> d;
     std::function<void(uint32_t, double)> p;
     if (done) d = [done, user](uint32_t id, bool ok) { done(id, ok, user); };
     if (progress) p = [progress, user](uint32_t id, double f) { progress(id, f, user); };
-    return tsqCompressAsync_MT(ctx, in, szin, infile, out, szout, outfile, useextensions, level, std::move(d), std::move(p));
+    return {std::move(d), std::move(p)};
+}
+
+extern "C" uint32_t tsqa_compress_async_cb(struct TSQCompressionContext_MT* ctx, uint8_t* in, size_t szin, bool infile, uint8_t** out,
+                                           size_t* szout, bool outfile, bool useextensions, uint32_t level, tsqa_done_fn done,
+                                           tsqa_progress_fn progress, void* user)
+{
+    auto cb = callbacks(done, progress, user);
+    return tsqCompressAsync_MT(ctx, in, szin, infile, out, szout, outfile, useextensions, level, std::move(cb.first), std::move(cb.second));
 }
 
 extern "C" uint32_t tsqa_decompress_async_cb(struct TSQDecompressionContext_MT* ctx, uint8_t* in, size_t szin, bool infile,
                                              uint8_t** out, size_t* szout, bool outfile, tsqa_done_fn done,
                                              tsqa_progress_fn progress, void* user)
 {
-    std::function<void(uint32_t, bool)> d;
-    std::function<void(uint32_t, double)> p;
-    if (done) d = [done, user](uint32_t id, bool ok) { done(id, ok, user); };
-    if (progress) p = [progress, user](uint32_t id, double f) { progress(id, f, user); };
-    return tsqDecompressAsync_MT(ctx, in, szin, infile, out, szout, outfile, std::move(d), std::move(p));
+    auto cb = callbacks(done, progress, user);
+    return tsqDecompressAsync_MT(ctx, in, szin, infile, out, szout, outfile, std::move(cb.first), std::move(cb.second));
 }
 
 // ---- FILE* to FILE* (turbosqueeze.cpp:48-147): same scheduler, streams supplied by the caller ----

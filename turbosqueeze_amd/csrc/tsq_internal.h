@@ -29,11 +29,35 @@ template <class T> struct tsqa_scratch {
     bool grow(tsqa_ctx* c, size_t n);          // to n elements where needs(n); false: refused, the error is set
 };
 
+// Its sibling in pinned host memory, with the same rules: grow() frees before it allocates, and a failed allocation -- returned, for
+// the caller to report -- leaves a null pointer and capacity 0.  How the memory is pinned belongs to the buffer: hipHostMallocPortable
+// where threads that have other devices current copy from it (the scheduler's lanes), hipHostMallocDefault otherwise.
+template <class T> struct tsqa_pinned {
+    T* p = nullptr;
+    size_t cap = 0;
+    const unsigned flags;
+    explicit tsqa_pinned(unsigned f = hipHostMallocDefault) : flags(f) {}
+    tsqa_pinned(const tsqa_pinned&) = delete;
+    tsqa_pinned& operator=(const tsqa_pinned&) = delete;
+    ~tsqa_pinned() { reset(); }
+    operator T*() const { return p; }
+    bool needs(size_t n) const { return n > cap; }
+    void reset() { (void)hipHostFree(p); p = nullptr; cap = 0; }
+    hipError_t grow(size_t n)                  // to n elements where needs(n)
+    {
+        if (!needs(n)) return hipSuccess;
+        reset();
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), flags);
+        if (e != hipSuccess) p = nullptr; else cap = n;
+        return e;
+    }
+};
+
 // Descriptors a call plans on the host for its kernels (range-read items, batch descriptors): a ring of two slots, used in turn, each a
 // pinned host buffer and its copy on the device, grown by doubling.  A slot is reused once the call that used it has finished: two
 // calls can be in flight, the third waits for the first.
 class tsqa_uploads {
-    void* host_[2] = {nullptr, nullptr};
+    tsqa_pinned<uint8_t> host_[2];
     tsqa_scratch<uint8_t> dev_[2];             // (the capacity of both copies, in bytes)
     hipEvent_t done_[2] = {nullptr, nullptr};
     bool pending_[2] = {false, false};
@@ -45,7 +69,7 @@ public:
     struct Slot {
         tsqa_uploads* u = nullptr;
         int k = 0;
-        template <class T> T* host(size_t at = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(u->host_[k]) + at); }
+        template <class T> T* host(size_t at = 0) const { return reinterpret_cast<T*>(u->host_[k] + at); }
         template <class T> T* dev(size_t at = 0) const { return reinterpret_cast<T*>(u->dev_[k] + at); }
         size_t cap() const { return u->dev_[k].cap; }
         hipError_t send(size_t bytes, hipStream_t s) const { return hipMemcpyAsync(u->dev_[k], u->host_[k], bytes, hipMemcpyHostToDevice, s); }
@@ -74,8 +98,7 @@ struct tsqa_ctx {
     tsqa_scratch<tsq::FrameInfo> frames;       // n_blocks frame descriptors (decode)
     tsqa_scratch<uint32_t> block_owner;        // n_blocks: the batch item each frame belongs to (tsqa_decompress_batch_items_async)
     tsqa_scratch<uint16_t> tables;             // n_blocks x 2^17 u16 position tables of the encoders
-    tsq::FrameInfo* host_frames = nullptr;     // frame descriptors built on the host (sharded fetch + decode): pinned
-    size_t cap_host_frames = 0;
+    tsqa_pinned<tsq::FrameInfo> host_frames;   // frame descriptors built on the host (sharded fetch + decode)
     std::vector<uint64_t> host_frame_src;      // where each owned frame's stream starts in the host container
     hipEvent_t host_frames_copied = nullptr;   // recorded behind the descriptors' copy to the device
     bool host_frames_pending = false;

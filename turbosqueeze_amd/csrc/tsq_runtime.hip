@@ -141,10 +141,9 @@ extern "C" void tsqa_destroy(tsqa_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_pool) if (e) (void)hipEventDestroy(e);
-    if (c->host_frames) (void)hipHostFree(c->host_frames);
     if (c->host_frames_copied) (void)hipEventDestroy(c->host_frames_copied);
     c->range_up.destroy(); c->batch_up.destroy();
-    delete c;                                            // (the scratch buffers free themselves)
+    delete c;                                            // (the scratch and pinned buffers free themselves)
 }
 
 extern "C" const char* tsqa_last_error(const tsqa_ctx* c) { return c ? c->err : "null context"; }
@@ -198,14 +197,8 @@ int tsqa_ctx::reserve_host_frames(size_t n)
     (void)hipSetDevice(device);
     if (host_frames_pending) { (void)hipEventSynchronize(host_frames_copied); host_frames_pending = false; }
     if (!host_frames_copied) TSQ_HIP(this, hipEventCreateWithFlags(&host_frames_copied, hipEventDisableTiming));
-    if (n > cap_host_frames) {
-        if (host_frames) (void)hipHostFree(host_frames);
-        host_frames = nullptr; cap_host_frames = 0;
-        const size_t want = doubled(64, n);
-        TSQ_HIP(this, hipHostMalloc(reinterpret_cast<void**>(&host_frames), want * sizeof(FrameInfo), hipHostMallocDefault));
-        cap_host_frames = want;
-    }
-    host_frame_src.resize(cap_host_frames);
+    if (host_frames.needs(n)) TSQ_HIP(this, host_frames.grow(doubled(64, n)));
+    host_frame_src.resize(host_frames.cap);
     return TSQA_OK;
 }
 
@@ -217,10 +210,9 @@ int tsqa_uploads::acquire(tsqa_ctx* c, size_t bytes, Slot* slot)
     if (pending_[k]) { (void)hipEventSynchronize(done_[k]); pending_[k] = false; }
     if (!done_[k]) TSQ_HIP(c, hipEventCreateWithFlags(&done_[k], hipEventDisableTiming));
     if (dev_[k].needs(bytes)) {
-        if (host_[k]) (void)hipHostFree(host_[k]);
-        host_[k] = nullptr; dev_[k].reset();
         const size_t want = doubled(4096, bytes);
-        TSQ_HIP(c, hipHostMalloc(&host_[k], want, hipHostMallocDefault));
+        host_[k].reset(); dev_[k].reset();
+        TSQ_HIP(c, host_[k].grow(want));
         if (!dev_[k].grow(c, want)) return TSQA_ERR_HIP;
     }
     *slot = Slot{this, k};
@@ -229,10 +221,8 @@ int tsqa_uploads::acquire(tsqa_ctx* c, size_t bytes, Slot* slot)
 
 void tsqa_uploads::destroy()
 {
-    for (int k = 0; k < 2; ++k) {
-        if (host_[k]) (void)hipHostFree(host_[k]);
+    for (int k = 0; k < 2; ++k)
         if (done_[k]) (void)hipEventDestroy(done_[k]);
-    }
 }
 
 // Per-item scratch of the batch entry points (tsq_internal.h), doubled from 256 items.
