@@ -184,6 +184,8 @@ int tsqa_profile_read_calls(tsqa_ctx *ctx, double *compress_ms, uint32_t *compre
                             double *decompress_ms, uint32_t *decompress_calls);
 /* The same for the copy kernel of tsqa_join_async alone (its other launches are short and lie outside the span). */
 int tsqa_profile_read_join(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launches);
+/* The same for the copy kernel of tsqa_cut_async alone. */
+int tsqa_profile_read_cut(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launches);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -544,6 +546,60 @@ int tsqa_join_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const
 int tsqa_join(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets, const uint64_t *d_sizes,
               uint32_t n_items, uint32_t cap_blocks, void *d_out, size_t out_cap, size_t *out_size, uint32_t *n_blocks,
               uint64_t *d_first_block, uint32_t *d_block_sizes, int32_t *d_item_status, void *hip_stream);
+
+/*
+ * Cut: block ranges of an indexed container, each as a container of its own, at copy speed -- the way back from the join.  The
+ * frames of blocks [first, first + count) are one contiguous span of the container, every frame carries its own ext bit, and a
+ * reader starts block k where the blocks before it end, so
+ *   "TSQ1" | u32 count | u64 totals[k] | the container's bytes [frame(first), end(first + count - 1))
+ * is a valid container and decodes to exactly those blocks' data.  Nothing is decoded, so -- unlike a range read that is
+ * compressed again -- the bytes are the source's own.  cut(join(items)) at the join's d_first_block gives the items back byte for
+ * byte; join([cut(a, 0..k), new, cut(a, k+1..nb)]) is the edit of block k; with short blocks a block is a page.
+ * The cut leaves d_offsets / d_sizes in the packed-arena shape: tsqa_join_async, tsqa_decompress_batch_packed_dense_async and the
+ * other calls that take a packed batch take its output unchanged.
+ *
+ * tsqa_plan_cut: host only, rules 2 to 5 below from host tables.  frame_at: the n_blocks + 1 frame boundaries (tsqa_walk_frames'
+ *   frame_at with the end of the last frame appended); out_start: the array tsqa_plan_ranges takes.  offsets (n_ranges + 1), sizes,
+ *   totals (may be NULL) and item_status (n_ranges) are filled; *n_fit = the first accepted range that does not fit out_size,
+ *   n_ranges when all do.  TSQA_ERR_ARG for a NULL pointer, n_blocks == 0, n_ranges == 0, a bad align, frame_at[0] < 16, a frame
+ *   shorter than 6 bytes or a block longer than TSQ_BLOCK_SZ.
+ *
+ * tsqa_cut_async: idx is an index of ONE item (tsqa_index_items(idx) == 1): tsqa_index_create, tsqa_index_create_sized*, or a batch
+ * index of a single item.  d_first and d_count (n_ranges each) are tables in device memory; nothing is uploaded, nothing in them is
+ * trusted, and ranges may overlap and repeat.  Per range k, on the device, all arithmetic in 64 bits:
+ *   1. Gate: where the index carries a verdict (a sized index) and it is nonzero, every range gets TSQA_ERR_FORMAT, sizes, totals
+ *      and offsets are all 0 and not one byte of d_out is written.
+ *   2. Range: count >= 1, first < n_blocks and count <= n_blocks - first (first + count is never formed), else TSQA_ERR_ARG for
+ *      that range: size 0, total 0, no room taken, nothing of it read.
+ *   3. Size: d_sizes[k] = 16 + end(first + count - 1) - frame(first); d_totals[k] (may be NULL) = the uncompressed bytes of the
+ *      range's blocks.
+ *   4. Layout: d_offsets (n_ranges + 1) = tsqa_plan_packed's rule applied to d_sizes with align, complete and correct for every
+ *      range whatever fits.  Padding is never written.
+ *   5. Fit: a container is written only if it ends at or before out_size, and nothing at or past d_out + out_size is written.  An
+ *      accepted range that does not fit gets TSQA_ERR_OVERFLOW, its size, total and place still correct; a retry with
+ *      d_offsets[n_ranges] bytes of room succeeds.  The written ranges are a prefix of the accepted ones.
+ *   6. Status: d_item_status[k] == 0 means container k is complete and exact, whatever the other ranges are; *d_status = the
+ *      largest item status.
+ *   7. Measure only: d_out == NULL with out_size == 0: the tables are made, every accepted range reads TSQA_ERR_OVERFLOW.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL index, table or status pointer (d_totals and, when
+ * measuring, d_out may be NULL), n_ranges == 0, a bad align, an index of several items (they already are separate containers), a
+ * NULL d_out with out_size != 0, a non-NULL d_out with out_size < 16, [d_out, d_out + out_size) overlapping the index's container,
+ * n_ranges * (container bytes + 4096) >= 2^55.
+ * The call must be ordered behind the index's creation, as reads are (a sized index: the same stream).  What it keeps per range
+ * lives in the context's scratch; it returns at once and may be enqueued again on the same stream before the first has run (a
+ * call with more ranges than any before it first waits for the device, then grows the scratch).
+ * tsqa_cut: the same with host tables (offsets n_ranges + 1, sizes, totals -- may be NULL --, item_status), filled after one
+ *   wait.  Returns the status.
+ */
+int tsqa_plan_cut(const uint64_t *frame_at, const uint64_t *out_start, uint32_t n_blocks, const uint64_t *first, const uint64_t *count,
+                  uint32_t n_ranges, uint32_t align, uint64_t out_size, uint64_t *offsets, uint64_t *sizes, uint64_t *totals,
+                  int32_t *item_status, uint32_t *n_fit);
+int tsqa_cut_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint64_t *d_first, const uint64_t *d_count, uint32_t n_ranges,
+                   uint32_t align, void *d_out, size_t out_size, uint64_t *d_offsets, uint64_t *d_sizes, uint64_t *d_totals,
+                   int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+int tsqa_cut(tsqa_ctx *ctx, const tsqa_index *idx, const uint64_t *d_first, const uint64_t *d_count, uint32_t n_ranges,
+             uint32_t align, void *d_out, size_t out_size, uint64_t *offsets, uint64_t *sizes, uint64_t *totals,
+             int32_t *item_status, void *hip_stream);
 
 /*
  * Short blocks: ONE container whose blocks are block_len bytes long instead of TSQ_BLOCK_SZ.  A job's speed follows its block

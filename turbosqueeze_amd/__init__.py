@@ -26,6 +26,7 @@ from .api import (  # noqa: F401
     lib_path,
     plan_batch,
     plan_compress_tables,
+    plan_cut,
     plan_dense,
     plan_item_ranges,
     plan_join,

@@ -211,6 +211,14 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_join_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.tsqa_join.restype = C.c_int
     L.tsqa_join.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, szp, u32p, vp, vp, vp, vp]
+    L.tsqa_profile_read_cut.restype = C.c_int
+    L.tsqa_profile_read_cut.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_plan_cut.restype = C.c_int
+    L.tsqa_plan_cut.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, u32p]
+    L.tsqa_cut_async.restype = C.c_int
+    L.tsqa_cut_async.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.tsqa_cut.restype = C.c_int
+    L.tsqa_cut.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -358,6 +366,45 @@ class RangeIndex:
         self.read_into(triples, out, sync=False)
         return out[:sum(int(ln) for _, ln in ranges)], views
 
+    def cut(self, ranges, align: int = 16, out=None) -> "PackedBatch":
+        """The block ranges `ranges` -- a list of (first, count), or a pair of int64 CUDA tensors (d_first, d_count) -- each as a
+        .tsq container of its own, packed in one arena at multiples of `align` (DeviceCodec.cut_async: the frames are copied, nothing
+        is decoded).  Without `out` the cut is measured first and an arena of exactly the bytes needed is made.  -> a PackedBatch
+        whose lengths are the ranges' uncompressed sizes: decompress(), index() and join() take it.  A nonzero status raises
+        TsqError with the item statuses in the text and in .item_status; for an `out` that is too small (6) .needed = the bytes a
+        retry needs."""
+        codec, torch = self.codec, self.codec.torch
+        if isinstance(ranges, (tuple, list)) and len(ranges) == 2 and all(hasattr(t, "data_ptr") for t in ranges):
+            d_first, d_count = ranges
+        else:
+            import numpy as np
+            table = np.array([[int(f) for f, _ in ranges], [int(n) for _, n in ranges]], dtype=np.uint64).view(np.int64)
+            d_first, d_count = torch.from_numpy(table).to(codec.device)
+        n = int(d_first.numel())
+        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
+        d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
+
+        def call(room):
+            codec._join()
+            codec.cut_async(self, d_first, d_count, n, align, room, d_offsets, d_sizes, d_totals, d_status)
+            codec._join()
+            status, item_status = codec.status(), d_status.cpu().tolist()
+            needed = int(d_offsets[n].item())
+            refused = [st for st in item_status if st not in (0, 6)]
+            if status and (room is not None or refused):     # (measuring: every accepted range reads 6)
+                e = TsqError(max(refused) if refused else status, f"cut: item statuses {item_status[:64]}{' ...' if n > 64 else ''}")
+                e.item_status, e.needed = item_status, needed
+                raise e
+            return needed
+
+        if out is None:
+            out = torch.empty(max(call(None), 16), dtype=torch.uint8, device=codec.device)
+        used = call(out)
+        host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
+        return PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:])
+
 
 class SizedIndex(RangeIndex):
     """The index of a container of short blocks, made on the device from its table of stream sizes (tsqa_index_create_sized*): the
@@ -503,6 +550,28 @@ def plan_join(frame_bytes, blocks, totals):
     return [int(x) for x in body_at], [int(x) for x in first], int(n_blocks.value), int(total.value), int(size.value)
 
 
+def plan_cut(frame_at, out_start, ranges, align: int = 16, out_size: int = 0):
+    """tsqa_plan_cut (host only): the cut of the block ranges (first, count) out of a container with these n_blocks + 1 frame
+    boundaries (tsqa_walk_frames' frame_at with the end of the last frame appended) and block starts (out_start, as plan_ranges takes
+    it) -> (offsets, then the bytes needed; sizes; totals; item_status: 0, 3 for a range outside the container, 6 for an accepted
+    range that does not fit out_size; n_fit).  Raises TsqError(3) when refused."""
+    import numpy as np
+    fa = np.ascontiguousarray(frame_at, dtype=np.uint64)
+    os_ = np.ascontiguousarray(out_start, dtype=np.uint64)
+    first = np.array([int(f) for f, _ in ranges], dtype=np.uint64)
+    count = np.array([int(n) for _, n in ranges], dtype=np.uint64)
+    n = len(first)
+    offsets, sizes, totals = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    status, n_fit = np.zeros(max(n, 1), dtype=np.int32), C.c_uint32(0)
+    if len(fa) != len(os_) or len(fa) < 1:
+        raise TsqError(3, "tsqa_plan_cut takes n_blocks + 1 frame boundaries and as many block starts")
+    rc = lib().tsqa_plan_cut(fa.ctypes.data, os_.ctypes.data, len(fa) - 1, first.ctypes.data, count.ctypes.data, n, align, out_size,
+                             offsets.ctypes.data, sizes.ctypes.data, totals.ctypes.data, status.ctypes.data, C.byref(n_fit))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_cut refused the arguments")
+    return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -576,6 +645,10 @@ class BatchIndex(RangeIndex):
         self.total = int(self.L.tsqa_index_total(self.h))
         self.items = int(self.L.tsqa_index_items(self.h))
         self.worst_status = rc
+
+    @property
+    def cut(self):
+        raise AttributeError("a BatchIndex has no cut: its items already are separate containers")
 
     def item_total(self, i: int) -> int:
         return int(self.L.tsqa_index_item_total(self.h, i))
@@ -757,6 +830,12 @@ class DeviceCodec:
         """-> (emit_ms_sum, launches): the copy kernel of join_async alone since the last read."""
         ms, n = C.c_double(0), C.c_uint32(0)
         self.L.tsqa_profile_read_join(self.h, C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+    def profile_read_cut(self):
+        """-> (emit_ms_sum, launches): the copy kernel of cut_async alone since the last read."""
+        ms, n = C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_cut(self.h, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
@@ -1165,6 +1244,20 @@ class DeviceCodec:
                                     out.data_ptr() if out is not None else None, out.numel() if out is not None else 0, self._size.data_ptr(),
                                     d_first_block.data_ptr(), d_block_sizes.data_ptr() if d_block_sizes is not None else None,
                                     d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def cut_async(self, index, d_first, d_count, n: int, align: int, out, d_offsets, d_sizes, d_totals, d_item_status) -> None:
+        """tsqa_cut_async on the current stream, nothing waited for and nothing about the ranges taken from the host: the blocks
+        [d_first[k], d_first[k] + d_count[k]) of the container behind `index` (a RangeIndex or SizedIndex made before, on this stream
+        where it was made without a wait) become container k of a packed arena in out: out[d_offsets[k]:][:d_sizes[k]], decoding
+        to d_totals[k] bytes (int64 CUDA tensors of n + 1, n and n entries; d_totals may be None; d_item_status: int32, n).  A range
+        outside the index gets TSQA_ERR_ARG (3), one that does not fit out TSQA_ERR_OVERFLOW (6), and d_offsets[n] is the room a
+        retry needs.  out None: measure only.  The largest item status lands in status()."""
+        rc = self.L.tsqa_cut_async(self.h, index.h, d_first.data_ptr(), d_count.data_ptr(), int(n), int(align),
+                                   out.data_ptr() if out is not None else None, out.numel() if out is not None else 0,
+                                   d_offsets.data_ptr(), d_sizes.data_ptr(), d_totals.data_ptr() if d_totals is not None else None,
+                                   d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 

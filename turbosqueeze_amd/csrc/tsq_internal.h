@@ -9,7 +9,7 @@
 
 #include "../../include/turbosqueeze_amd.h"
 
-namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; }
+namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; struct CutRange; }
 
 struct tsqa_ctx;
 
@@ -123,6 +123,8 @@ struct tsqa_ctx {
     tsqa_scratch<uint32_t> table_launch_item;
     // tsqa_join_async: where each item's body starts in the joined container (one more than items)
     tsqa_scratch<uint64_t> join_at;
+    // tsqa_cut_async: per range its source place and its header's fields (one more than ranges: where the written output ends)
+    tsqa_scratch<tsq::CutRange> cut_ranges;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     tsqa_scratch<uint32_t> duo_flags;          // and their progress counters
@@ -133,11 +135,12 @@ struct tsqa_ctx {
     char err[256] = {0};
     // optional timing (tsqa_profile_*): HIP event pairs on the launch stream, taken from a pool made when profiling is
     // switched on (nothing is created or destroyed between the events).  Kinds: 0 encode kernel, 1 decode kernel,
-    // 2 whole compress call (encode + container pack), 3 whole decompress call (frame walk + decode), 4 the join's copy kernel.
-    static constexpr int kProfKinds = 5, kProfPairs = 256;
+    // 2 whole compress call (encode + container pack), 3 whole decompress call (frame walk + decode), 4 the join's copy kernel,
+    // 5 the cut's copy kernel.
+    static constexpr int kProfKinds = 6, kProfPairs = 256;
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
-    uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0};
+    uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0, 0};
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     // what a growing reserve waits for before it frees scratch: the context's own stream and `s`, the stream the call was given
@@ -148,6 +151,7 @@ struct tsqa_ctx {
     int reserve_batch(size_t n_items);
     int reserve_tables(size_t n_blocks, size_t n_launches);
     int reserve_join(size_t n_items);
+    int reserve_cut(size_t n_ranges);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]

@@ -108,6 +108,18 @@ __device__ __forceinline__ uint32_t join_item_of(const uint64_t* __restrict__ bo
 // four items -- or cut by the header or the container's end goes byte by byte.  No 16-byte load runs past its body's end, and no
 // byte outside an item's frames is read.  Bytes 0 .. 15 are join_bodies_kernel's.
 constexpr uint32_t kJoinPiece = 16384;                       // 256 lanes x 4 words
+
+// A lane's share of a piece whose every word is whole and of one body (also cut_emit_kernel's, tsq_cut.cuh): its four words lie
+// 4096 bytes apart from dst on, which is a multiple of 16; four unaligned loads in flight, then four aligned stores.
+__device__ __forceinline__ void join_copy_piece(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
+{
+    uint4 a, b, c, d;
+    __builtin_memcpy(&a, src, 16); __builtin_memcpy(&b, src + 4096, 16);
+    __builtin_memcpy(&c, src + 8192, 16); __builtin_memcpy(&d, src + 12288, 16);
+    *reinterpret_cast<uint4*>(dst) = a; *reinterpret_cast<uint4*>(dst + 4096) = b;
+    *reinterpret_cast<uint4*>(dst + 8192) = c; *reinterpret_cast<uint4*>(dst + 12288) = d;
+}
+
 __global__ __launch_bounds__(256) void join_emit_kernel(const uint8_t* __restrict__ in, const BatchItem* __restrict__ items, uint32_t n_items,
                                                         const uint64_t* __restrict__ body_at, uint8_t* __restrict__ out,
                                                         const uint64_t* __restrict__ out_size, const int32_t* __restrict__ status)
@@ -125,13 +137,7 @@ __global__ __launch_bounds__(256) void join_emit_kernel(const uint8_t* __restric
             const uint64_t delta = items[j0].in_at + kHeaderSize - body_at[j0] - skew;
             const uint64_t v0 = p0 + ((uint64_t)threadIdx.x << 4);                            // this lane's words: v0 + u * 4096
             if (lo == p0 && hi == p1) {                      // every word of the piece is whole: four loads in flight, then four stores
-                const uint8_t* const src = in + (delta + v0);
-                uint8_t* const dst = out + (v0 - skew);
-                uint4 a, b, c, d;
-                __builtin_memcpy(&a, src, 16); __builtin_memcpy(&b, src + 4096, 16);
-                __builtin_memcpy(&c, src + 8192, 16); __builtin_memcpy(&d, src + 12288, 16);
-                *reinterpret_cast<uint4*>(dst) = a; *reinterpret_cast<uint4*>(dst + 4096) = b;
-                *reinterpret_cast<uint4*>(dst + 8192) = c; *reinterpret_cast<uint4*>(dst + 12288) = d;
+                join_copy_piece(in + (delta + v0), out + (v0 - skew));
                 continue;
             }
             for (uint32_t u = 0; u < 4u; ++u) {              // the first and the last piece of the container: cut by the header or the end

@@ -15,6 +15,7 @@
 #include "tsq_split.cuh"
 #include "tsq_index.cuh"
 #include "tsq_join.cuh"
+#include "tsq_cut.cuh"
 #include "tsq_launch.cuh"
 
 #include <algorithm>
@@ -260,6 +261,16 @@ int tsqa_ctx::reserve_join(size_t n_items)
     return join_at.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the cut (tsq_internal.h): one entry per range and one more, doubled from 256 ranges as the join's grows.
+int tsqa_ctx::reserve_cut(size_t n_ranges)
+{
+    (void)hipSetDevice(device);
+    const size_t want = doubled(256, n_ranges) + 1;
+    if (!cut_ranges.needs(want)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return cut_ranges.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -339,6 +350,15 @@ extern "C" int tsqa_profile_read_join(tsqa_ctx* c, double* emit_ms, uint32_t* em
     (void)hipSetDevice(c->device);
     if (c->prof_pool.empty()) { if (emit_ms) *emit_ms = 0; if (emit_n) *emit_n = 0; return TSQA_OK; }
     drain_events(c, 4, emit_ms, emit_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_cut(tsqa_ctx* c, double* emit_ms, uint32_t* emit_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (emit_ms) *emit_ms = 0; if (emit_n) *emit_n = 0; return TSQA_OK; }
+    drain_events(c, 5, emit_ms, emit_n);
     return TSQA_OK;
 }
 
@@ -1740,6 +1760,97 @@ extern "C" int tsqa_join(tsqa_ctx* c, const void* d_arena, size_t arena_size, co
     const int rc = finish_sync(c, s, "join", out_size);
     if (rc == TSQA_OK || rc == TSQA_ERR_FORMAT || rc == TSQA_ERR_OVERFLOW) *n_blocks = blocks > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)blocks;
     return rc;
+}
+
+// ---- cut: block ranges of an indexed container, each as a container of its own, nothing decoded (tsq_cut.cuh) ----
+
+extern "C" int tsqa_plan_cut(const uint64_t* frame_at, const uint64_t* out_start, uint32_t n_blocks, const uint64_t* first, const uint64_t* count,
+                             uint32_t n_ranges, uint32_t align, uint64_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals,
+                             int32_t* item_status, uint32_t* n_fit)
+{
+    if (!frame_at || !out_start || !first || !count || !offsets || !sizes || !item_status || !n_fit || n_blocks == 0 || n_ranges == 0 ||
+        !packed_align_ok(align)) return TSQA_ERR_ARG;
+    if (frame_at[0] < kHeaderSize) return TSQA_ERR_ARG;
+    for (uint32_t b = 0; b < n_blocks; ++b)
+        if (frame_at[b + 1] < frame_at[b] || frame_at[b + 1] - frame_at[b] < kMinFrameSize || out_start[b + 1] < out_start[b] ||
+            out_start[b + 1] - out_start[b] > kBlockSize) return TSQA_ERR_ARG;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t at = 0;
+    uint32_t fit = n_ranges;
+    for (uint32_t k = 0; k < n_ranges; ++k) {
+        const uint64_t f = first[k], n = count[k];
+        const bool ok = n >= 1 && f < n_blocks && n <= n_blocks - f;
+        const uint64_t size = ok ? kHeaderSize + frame_at[f + n] - frame_at[f] : 0;
+        offsets[k] = at; sizes[k] = size;
+        if (totals) totals[k] = ok ? out_start[f + n] - out_start[f] : 0;
+        const bool fits = ok && size <= out_size && at <= out_size - size;
+        if (ok && !fits && fit == n_ranges) fit = k;
+        item_status[k] = !ok ? TSQA_ERR_ARG : fits ? TSQA_OK : TSQA_ERR_OVERFLOW;
+        at += size;
+        if (k + 1 < n_ranges) at = (at + mask) & ~mask;
+    }
+    offsets[n_ranges] = at;
+    *n_fit = fit;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_cut_async(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges,
+                              uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes, uint64_t* d_totals,
+                              int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_first || !d_count || !d_offsets || !d_sizes || !d_item_status || !d_status) { c->set_error("cut: null pointer"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("cut: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (n_ranges == 0) { c->set_error("cut: no ranges"); return TSQA_ERR_ARG; }
+    if (!packed_align_ok(align)) { c->set_error("cut: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
+    if (idx->item_status.size() != 1) { c->set_error("cut: an index of %zu items; its items already are separate containers", idx->item_status.size()); return TSQA_ERR_ARG; }
+    if (d_out ? out_size < kHeaderSize : out_size != 0) {
+        c->set_error("cut: an output needs out_size of at least 16; measuring takes d_out NULL and out_size 0");
+        return TSQA_ERR_ARG;
+    }
+    {
+        const uintptr_t a = (uintptr_t)idx->container, o = (uintptr_t)d_out;
+        if (d_out && o < a + idx->n && a < o + out_size) { c->set_error("cut: the output overlaps the index's container"); return TSQA_ERR_ARG; }
+    }
+    // (the sizes go through group_scan_excl64, whose sums stay below 2^55; one source byte may be counted once per range)
+    if ((unsigned __int128)n_ranges * ((unsigned __int128)idx->n + 4096u) >= (unsigned __int128)1 << 55) { c->set_error("cut: %u ranges of a container of %zu B", n_ranges, idx->n); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_cut(n_ranges)) return rc;
+    CutRange* const ranges = c->cut_ranges;
+    hipLaunchKernelGGL(cut_measure_kernel, dim3((uint32_t)(((uint64_t)n_ranges + 255u) / 256u)), dim3(256), 0, s,
+                       static_cast<const FrameInfo*>(idx->frames), idx->n_blocks, static_cast<const int32_t*>(idx->verdict), d_first, d_count,
+                       n_ranges, ranges, d_sizes, d_totals, d_item_status);
+    hipLaunchKernelGGL(cut_layout_kernel, dim3(1), dim3(256), 0, s, ranges, n_ranges, align, static_cast<uint8_t*>(d_out), (uint64_t)out_size,
+                       static_cast<const uint64_t*>(d_sizes), d_offsets, d_item_status, d_status);
+    if (d_out) {
+        ProfSpan span(c, 5, s);
+        hipLaunchKernelGGL(cut_emit_kernel, dim3(join_emit_groups(c, out_size)), dim3(256), 0, s, idx->container,
+                           static_cast<const CutRange*>(ranges), n_ranges, static_cast<const uint64_t*>(d_offsets),
+                           static_cast<const uint64_t*>(d_sizes), static_cast<uint8_t*>(d_out));
+        span.end();
+    }
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_cut(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges, uint32_t align,
+                        void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals, int32_t* item_status,
+                        void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!offsets || !sizes || !item_status) { c->set_error("cut: null pointer"); return TSQA_ERR_ARG; }
+    if (n_ranges == 0) { c->set_error("cut: no ranges"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_batch(n_ranges)) return rc;      // (the device tables of the waiting form are the batch calls')
+    if (int rc = tsqa_cut_async(c, idx, d_first, d_count, n_ranges, align, d_out, out_size, c->batch_offsets, c->batch_sizes, c->batch_at,
+                                c->batch_status, c->d_status, s)) return rc;
+    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_ranges + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (totals) TSQ_HIP(c, hipMemcpyAsync(totals, c->batch_at, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(item_status, c->batch_status, (size_t)n_ranges * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return finish_sync(c, s, "cut");
 }
 
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
