@@ -186,6 +186,9 @@ int tsqa_profile_read_calls(tsqa_ctx *ctx, double *compress_ms, uint32_t *compre
 int tsqa_profile_read_join(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launches);
 /* The same for the copy kernel of tsqa_cut_async alone. */
 int tsqa_profile_read_cut(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launches);
+/* The same for record reads: the planner of tsqa_gather_async (its launches in front of the decode, as one span per call) and
+ * the decode kernel of a record read (tsqa_decompress_item_ranges_async and tsqa_gather_async). */
+int tsqa_profile_read_gather(tsqa_ctx *ctx, double *plan_ms, uint32_t *plan_calls, double *decode_ms, uint32_t *decode_launches);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -735,6 +738,55 @@ int tsqa_decompress_item_ranges_async(tsqa_ctx *ctx, const tsqa_index *idx, cons
                                       void *d_out, size_t out_cap, int32_t *d_status, void *hip_stream);
 int tsqa_decompress_item_ranges(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa_item_range *ranges, uint32_t n_ranges,
                                 void *d_out, size_t out_cap, void *hip_stream);
+
+/*
+ * Gather: record reads whose ranges lie in DEVICE memory -- sampler indices, a filter's result, offsets a kernel has just
+ * computed.  Nothing is uploaded, read back or waited for: the plan that the host makes for tsqa_decompress_item_ranges* is made
+ * on the device, and the output is dense, each range's place a prefix sum, so no two destinations can overlap.  Any index:
+ * tsqa_index_create, tsqa_index_create_batch, tsqa_index_create_sized*.
+ *
+ * Range k is bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) -- of the index's whole data when d_items is NULL (a batch index:
+ * the concatenation, as tsqa_decompress_ranges* reads it), else of item d_items[k]'s own data.  Its bytes land at
+ * d_out + d_out_offsets[k].  Nothing in the tables is trusted; per range, in this order:
+ *   1. Gate: where the index carries a verdict (a sized index) and it is nonzero, every range gets TSQA_ERR_FORMAT and no
+ *      descriptor is read.
+ *   2. Range: the item number below tsqa_index_items, the item not refused, length <= its total and offset <= total - length
+ *      (offset + length is never formed), else TSQA_ERR_ARG.  A refused range takes no room and has no pieces.
+ *   3. Layout: d_out_offsets (n_ranges + 1) = tsqa_plan_packed's rule applied to the accepted ranges' lengths with align (a power
+ *      of two, 1 to 4096): every place is a multiple of align and the last length is not rounded; a refused or zero-length range
+ *      takes no room.  Complete whatever fits; d_out_offsets[n_ranges] is the room a retry needs.
+ *   4. Fit: a range is cut into one piece per block it touches.  An accepted range fits when its bytes end at or before out_cap
+ *      and its pieces, numbered on from the accepted ranges before it, at or before cap_pieces (a zero-length range asks for
+ *      neither).  Both only grow: the fitting ranges are a prefix of the accepted ones, the first unfit range ends it, and every
+ *      accepted range behind gets TSQA_ERR_OVERFLOW.  *d_need_pieces = the pieces of all accepted ranges.
+ *   5. Decode: one workgroup per touched block, as tsqa_decompress_item_ranges_async; the launch has min(cap_pieces, blocks)
+ *      workgroups, and those past the touched blocks leave at once.  The scratch, in the context, follows cap_pieces too.
+ * *d_status = the largest range status, raised to TSQA_ERR_STREAM when a decoder met a malformed stream (while it is
+ * TSQA_ERR_OVERFLOW it stays that).  Trust as for record reads: when *d_status is TSQA_ERR_STREAM the destinations' contents are
+ * undefined.  In every case nothing is written outside the fitting ranges' destinations; padding between them is nobody's.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL pointer other than d_items, a bad align,
+ * cap_pieces == 0, an index of another device, or n_ranges * (tsqa_index_total + 4096) >= 2^55 or n_ranges * tsqa_index_blocks
+ * >= 2^55 (what lets a sum of the layout wrap).  n_ranges == 0 clears *d_status, *d_need_pieces and d_out_offsets[0].  d_items with
+ * an index of one item is allowed: only item 0 exists.  Calls that share a context share its scratch: order them on one stream.
+ *
+ * tsqa_gather: the same, then waits for hip_stream and returns *d_status.
+ *
+ * tsqa_plan_gather: host only, the same rule on host tables (out_start and item_first_block as tsqa_plan_item_ranges takes them;
+ *   items may be NULL): out_offsets[n_ranges + 1], range_status[n_ranges], *n_pieces = what *d_need_pieces reads, *n_groups = the
+ *   blocks the fitting ranges touch.  With out_cap = UINT64_MAX and cap_pieces = UINT32_MAX it sizes a call.  Returns TSQA_OK
+ *   whatever the ranges' statuses; TSQA_ERR_ARG for a NULL pointer other than items, n_items == 0, a bad align, cap_pieces == 0,
+ *   tables that do not run from 0 upwards, a block longer than TSQ_BLOCK_SZ, or the size limits above.
+ */
+int tsqa_plan_gather(const uint64_t *out_start, uint32_t n_blocks, const uint64_t *item_first_block, uint32_t n_items,
+                     const uint32_t *items, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_ranges,
+                     uint32_t align, uint64_t out_cap, uint32_t cap_pieces,
+                     uint64_t *out_offsets, int32_t *range_status, uint64_t *n_pieces, uint32_t *n_groups);
+int tsqa_gather_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
+                      const uint64_t *d_lengths, uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void *d_out, size_t out_cap,
+                      uint64_t *d_out_offsets, int32_t *d_range_status, uint64_t *d_need_pieces, int32_t *d_status, void *hip_stream);
+int tsqa_gather(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
+                const uint64_t *d_lengths, uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void *d_out, size_t out_cap,
+                uint64_t *d_out_offsets, int32_t *d_range_status, uint64_t *d_need_pieces, int32_t *d_status, void *hip_stream);
 
 /* =====================================================================================
  * (1) The reference API (turbosqueeze.h:441-674), C-callable subset

@@ -27,6 +27,7 @@ from .api import (  # noqa: F401
     plan_batch,
     plan_compress_tables,
     plan_cut,
+    plan_gather,
     plan_dense,
     plan_item_ranges,
     plan_join,

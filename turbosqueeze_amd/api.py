@@ -219,6 +219,14 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_cut_async.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.tsqa_cut.restype = C.c_int
     L.tsqa_cut.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.tsqa_profile_read_gather.restype = C.c_int
+    L.tsqa_profile_read_gather.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_plan_gather.restype = C.c_int
+    L.tsqa_plan_gather.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, u64p, u32p]
+    L.tsqa_gather_async.restype = C.c_int
+    L.tsqa_gather_async.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.tsqa_gather.restype = C.c_int
+    L.tsqa_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -405,6 +413,50 @@ class RangeIndex:
         host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
         return PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:])
 
+    def _gather(self, d_items, d_offsets, d_lengths, align, out, cap_pieces, range_status):
+        codec, torch = self.codec, self.codec.torch
+        n = int(d_offsets.numel())
+        for name, t, dtypes in (("d_offsets", d_offsets, (torch.int64,)), ("d_lengths", d_lengths, (torch.int64,)),
+                                ("d_items", d_items, (torch.int32, getattr(torch, "uint32", torch.int32)))):
+            if t is not None and (t.dtype not in dtypes or t.device != codec.device or not t.is_contiguous() or t.numel() != n):
+                raise TsqError(3, f"{name} must be a contiguous {str(dtypes[0])[6:]} tensor of {n} entries on the codec's device")
+        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        d_out_offsets = torch.empty(n + 1, dtype=torch.int64, device=codec.device)
+        d_status = torch.empty(max(n, 1), dtype=torch.int32, device=codec.device)
+        d_need = torch.empty(1, dtype=torch.int64, device=codec.device)
+        if n == 0:                                           # (an empty tensor has no address to give: the call reads no table entry)
+            d_offsets = d_lengths = d_need
+            d_items = None
+        if out is None or cap_pieces is None:
+            # the two sums, measured: a call with no room refuses every range with bytes and still makes the whole layout
+            codec._join()
+            codec.gather_async(self, d_items, d_offsets, d_lengths, n, align, 1, torch.empty(1, dtype=torch.uint8, device=codec.device),
+                               d_out_offsets, d_status, d_need, out_cap=0)
+            codec._join()
+            room, need = (int(x) for x in torch.stack([d_out_offsets[n], d_need[0]]).cpu().tolist())
+            if out is None:
+                out = torch.empty(max(room, 1), dtype=torch.uint8, device=codec.device)[:room]
+            if cap_pieces is None:
+                cap_pieces = max(min(need, 0xFFFFFFFF), 1)
+        codec._join()
+        codec.gather_async(self, d_items, d_offsets, d_lengths, n, align, cap_pieces, out if out.numel() else torch.empty(1, dtype=torch.uint8, device=codec.device),
+                           d_out_offsets, d_status, d_need, out_cap=out.numel())
+        codec._join()
+        return (out, d_out_offsets, d_status[:n]) if range_status else (out, d_out_offsets)
+
+    def gather(self, d_offsets, d_lengths, align: int = 1, out=None, cap_pieces=None, range_status: bool = False):
+        """Bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) of the uncompressed data for int64 CUDA tensors of offsets and lengths,
+        planned on the device (DeviceCodec.gather_async): nothing about the ranges is read on the host.  -> (out, d_out_offsets):
+        range k lies at out[d_out_offsets[k]:][:d_lengths[k]], d_out_offsets[n] is the room the ranges need; with range_status=True
+        also the int32 verdict per range (0; 3 refused; 6 does not fit out or cap_pieces).  The largest verdict lands in
+        codec.status().  On a stream of the caller's (torch.cuda.stream) the call is enqueued there and, with both `out` and
+        `cap_pieces` given, nothing is waited for.  On torch's default stream the library runs on the context's own stream, which
+        torch's work does not order itself against: there the wrapper waits for the device before and after the call.  Without
+        `out` or `cap_pieces` the call is first run with no room, and the host WAITS ONCE for its two sums -- the bytes and the
+        pieces needed -- because no bound on them is known to the host while the lengths are the device's."""
+        return self._gather(None, d_offsets, d_lengths, align, out, cap_pieces, range_status)
+
 
 class SizedIndex(RangeIndex):
     """The index of a container of short blocks, made on the device from its table of stream sizes (tsqa_index_create_sized*): the
@@ -572,6 +624,31 @@ def plan_cut(frame_at, out_start, ranges, align: int = 16, out_size: int = 0):
     return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
 
 
+def plan_gather(out_start, item_first_block, items, offsets, lengths, align: int = 1, out_cap=None, cap_pieces=None):
+    """tsqa_plan_gather (host only): the layout and the verdicts of a gather of the ranges [offsets[k], offsets[k] + lengths[k]) --
+    of item items[k]'s data, or of the whole data when items is None -- out of an index with these block starts (out_start, as
+    plan_ranges takes it) and first blocks per item (item_first_block, as plan_item_ranges takes it; [0, n_blocks] for one
+    container).  out_cap / cap_pieces None: no limit, which sizes a call.  -> (out_offsets, then the bytes needed; range_status: 0,
+    3 for a refused range, 6 for an accepted one that does not fit; the pieces the accepted ranges need; the blocks the fitting
+    ranges touch).  Raises TsqError(3) when the arguments are refused."""
+    import numpy as np
+    u64 = lambda v: np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in v], dtype=np.uint64))
+    starts, first, off, ln = u64(out_start), u64(item_first_block), u64(offsets), u64(lengths)
+    it = None if items is None else np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFF for x in items], dtype=np.uint32))
+    n = len(off)
+    if len(ln) != n or (it is not None and len(it) != n) or len(starts) < 1 or len(first) < 2:
+        raise TsqError(3, "tsqa_plan_gather takes as many lengths (and items) as offsets, n_blocks + 1 block starts and n_items + 1 first blocks")
+    out_offsets, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32)
+    pieces, groups = C.c_uint64(0), C.c_uint32(0)
+    rc = lib().tsqa_plan_gather(starts.ctypes.data, len(starts) - 1, first.ctypes.data, len(first) - 1, None if it is None else it.ctypes.data,
+                                off.ctypes.data, ln.ctypes.data, n, align, 0xFFFFFFFFFFFFFFFF if out_cap is None else int(out_cap),
+                                0xFFFFFFFF if cap_pieces is None else int(cap_pieces), out_offsets.ctypes.data, status.ctypes.data,
+                                C.byref(pieces), C.byref(groups))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_gather refused the arguments")
+    return [int(x) for x in out_offsets], [int(x) for x in status[:n]], int(pieces.value), int(groups.value)
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -655,6 +732,11 @@ class BatchIndex(RangeIndex):
 
     def item_status(self, i: int) -> int:
         return int(self.L.tsqa_index_item_status(self.h, i))
+
+    def gather(self, d_items, d_offsets, d_lengths, align: int = 1, out=None, cap_pieces=None, range_status: bool = False):
+        """RangeIndex.gather addressed by item: range k is bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) of item d_items[k]'s
+        own data (d_items: an int32 CUDA tensor, read as unsigned; None: offsets into the concatenation of the healthy items)."""
+        return self._gather(d_items, d_offsets, d_lengths, align, out, cap_pieces, range_status)
 
     def read_items_into(self, ranges, out, sync: bool = True) -> None:
         """The raw call: ranges = (item, offset, length, out_at), bytes land at out[out_at:].  sync=False: on the current stream,
@@ -837,6 +919,13 @@ class DeviceCodec:
         ms, n = C.c_double(0), C.c_uint32(0)
         self.L.tsqa_profile_read_cut(self.h, C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+    def profile_read_gather(self):
+        """-> (plan_ms_sum, calls, decode_ms_sum, launches): the planner of gather_async, and the decode kernel of the record reads
+        (gather_async and BatchIndex.read_items_into) since the last read."""
+        pm, pn, dm, dn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_gather(self.h, C.byref(pm), C.byref(pn), C.byref(dm), C.byref(dn))
+        return pm.value, pn.value, dm.value, dn.value
 
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
@@ -1258,6 +1347,23 @@ class DeviceCodec:
                                    out.data_ptr() if out is not None else None, out.numel() if out is not None else 0,
                                    d_offsets.data_ptr(), d_sizes.data_ptr(), d_totals.data_ptr() if d_totals is not None else None,
                                    d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def gather_async(self, index, d_items, d_offsets, d_lengths, n: int, align: int, cap_pieces: int, out, d_out_offsets, d_range_status,
+                     d_need_pieces, out_cap=None) -> None:
+        """tsqa_gather_async on the current stream, nothing waited for and nothing about the ranges taken from the host: bytes
+        [d_offsets[k], d_offsets[k] + d_lengths[k]) (int64 CUDA tensors) of the data behind `index` -- any index; of item d_items[k]
+        (an int32 CUDA tensor, read as unsigned) where d_items is given -- land at out[d_out_offsets[k]:], packed at multiples of
+        align (d_out_offsets: int64, n + 1; d_range_status: int32, n; d_need_pieces: int64, 1).  A range outside its data gets
+        TSQA_ERR_ARG (3); one that does not fit out, or whose pieces -- one per block it touches -- do not fit cap_pieces,
+        TSQA_ERR_OVERFLOW (6), and d_out_offsets[n] and d_need_pieces say what a retry needs.  The largest range status lands in
+        status().  out_cap: the bytes of out that may be written, all of it when None; 0 measures."""
+        rc = self.L.tsqa_gather_async(self.h, index.h, d_items.data_ptr() if d_items is not None else None, d_offsets.data_ptr(),
+                                      d_lengths.data_ptr(), int(n), int(align), int(cap_pieces), out.data_ptr(),
+                                      out.numel() if out_cap is None else min(int(out_cap), out.numel()),
+                                      d_out_offsets.data_ptr(), d_range_status.data_ptr(), d_need_pieces.data_ptr(), self._status.data_ptr(),
+                                      self._stream())
         if rc:
             raise self._err(rc)
 

@@ -9,7 +9,7 @@
 
 #include "../../include/turbosqueeze_amd.h"
 
-namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; struct CutRange; }
+namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; struct CutRange; struct GatherRange; struct GatherWords; struct RangeItem; struct BlockGroup; }
 
 struct tsqa_ctx;
 
@@ -125,6 +125,17 @@ struct tsqa_ctx {
     tsqa_scratch<uint64_t> join_at;
     // tsqa_cut_async: per range its source place and its header's fields (one more than ranges: where the written output ends)
     tsqa_scratch<tsq::CutRange> cut_ranges;
+    // tsqa_gather_async (tsq_gather.cuh): per range its place and piece count; per piece slot -- cap_pieces of them -- the item as
+    // it is cut and as it is sorted (two halves of gather_items), the key and the slot number in front of and behind the sort (two
+    // halves each); one group per block that can be touched; the sort's temporary storage, asked for gather_sort_n pairs; the words
+    tsqa_scratch<tsq::GatherRange> gather_ranges;
+    tsqa_scratch<tsq::RangeItem> gather_items;
+    tsqa_scratch<uint64_t> gather_keys;
+    tsqa_scratch<uint32_t> gather_slots;
+    tsqa_scratch<tsq::BlockGroup> gather_groups;
+    tsqa_scratch<uint8_t> gather_sort;
+    tsqa_scratch<tsq::GatherWords> gather_words;
+    size_t gather_sort_n = 0, gather_sort_bytes = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     tsqa_scratch<uint32_t> duo_flags;          // and their progress counters
@@ -136,11 +147,12 @@ struct tsqa_ctx {
     // optional timing (tsqa_profile_*): HIP event pairs on the launch stream, taken from a pool made when profiling is
     // switched on (nothing is created or destroyed between the events).  Kinds: 0 encode kernel, 1 decode kernel,
     // 2 whole compress call (encode + container pack), 3 whole decompress call (frame walk + decode), 4 the join's copy kernel,
-    // 5 the cut's copy kernel.
-    static constexpr int kProfKinds = 6, kProfPairs = 256;
+    // 5 the cut's copy kernel, 6 the gather's planner (its launches in front of the decode), 7 the decode kernel of a record read
+    // (tsqa_decompress_item_ranges_async and tsqa_gather_async).
+    static constexpr int kProfKinds = 8, kProfPairs = 256;
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
-    uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0, 0};
+    uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     // what a growing reserve waits for before it frees scratch: the context's own stream and `s`, the stream the call was given
@@ -152,6 +164,7 @@ struct tsqa_ctx {
     int reserve_tables(size_t n_blocks, size_t n_launches);
     int reserve_join(size_t n_items);
     int reserve_cut(size_t n_ranges);
+    int reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]
@@ -193,6 +206,10 @@ struct tsqa_index {
     // is why two creations on one stream do not share them, and the walk's verdict, which gates every read (NULL otherwise)
     uint64_t* group_sum = nullptr;
     int32_t* verdict = nullptr;
+    // tsqa_gather_async: log2 of a sized index's block_len (0 otherwise: the block of a byte is found by bisection), and, for a batch
+    // index, item_first on the device (n_items + 1; NULL for an index of one item, which owns every block)
+    uint32_t block_shift = 0;
+    uint64_t* d_item_first = nullptr;
     std::vector<tsqa_frame> host_frames;       // their host copy
     std::vector<uint64_t> out_start;           // n_blocks + 1: where each block's output starts, then the total
     // items (one for a single container): item i owns the blocks [item_first[i], item_first[i + 1]), none when it was refused

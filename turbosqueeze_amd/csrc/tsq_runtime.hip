@@ -17,6 +17,8 @@
 #include "tsq_join.cuh"
 #include "tsq_cut.cuh"
 #include "tsq_launch.cuh"
+#include "tsq_gather.cuh"
+#include "tsq_gather_sort.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -271,6 +273,26 @@ int tsqa_ctx::reserve_cut(size_t n_ranges)
     return cut_ranges.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the gather (tsq_internal.h): the ranges doubled from 256 as the cut's, the piece slots and groups as many as the call
+// names (cap_pieces is the caller's statement of what the call may hold, and the sort runs over exactly that many pairs), each
+// buffer on its own.  The sort's temporary storage is asked for here, once per cap_pieces, not per call.
+int tsqa_ctx::reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups)
+{
+    (void)hipSetDevice(device);
+    if (gather_sort_n != cap_pieces) {
+        size_t bytes = 0;
+        TSQ_HIP(this, gather_sort_storage(cap_pieces > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_pieces, &bytes));
+        gather_sort_n = cap_pieces; gather_sort_bytes = bytes ? bytes : 1;
+    }
+    const size_t want = doubled(256, n_ranges);
+    if (!gather_ranges.needs(want) && !gather_items.needs(2 * cap_pieces) && !gather_keys.needs(2 * cap_pieces) && !gather_slots.needs(2 * cap_pieces) &&
+        !gather_groups.needs(cap_groups) && !gather_sort.needs(gather_sort_bytes) && !gather_words.needs(1)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return gather_ranges.grow(this, want) && gather_items.grow(this, 2 * cap_pieces) && gather_keys.grow(this, 2 * cap_pieces) &&
+           gather_slots.grow(this, 2 * cap_pieces) && gather_groups.grow(this, cap_groups) && gather_sort.grow(this, gather_sort_bytes) &&
+           gather_words.grow(this, 1) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -359,6 +381,16 @@ extern "C" int tsqa_profile_read_cut(tsqa_ctx* c, double* emit_ms, uint32_t* emi
     (void)hipSetDevice(c->device);
     if (c->prof_pool.empty()) { if (emit_ms) *emit_ms = 0; if (emit_n) *emit_n = 0; return TSQA_OK; }
     drain_events(c, 5, emit_ms, emit_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_gather(tsqa_ctx* c, double* plan_ms, uint32_t* plan_n, double* dec_ms, uint32_t* dec_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (plan_ms) *plan_ms = 0; if (plan_n) *plan_n = 0; if (dec_ms) *dec_ms = 0; if (dec_n) *dec_n = 0; return TSQA_OK; }
+    drain_events(c, 6, plan_ms, plan_n);
+    drain_events(c, 7, dec_ms, dec_n);
     return TSQA_OK;
 }
 
@@ -834,6 +866,7 @@ extern "C" int tsqa_index_create_sized_async(tsqa_ctx* c, const void* d_containe
     if (!idx) return TSQA_ERR_ARG;
     for (uint32_t b = 0; b < nb; ++b) idx->out_start[b] = (uint64_t)b * block_len;
     idx->out_start[nb] = n_total;
+    idx->block_shift = (uint32_t)__builtin_ctz(block_len);
     // one allocation: the descriptors, the group sums, the verdict; all zero in front of the walk
     const uint32_t n_groups = (uint32_t)(((uint64_t)nb + kIndexGroup - 1u) / kIndexGroup);
     const size_t frames_bytes = (size_t)nb * sizeof(FrameInfo), bytes = frames_bytes + ((size_t)n_groups + 1u) * sizeof(uint64_t);
@@ -881,6 +914,7 @@ extern "C" void tsqa_index_destroy(tsqa_index* idx)
     if (!idx) return;
     (void)hipSetDevice(idx->device);
     (void)hipFree(idx->frames);
+    (void)hipFree(idx->d_item_first);
     delete idx;
 }
 
@@ -1093,8 +1127,10 @@ extern "C" int tsqa_decompress_item_ranges_async(tsqa_ctx* c, const tsqa_index* 
     std::copy(vi.begin(), vi.end(), up.host<tsqa_range_item>());
     std::copy(vg.begin(), vg.end(), up.host<tsqa_block_group>(groups_at));
     TSQ_HIP(c, up.send(bytes, s));
+    ProfSpan span(c, 7, s);
     const int rc = launch_read_kernel<dec_group_kernel>(c, n_groups, s, idx->container, idx->frames, idx->n_blocks, up.dev<RangeItem>(), n_items,
                                                         up.dev<BlockGroup>(groups_at), static_cast<uint8_t*>(d_out), d_status);
+    span.end();
     TSQ_HIP(c, up.commit(s));
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
@@ -1853,6 +1889,145 @@ extern "C" int tsqa_cut(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_fi
     return finish_sync(c, s, "cut");
 }
 
+// ---- gather: record reads whose ranges lie in device memory, planned there, into a dense output (tsq_gather.cuh) ----
+
+// What keeps every sum of the gather's scans below 2^55 (group_scan_excl64): a range is at most the index's total and is padded by
+// less than 4096, and it has at most one piece per block.
+static bool gather_sums_ok(uint32_t n_ranges, uint64_t total, uint32_t n_blocks)
+{
+    const unsigned __int128 limit = (unsigned __int128)1 << 55;
+    return (unsigned __int128)n_ranges * ((unsigned __int128)total + 4096u) < limit && (unsigned __int128)n_ranges * n_blocks < limit;
+}
+
+extern "C" int tsqa_plan_gather(const uint64_t* out_start, uint32_t n_blocks, const uint64_t* item_first_block, uint32_t n_items,
+                                const uint32_t* items, const uint64_t* offsets, const uint64_t* lengths, uint32_t n_ranges, uint32_t align,
+                                uint64_t out_cap, uint32_t cap_pieces, uint64_t* out_offsets, int32_t* range_status, uint64_t* n_pieces,
+                                uint32_t* n_groups)
+{
+    if (!out_start || !item_first_block || !offsets || !lengths || !out_offsets || !range_status || !n_pieces || !n_groups || n_items == 0 ||
+        !packed_align_ok(align) || cap_pieces < 1) return TSQA_ERR_ARG;
+    if (out_start[0] != 0 || item_first_block[0] != 0 || item_first_block[n_items] != n_blocks) return TSQA_ERR_ARG;
+    for (uint32_t b = 0; b < n_blocks; ++b)
+        if (out_start[b + 1] < out_start[b] || out_start[b + 1] - out_start[b] > kBlockSize) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_first_block[i + 1] < item_first_block[i]) return TSQA_ERR_ARG;
+    if (!gather_sums_ok(n_ranges, out_start[n_blocks], n_blocks)) return TSQA_ERR_ARG;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t at = 0, pieces_at = 0, last_len = 0;
+    bool open = true;                                        // no accepted range has failed to fit yet
+    std::vector<uint32_t> touched;
+    try {
+        for (uint32_t k = 0; k < n_ranges; ++k) {
+            uint64_t base = 0, mine = out_start[n_blocks];
+            bool ok = true;
+            if (items) {
+                ok = items[k] < n_items && item_first_block[items[k]] < item_first_block[items[k] + 1];
+                if (ok) { base = out_start[item_first_block[items[k]]]; mine = out_start[item_first_block[items[k] + 1]] - base; }
+            }
+            ok = ok && lengths[k] <= mine && offsets[k] <= mine - lengths[k];
+            const uint64_t len = ok ? lengths[k] : 0, a = base + offsets[k], e = a + len;
+            uint64_t first = 0, pieces = 0;
+            if (len) {
+                first = (uint64_t)(std::upper_bound(out_start, out_start + n_blocks + 1, a) - out_start) - 1;
+                for (uint64_t b = first; b < n_blocks && out_start[b] < e; ++b) pieces += out_start[b + 1] > out_start[b];
+            }
+            const bool fits = ok && open && (len == 0 || (len <= out_cap && at <= out_cap - len && pieces <= cap_pieces && pieces_at <= cap_pieces - pieces));
+            if (ok && !fits) open = false;
+            range_status[k] = !ok ? TSQA_ERR_ARG : fits ? TSQA_OK : TSQA_ERR_OVERFLOW;
+            out_offsets[k] = at;
+            if (fits && len)
+                for (uint64_t b = first; b < n_blocks && out_start[b] < e; ++b)
+                    if (out_start[b + 1] > out_start[b]) touched.push_back((uint32_t)b);
+            last_len = len;
+            at += (len + mask) & ~mask;
+            pieces_at += pieces;
+        }
+        std::sort(touched.begin(), touched.end());
+        *n_groups = (uint32_t)(std::unique(touched.begin(), touched.end()) - touched.begin());
+    } catch (...) { return TSQA_ERR_ARG; }
+    out_offsets[n_ranges] = n_ranges ? at - ((last_len + mask) & ~mask) + last_len : 0;
+    *n_pieces = pieces_at;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_gather_async(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_offsets, const uint64_t* d_lengths,
+                                 uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void* d_out, size_t out_cap, uint64_t* d_out_offsets,
+                                 int32_t* d_range_status, uint64_t* d_need_pieces, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_offsets || !d_lengths || !d_out || !d_out_offsets || !d_range_status || !d_need_pieces || !d_status) { c->set_error("gather: null pointer"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("gather: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (!packed_align_ok(align)) { c->set_error("gather: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
+    if (cap_pieces < 1) { c->set_error("gather: cap_pieces of 0"); return TSQA_ERR_ARG; }
+    // (the lengths and the piece counts go through group_scan_excl64, whose sums stay below 2^55)
+    if (!gather_sums_ok(n_ranges, idx->total, idx->n_blocks)) {
+        c->set_error("gather: %u ranges of an index of %llu B in %u blocks", n_ranges, (unsigned long long)idx->total, idx->n_blocks);
+        return TSQA_ERR_ARG;
+    }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (n_ranges == 0) {
+        TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+        TSQ_HIP(c, hipMemsetAsync(d_need_pieces, 0, sizeof(uint64_t), s));
+        TSQ_HIP(c, hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
+        return TSQA_OK;
+    }
+    const uint32_t n_blocks = idx->n_blocks, cap_groups = cap_pieces < n_blocks ? cap_pieces : n_blocks;
+    if (int rc = c->reserve_gather(n_ranges, cap_pieces, cap_groups ? cap_groups : 1)) return rc;
+    GatherRange* const ranges = c->gather_ranges;
+    GatherWords* const words = c->gather_words;
+    RangeItem* const items = c->gather_items;
+    RangeItem* const sorted = items + cap_pieces;
+    uint64_t* const keys = c->gather_keys;
+    uint32_t* const slots = c->gather_slots;
+    BlockGroup* const groups = c->gather_groups;
+    const uint32_t n_items = (uint32_t)idx->item_status.size();
+    ProfSpan plan(c, 6, s);
+    hipLaunchKernelGGL(gather_measure_kernel, dim3((uint32_t)(((uint64_t)n_ranges + 255u) / 256u)), dim3(256), 0, s,
+                       static_cast<const FrameInfo*>(idx->frames), n_blocks, idx->total, idx->block_shift, static_cast<const int32_t*>(idx->verdict),
+                       static_cast<const uint64_t*>(idx->d_item_first), n_items, d_items, d_offsets, d_lengths, n_ranges, ranges, d_range_status);
+    hipLaunchKernelGGL(gather_layout_kernel, dim3(1), dim3(256), 0, s, ranges, n_ranges, align, (uint64_t)out_cap, cap_pieces, d_out_offsets,
+                       d_range_status, d_need_pieces, words, d_status);
+    int rc = TSQA_OK;
+    if (n_blocks) {
+        const uint64_t lanes = n_ranges > cap_pieces ? n_ranges : cap_pieces, piece_groups = ((uint64_t)cap_pieces + 255u) / 256u;
+        hipLaunchKernelGGL(gather_pieces_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, s, static_cast<const FrameInfo*>(idx->frames),
+                           n_blocks, static_cast<const GatherRange*>(ranges), n_ranges, static_cast<const int32_t*>(d_range_status),
+                           static_cast<const uint64_t*>(d_out_offsets), static_cast<const GatherWords*>(words), cap_pieces, items, keys, slots);
+        TSQ_HIP(c, gather_sort_pairs(c->gather_sort, c->gather_sort_bytes, keys, keys + cap_pieces, slots, slots + cap_pieces, cap_pieces, s));
+        const uint64_t movers = piece_groups < 4ull * (uint64_t)c->n_cus ? piece_groups : 4ull * (uint64_t)c->n_cus;
+        hipLaunchKernelGGL(gather_groups_kernel, dim3((uint32_t)(1u + movers)), dim3(256), 0, s, static_cast<const RangeItem*>(items),
+                           static_cast<const uint64_t*>(keys + cap_pieces), static_cast<const uint32_t*>(slots + cap_pieces), words, cap_pieces,
+                           sorted, groups, cap_groups);
+        hipLaunchKernelGGL(gather_spans_kernel, dim3((cap_groups + 255u) / 256u), dim3(256), 0, s, static_cast<const RangeItem*>(sorted),
+                           static_cast<const GatherWords*>(words), cap_pieces, groups, cap_groups);
+        plan.end();
+        ProfSpan dec(c, 7, s);
+        rc = launch_read_kernel<dec_group_live_kernel>(c, cap_groups, s, idx->container, static_cast<const FrameInfo*>(idx->frames), n_blocks,
+                                                       static_cast<const RangeItem*>(sorted), cap_pieces, static_cast<const BlockGroup*>(groups),
+                                                       static_cast<uint8_t*>(d_out), &words->stream, static_cast<const uint32_t*>(&words->n_groups));
+        dec.end();
+    } else plan.end();
+    hipLaunchKernelGGL(gather_close_kernel, dim3(1), dim3(1), 0, s, static_cast<const GatherWords*>(words), d_status);
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_gather(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_offsets, const uint64_t* d_lengths,
+                           uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void* d_out, size_t out_cap, uint64_t* d_out_offsets,
+                           int32_t* d_range_status, uint64_t* d_need_pieces, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_gather_async(c, idx, d_items, d_offsets, d_lengths, n_ranges, align, cap_pieces, d_out, out_cap, d_out_offsets,
+                                   d_range_status, d_need_pieces, d_status, s)) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "gather");
+}
+
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
 static int gather_heads(tsqa_ctx* c, const void* d_in, const tsqa_batch_item* items, uint32_t n_items, hipStream_t s, std::vector<uint8_t>& heads)
 {
@@ -2018,6 +2193,9 @@ static int index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_size, con
         const hipError_t e = hipMemcpy(idx->frames, idx->host_frames.data(), (size_t)idx->n_blocks * sizeof(FrameInfo), hipMemcpyHostToDevice);
         if (e != hipSuccess) { c->set_error("index_create_batch: hipMemcpy failed: %s", hipGetErrorString(e)); return TSQA_ERR_HIP; }
     }
+    // each item's first block, for the reads that name their items in device memory (tsqa_gather_async)
+    TSQ_HIP(c, hipMalloc(&idx->d_item_first, ((size_t)n_items + 1) * sizeof(uint64_t)));
+    TSQ_HIP(c, hipMemcpy(idx->d_item_first, idx->item_first.data(), ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (worst) c->set_error("index_create_batch: %u of %u items refused", refused, n_items);
     *out = idx.release();
     return worst;
