@@ -636,6 +636,60 @@ int tsqa_compress_device_split(tsqa_ctx *ctx, const void *d_in, size_t n, uint32
                                size_t *out_size, uint32_t *d_block_sizes, uint32_t ext, void *hip_stream);
 
 /*
+ * Short blocks in a packed batch: tsqa_compress_batch_packed* and tsqa_compress_batch_packed_tables_async with every item cut every
+ * block_len bytes, as tsqa_compress_device_split cuts one buffer.  A batch's speed follows its block count too: 64 items of 1 MiB
+ * are 64 serial chains on 256 CUs.  The pack scan behind each encode launch is parallel over the launch's blocks (one item may own
+ * all 2 x CUs of them), and every call that takes a packed batch takes the result: the batch decodes, the dense decompress,
+ * tsqa_index_create_batch, join, cut, gather, and per item tsqa_decompress_device_sized* and tsqa_index_create_sized*.
+ *
+ * tsqa_plan_batch_split: host only.  block_len: tsqa_plan_split's rule, a power of two from 2^12 to 2^22.  Item i has
+ *   ceil(in_len / block_len) blocks; first_block (n_items + 1) is their prefix sum.  *bound = the sum over the items of
+ *   round_up(tsqa_plan_split(in_len, block_len)'s bound, align): room that always holds the arena.  TSQA_ERR_ARG for
+ *   tsqa_compress_batch_packed_async's refusals (a NULL pointer, n_items == 0, an empty item, an input range past in_size, a bad
+ *   align), a bad block_len, or block counts that do not fit 32 bits.
+ *
+ * tsqa_compress_batch_packed_split_async: the arguments of tsqa_compress_batch_packed_async, block_len, and d_block_sizes (device,
+ *   may be NULL).  Container i, at d_out + offsets[i], is byte for byte what tsqa_compress_device_split gives for item i's bytes
+ *   alone at that block_len and ext: block j's look-ahead runs on into the item's following bytes and ends at the item's last
+ *   byte; it never sees the next item.  d_offsets and d_sizes follow tsqa_plan_packed's rule and are complete and correct whatever
+ *   fits.  The overflow contract is the packed compress's: a header or frame is written only if it ends at or before out_size,
+ *   nothing at or past d_out + out_size is written, padding never; offsets[n_items] > out_size gives TSQA_ERR_OVERFLOW in *d_status,
+ *   every item that lies wholly inside out_size is exact, and a retry with offsets[n_items] bytes succeeds.  d_block_sizes holds
+ *   first_block[n_items] words, word first_block[i] + j = the stream length of block j of item i, complete whatever fits: words
+ *   [first_block[i], first_block[i + 1]) are the table that tsqa_decompress_device_sized* and tsqa_index_create_sized* take for item
+ *   i, and laid end to end they are the table tsqa_join_async leaves for the joined container.  With block_len = TSQ_BLOCK_SZ the
+ *   arena and both tables are tsqa_compress_batch_packed_async's, byte for byte.  The copy pieces per block are counted from the
+ *   split bound of a block; a stream longer than that -- the encoder never makes one -- is TSQA_ERR_OVERFLOW, not a silent cut.
+ *   TSQA_ERR_ARG before anything is enqueued or written: tsqa_compress_batch_packed_async's refusals and a bad block_len.  Encoder
+ *   variants 0, 6 and 7.  Only the item table and first_block are uploaded: the block descriptors are made on the device.
+ * tsqa_compress_batch_packed_split: the waiting form, with host offsets and sizes, as tsqa_compress_batch_packed.
+ *
+ * tsqa_plan_compress_tables_split, tsqa_compress_batch_packed_tables_split_async: the same extension of the device-tables form.
+ *   Rules 1 to 5 of tsqa_compress_batch_packed_tables_async hold with blocks_i = ceil(in_sizes[i] / block_len); an item whose block
+ *   count exceeds 2^32 - 1 is TSQA_ERR_ARG for that item; the bound's term is tsqa_plan_split's bound; d_block_sizes (device, may be
+ *   NULL) is as above, cap_blocks words at most: no word is written past first_block[n_items] or cap_blocks, and the words of
+ *   refused and unfit items do not exist (they have no blocks).  Measure-only and every TSQA_ERR_ARG of that call carry over; a bad
+ *   block_len is one more.  Nothing is uploaded.
+ */
+int tsqa_plan_batch_split(const tsqa_batch_item *items, uint32_t n_items, size_t in_size, uint32_t block_len, uint32_t align,
+                          uint64_t *first_block, uint64_t *bound);
+int tsqa_compress_batch_packed_split_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items,
+                                           uint32_t n_items, uint32_t ext, uint32_t align, uint32_t block_len, void *d_out,
+                                           size_t out_size, uint64_t *d_offsets, uint64_t *d_sizes, uint32_t *d_block_sizes,
+                                           int32_t *d_status, void *hip_stream);
+int tsqa_compress_batch_packed_split(tsqa_ctx *ctx, const void *d_in, size_t in_size, const tsqa_batch_item *items, uint32_t n_items,
+                                     uint32_t ext, uint32_t align, uint32_t block_len, void *d_out, size_t out_size, uint64_t *offsets,
+                                     uint64_t *sizes, uint32_t *d_block_sizes, void *hip_stream);
+int tsqa_plan_compress_tables_split(const uint64_t *in_offsets, const uint64_t *in_sizes, uint32_t n_items, uint64_t in_size,
+                                    uint32_t block_len, uint32_t align, uint32_t cap_blocks, uint64_t *first_block,
+                                    int32_t *item_status, uint64_t *bound, uint32_t *n_fit);
+int tsqa_compress_batch_packed_tables_split_async(tsqa_ctx *ctx, const void *d_in, size_t in_size, const uint64_t *d_in_offsets,
+                                                  const uint64_t *d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
+                                                  uint32_t align, uint32_t block_len, void *d_out, size_t out_size,
+                                                  uint64_t *d_offsets, uint64_t *d_sizes, uint64_t *d_first_block, uint64_t *d_bound,
+                                                  uint32_t *d_block_sizes, int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+
+/*
  * tsqa_decompress_device_sized_async: tsqa_decompress_device_async with the frame walk made in parallel.  A frame carries no
  *   marker, so the plain walk is one lane reading frame after frame (16 384 dependent loads for 1 GiB in 64 KiB blocks); with
  *   d_block_sizes (device, n_blocks words: what the split compress left, or any table of the frames' stream lengths) every frame's

@@ -25,7 +25,9 @@ from .api import (  # noqa: F401
     lib,
     lib_path,
     plan_batch,
+    plan_batch_split,
     plan_compress_tables,
+    plan_compress_tables_split,
     plan_cut,
     plan_gather,
     plan_dense,

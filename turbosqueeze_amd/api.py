@@ -233,6 +233,19 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_compress_device_split_async.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp, C.c_uint32, vp]
     L.tsqa_compress_device_split.restype = C.c_int
     L.tsqa_compress_device_split.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, szp, vp, C.c_uint32, vp]
+    L.tsqa_plan_batch_split.restype = C.c_int
+    L.tsqa_plan_batch_split.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, vp, u64p]
+    L.tsqa_compress_batch_packed_split_async.restype = C.c_int
+    L.tsqa_compress_batch_packed_split_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                                         vp, vp, vp, vp, vp]
+    L.tsqa_compress_batch_packed_split.restype = C.c_int
+    L.tsqa_compress_batch_packed_split.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                                   vp, vp, vp, vp]
+    L.tsqa_plan_compress_tables_split.restype = C.c_int
+    L.tsqa_plan_compress_tables_split.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.tsqa_compress_batch_packed_tables_split_async.restype = C.c_int
+    L.tsqa_compress_batch_packed_tables_split_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tsqa_decompress_device_sized_async.restype = C.c_int
     L.tsqa_decompress_device_sized_async.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
     L.tsqa_decompress_device_sized.restype = C.c_int
@@ -535,6 +548,22 @@ def plan_split(n: int, block_len: int):
     return int(nb.value), int(bound.value)
 
 
+def plan_batch_split(items, in_size: int, block_len: int, align: int = 16):
+    """tsqa_plan_batch_split (host only): items = (in_at, in_len, ...) cut every block_len bytes, a power of two from 2^12 to 2^22
+    -> (each item's first block in the batch, then the batch's block count; the room that always holds the packed arena: the sum
+    of round_up(plan_split's bound, align)).  Raises TsqError(3) when refused."""
+    import numpy as np
+    first = np.zeros(len(items) + 1, dtype=np.uint64)
+    bound = C.c_uint64(0)
+    if not 0 <= block_len < 1 << 32 or not 0 <= align < 1 << 32:
+        raise TsqError(3, "tsqa_plan_batch_split refused the batch")
+    quads = [(it[0], it[1], 0, 0) for it in items]
+    rc = lib().tsqa_plan_batch_split(_batch_array(quads), len(quads), in_size, block_len, align, first.ctypes.data, C.byref(bound))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_batch_split refused the batch")
+    return [int(x) for x in first], int(bound.value)
+
+
 def plan_packed(sizes, align: int = 16):
     """tsqa_plan_packed (host only): the packed layout of containers of the given sizes -> their offsets, then the bytes used
     (offsets[i + 1] = round_up(offsets[i] + sizes[i], align), the last without the rounding).  Raises TsqError(3) when refused."""
@@ -576,6 +605,23 @@ def plan_compress_tables(in_offsets, in_sizes, in_size: int, align: int = 16, ca
                                          status.ctypes.data, C.byref(bound), C.byref(n_fit))
     if rc:
         raise TsqError(rc, "tsqa_plan_compress_tables refused the arguments")
+    return [int(x) for x in first], [int(x) for x in status], int(bound.value), int(n_fit.value)
+
+
+def plan_compress_tables_split(in_offsets, in_sizes, in_size: int, block_len: int, align: int = 16, cap_blocks: int = 0):
+    """tsqa_plan_compress_tables_split (host only): plan_compress_tables with the items cut every block_len bytes; an item of more
+    than 2^32 - 1 blocks reads 3 as well, and the bound's term is plan_split's."""
+    import numpy as np
+    at = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+    sz = np.ascontiguousarray(in_sizes, dtype=np.uint64)
+    first, status = np.zeros(len(sz) + 1, dtype=np.uint64), np.zeros(len(sz), dtype=np.int32)
+    bound, n_fit = C.c_uint64(0), C.c_uint32(0)
+    if not 0 <= block_len < 1 << 32:
+        raise TsqError(3, "tsqa_plan_compress_tables_split refused the arguments")
+    rc = lib().tsqa_plan_compress_tables_split(at.ctypes.data, sz.ctypes.data, min(len(at), len(sz)), in_size, block_len, align, cap_blocks,
+                                               first.ctypes.data, status.ctypes.data, C.byref(bound), C.byref(n_fit))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_compress_tables_split refused the arguments")
     return [int(x) for x in first], [int(x) for x in status], int(bound.value), int(n_fit.value)
 
 
@@ -784,10 +830,13 @@ class BatchIndex(RangeIndex):
 class PackedBatch:
     """What DeviceCodec.compress_batch_packed gives: the containers of a batch one after the other in a dense arena.
     arena: the used bytes (offsets[-1] of them); offsets (n + 1) and sizes (n): host ints, container i = arena[offsets[i]:offsets[i] +
-    sizes[i]] = views[i]; lengths: the items' uncompressed sizes."""
+    sizes[i]] = views[i]; lengths: the items' uncompressed sizes.  A batch of short blocks (compress_batch_packed(..., block_len=))
+    also carries block_len, first_block (host ints, n + 1) and d_block_sizes (an int32 CUDA tensor): d_block_sizes[first_block[i]:
+    first_block[i + 1]] is the table that decompress_sized and index_sized take for views[i]; all three are None otherwise."""
 
-    def __init__(self, codec: "DeviceCodec", arena, offsets, sizes, lengths):
+    def __init__(self, codec: "DeviceCodec", arena, offsets, sizes, lengths, block_len=None, d_block_sizes=None, first_block=None):
         self.codec, self.arena, self.offsets, self.sizes, self.lengths = codec, arena, offsets, sizes, lengths
+        self.block_len, self.d_block_sizes, self.first_block = block_len, d_block_sizes, first_block
         self.views = [arena[o:o + n] for o, n in zip(offsets, sizes)]
 
     @classmethod
@@ -1163,12 +1212,14 @@ class DeviceCodec:
             raise self._err(rc)
         return [out[a:a + int(sizes[k])] for k, (_, _, a, _) in enumerate(items)]
 
-    def compress_batch_packed(self, srcs, ext: int, out=None, align: int = 16) -> PackedBatch:
+    def compress_batch_packed(self, srcs, ext: int, out=None, align: int = 16, block_len=None) -> PackedBatch:
         """compress_batch into a dense arena: container i starts where container i - 1 ended, rounded up to `align` (a power of two,
         1 to 4096); the places are made on the device once the sizes exist.  -> a PackedBatch whose arena is `out`, or a new tensor
         of the sum(batch_bound(n)) worst case, trimmed to the bytes used.  (The trimmed view keeps the worst-case allocation alive:
         to hold only the used bytes, compress again into an `out` of offsets[-1] bytes.)  An `out` that is too small raises
-        TsqError(6) with .needed = the bytes a retry needs."""
+        TsqError(6) with .needed = the bytes a retry needs.  block_len (a power of two from 2^12 to 2^22): every item is cut into
+        blocks of that length, as compress_split cuts one buffer -- container i is compress_split(srcs[i], ext, block_len) --, the
+        new arena is made of plan_batch_split's bound, and the batch carries block_len, first_block and d_block_sizes."""
         align = int(align)
         if not 1 <= align <= 4096 or align & (align - 1):
             raise TsqError(3, f"align {align} is not a power of two from 1 to 4096")
@@ -1176,6 +1227,23 @@ class DeviceCodec:
             raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
         arena, offs = self._arena(srcs)
         items = [(o, t.numel(), 0, 0) for o, t in zip(offs, srcs)]
+        if block_len is not None:
+            first, bound = plan_batch_split(items, arena.numel(), int(block_len), align)
+            if out is None:
+                out = self.torch.empty(bound, dtype=self.torch.uint8, device=self.device)
+            table = self.torch.empty(first[-1], dtype=self.torch.int32, device=self.device)
+            offsets = (C.c_uint64 * (len(items) + 1))()
+            sizes = (C.c_uint64 * len(items))()
+            rc = self.L.tsqa_compress_batch_packed_split(self.h, arena.data_ptr(), arena.numel(), _batch_array(items), len(items), int(ext), align,
+                                                         int(block_len), out.data_ptr(), out.numel(), offsets, sizes, table.data_ptr(),
+                                                         self._stream())
+            if rc:
+                e = self._err(rc)
+                if rc == 6:
+                    e.needed = int(offsets[len(items)])
+                raise e
+            offsets = [int(x) for x in offsets]
+            return PackedBatch(self, out[:offsets[-1]], offsets, [int(x) for x in sizes], [t.numel() for t in srcs], int(block_len), table, first)
         if out is None:
             worst = sum(batch_bound(t.numel()) for t in srcs) + (len(srcs) - 1) * (align - 1)           # (and the padding between them)
             out = self.torch.empty(worst, dtype=self.torch.uint8, device=self.device)
@@ -1261,6 +1329,21 @@ class DeviceCodec:
         rc = self.L.tsqa_compress_batch_packed_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(quads), len(quads), int(ext), int(align),
                                                      out.data_ptr(), out.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(),
                                                      self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def compress_batch_packed_split_async(self, arena, items, ext: int, align: int, block_len: int, out, d_offsets, d_sizes,
+                                          d_block_sizes=None) -> None:
+        """tsqa_compress_batch_packed_split_async on the current stream, nothing waited for: compress_batch_packed_async with every
+        item cut every block_len bytes; d_block_sizes (an int32 CUDA tensor of plan_batch_split's block count, or None) gets every
+        block's stream length, item after item."""
+        quads = [(it[0], it[1], 0, 0) for it in items]
+        if d_block_sizes is not None:
+            self._check_table(d_block_sizes, plan_batch_split(quads, arena.numel(), int(block_len), int(align))[0][-1], at_least=True)
+        rc = self.L.tsqa_compress_batch_packed_split_async(self.h, arena.data_ptr(), arena.numel(), _batch_array(quads), len(quads), int(ext),
+                                                           int(align), int(block_len), out.data_ptr(), out.numel(), d_offsets.data_ptr(),
+                                                           d_sizes.data_ptr(), d_block_sizes.data_ptr() if d_block_sizes is not None else None,
+                                                           self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 
@@ -1423,29 +1506,56 @@ class DeviceCodec:
         if rc:
             raise self._err(rc)
 
+    def compress_batch_packed_tables_split_async(self, data, d_in_offsets, d_in_sizes, n_items: int, cap_blocks: int, ext: int, align: int,
+                                                 block_len: int, out, d_offsets, d_sizes, d_first_block, d_bound, d_block_sizes,
+                                                 d_item_status) -> None:
+        """tsqa_compress_batch_packed_tables_split_async on the current stream: compress_batch_packed_tables_async with every item
+        cut every block_len bytes; d_block_sizes (an int32 CUDA tensor of at least cap_blocks entries, or None) gets the stream
+        lengths of the fitting items' blocks, word d_first_block[i] + j for block j of item i."""
+        if d_block_sizes is not None and out is not None:
+            self._check_table(d_block_sizes, int(cap_blocks), at_least=True)
+        rc = self.L.tsqa_compress_batch_packed_tables_split_async(self.h, data.data_ptr(), data.numel(), d_in_offsets.data_ptr(),
+                                                                  d_in_sizes.data_ptr(), int(n_items), int(cap_blocks), int(ext), int(align),
+                                                                  int(block_len), out.data_ptr() if out is not None else None,
+                                                                  out.numel() if out is not None else 0, d_offsets.data_ptr(), d_sizes.data_ptr(),
+                                                                  d_first_block.data_ptr(), d_bound.data_ptr() if d_bound is not None else None,
+                                                                  d_block_sizes.data_ptr() if d_block_sizes is not None else None,
+                                                                  d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
     def compress_packed_tables(self, data, d_in_offsets, d_in_sizes, ext: int, align: int = 16, cap_blocks=None, out=None,
-                               item_status: bool = False):
+                               item_status: bool = False, block_len=None):
         """Compress the items data[d_in_offsets[i]:][:d_in_sizes[i]] (int64 CUDA tensors) into a dense arena.  With cap_blocks or out
         missing the batch is measured on the device first and the two "needed" words come back with one copy: the block count, and
         the room that always holds the arena, of which a new `out` is made (trimmed to the bytes used afterwards).  -> a PackedBatch
         (PackedBatch.from_device); item_status=True: -> (batch, statuses), and a refused or unfit item -- status 3 or 6, size 0 --
-        does not raise; without it such an item raises TsqError with the largest item status and .item_status."""
+        does not raise; without it such an item raises TsqError with the largest item status and .item_status.  block_len: every
+        item is cut into blocks of that length (compress_batch_packed's block_len), and the batch carries block_len, first_block
+        and d_block_sizes (cap_blocks words)."""
         torch = self.torch
         n = int(d_in_sizes.numel())
         d_offsets, d_sizes, d_first, d_status = self._dense_tables(n)
         d_bound = torch.empty(1, dtype=torch.int64, device=self.device)
         self._join()
+        if block_len is not None:
+            def run(cap, arena, table):
+                self.compress_batch_packed_tables_split_async(data, d_in_offsets, d_in_sizes, n, cap, ext, align, block_len, arena, d_offsets,
+                                                              d_sizes, d_first, d_bound, table, d_status)
+        else:
+            def run(cap, arena, table):
+                self.compress_batch_packed_tables_async(data, d_in_offsets, d_in_sizes, n, cap, ext, align, arena, d_offsets, d_sizes, d_first,
+                                                        d_bound, d_status)
         if cap_blocks is None or out is None:
-            self.compress_batch_packed_tables_async(data, d_in_offsets, d_in_sizes, n, 0, ext, align, None, d_offsets, d_sizes, d_first, d_bound,
-                                                    d_status)
+            run(0, None, None)
             self._join()
             need_blocks, bound = torch.stack([d_first[n], d_bound[0]]).cpu().tolist()
             if cap_blocks is None:
                 cap_blocks = max(need_blocks, 1)
             if out is None:
                 out = torch.empty(max(bound, 16), dtype=torch.uint8, device=self.device)
-        self.compress_batch_packed_tables_async(data, d_in_offsets, d_in_sizes, n, cap_blocks, ext, align, out, d_offsets, d_sizes, d_first, d_bound,
-                                                d_status)
+        table = torch.zeros(max(int(cap_blocks), 1), dtype=torch.int32, device=self.device) if block_len is not None else None
+        run(cap_blocks, out, table)
         self._join()
         status = d_status.cpu().tolist()
         if any(status) and not item_status:
@@ -1454,6 +1564,8 @@ class DeviceCodec:
             raise e
         used = int(d_offsets[n].item())
         batch = PackedBatch.from_device(self, out[:min(used, out.numel())], d_offsets, d_sizes)
+        if block_len is not None:
+            batch.block_len, batch.d_block_sizes, batch.first_block = int(block_len), table, d_first.cpu().tolist()
         return (batch, status) if item_status else batch
 
     def decompress_packed(self, arena, d_offsets, d_sizes, align: int = 16, out=None, item_status: bool = False):

@@ -247,41 +247,45 @@ __global__ __launch_bounds__(256) void batch_layout_kernel(BatchItem* __restrict
 
 // First kernel of tsqa_compress_batch_packed_tables_async, which reads the items' places from tables in device memory: one lane per
 // item.  The tables are not trusted: an item must have at least one byte and lie inside the input (tsqa_plan_batch's checks, which
-// cost the whole call there and the item here).  An accepted item gets in_at, in_len, its block count and status 0; a refused one
-// is all zeros and kErrArg, and not one byte of it is read.  first_block is batch_layout_tables_kernel's.
+// cost the whole call there and the item here), and its blocks of 2^block_shift bytes (22: TSQ_BLOCK_SZ; less: the split form) must
+// be counted in 32 bits.  An accepted item gets in_at, in_len, its block count and status 0; a refused one is all zeros and
+// kErrArg, and not one byte of it is read.  first_block is batch_layout_tables_kernel's.
 __global__ __launch_bounds__(256) void batch_measure_tables_kernel(BatchItem* __restrict__ items, uint32_t n_items,
                                                                    const uint64_t* __restrict__ d_in_offsets,
                                                                    const uint64_t* __restrict__ d_in_sizes, uint64_t in_size,
-                                                                   int32_t* __restrict__ item_status)
+                                                                   uint32_t block_shift, int32_t* __restrict__ item_status)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n_items) return;
     const uint64_t at = d_in_offsets[i], n = d_in_sizes[i];
-    const bool ok = n >= 1u && n <= in_size && at <= in_size - n;
-    // (in_size <= 2^48, the call's own limit: at most 2^26 blocks per item)
-    items[i] = ok ? BatchItem{at, n, 0, 0, 0, (uint32_t)((n + kBlockSize - 1u) / kBlockSize), 0u} : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
+    // (in_size <= 2^48, the call's own limit: at most 2^26 blocks of TSQ_BLOCK_SZ per item, at most 2^36 of 4 KiB)
+    const uint64_t nb = (n >> block_shift) + ((n & (((uint64_t)1 << block_shift) - 1u)) != 0u);
+    const bool ok = n >= 1u && n <= in_size && at <= in_size - n && nb <= 0xFFFFFFFFull;
+    items[i] = ok ? BatchItem{at, n, 0, 0, 0, (uint32_t)nb, 0u} : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
     item_status[i] = ok ? kOk : kErrArg;
 }
 
 // Behind batch_measure_tables_kernel: batch_layout_kernel for a compress, whose arena places exist only once the sizes do.  ONE
-// workgroup of exactly 256 threads, the same two sums per pass with both carries: block counts, and round_up(batch_bound(in_len),
-// align) of the accepted items -- *d_bound (may be NULL), the room that always holds the arena; a refused item adds nothing to
-// either, so a lying size cannot inflate them.  first_block[i + 1] = first_block[i] + blocks_i is complete whatever fits.  An
-// accepted item fits when first_block[i] + blocks_i <= cap_blocks; the fitting items are a prefix of the accepted ones, held as
-// batch_layout_kernel holds it (first_unfit), so a verdict rests on a sum of at most cap_blocks; the whole sums stay below 2^59
-// (2^32 items of at most 2^26 blocks) and cannot wrap.  An item that does not fit gets kErrOverflow and becomes all zeros: nothing
-// of it is read.  *live_blocks = the blocks of the fitting prefix; *status (zero before) = the largest verdict given here.
+// workgroup of exactly 256 threads, the same two sums per pass with both carries: block counts, and round_up(split_bound(in_len,
+// 2^block_shift), align) of the accepted items (block_shift 22: batch_bound) -- *d_bound (may be NULL), the room that always holds
+// the arena; a refused item adds nothing to either, so a lying size cannot inflate them.  first_block[i + 1] = first_block[i] +
+// blocks_i is complete whatever fits.  An accepted item fits when first_block[i] + blocks_i <= cap_blocks; the fitting items are a
+// prefix of the accepted ones, held as batch_layout_kernel holds it (first_unfit), so a verdict rests on a sum of at most
+// cap_blocks; the whole block sum stays below 2^64 (fewer than 2^32 items of fewer than 2^32 blocks each; 2^59 with blocks of
+// TSQ_BLOCK_SZ) and cannot wrap.  An item that does not fit gets kErrOverflow and becomes all zeros: nothing of it is read.
+// *live_blocks = the blocks of the fitting prefix; *status (zero before) = the largest verdict given here.
 // d_offsets != NULL: the measure-only call, which runs nothing behind this kernel (cap_blocks is 0: nothing fits): d_offsets and
 // d_sizes are written, all 0.
 __global__ __launch_bounds__(256) void batch_layout_tables_kernel(BatchItem* __restrict__ items, uint32_t n_items, uint32_t align,
-                                                                  uint32_t cap_blocks, uint64_t* __restrict__ d_offsets,
-                                                                  uint64_t* __restrict__ d_sizes, uint64_t* __restrict__ d_first_block,
+                                                                  uint32_t block_shift, uint32_t cap_blocks,
+                                                                  uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                  uint64_t* __restrict__ d_first_block,
                                                                   uint64_t* __restrict__ d_bound, int32_t* __restrict__ item_status,
                                                                   uint32_t* __restrict__ live_blocks, int32_t* __restrict__ status)
 {
     __shared__ uint64_t wave_sum[4];
     __shared__ uint32_t first_unfit, live;
-    const uint64_t mask = (uint64_t)align - 1u;
+    const uint64_t mask = (uint64_t)align - 1u, in_block = ((uint64_t)1 << block_shift) - 1u;
     if (threadIdx.x == 0) { first_unfit = ~0u; live = 0u; d_first_block[0] = 0; if (d_offsets) d_offsets[0] = 0; }
     uint64_t block_base = 0, bound_base = 0;
     for (uint64_t i0 = 0; i0 < n_items; i0 += 256u) {
@@ -295,7 +299,10 @@ __global__ __launch_bounds__(256) void batch_layout_tables_kernel(BatchItem* __r
         uint64_t sum;
         const uint64_t first = block_base + group_scan_excl64(nb, wave_sum, &sum);
         block_base += sum;
-        group_scan_excl64(accepted ? (batch_bound(len) + mask) & ~mask : 0ull, wave_sum, &sum);
+        // (split_bound(len, 2^block_shift), its division a shift)
+        const uint64_t rest = len & in_block;
+        const uint64_t room = kHeaderSize + (len >> block_shift) * block_bound(in_block + 1u) + (rest ? block_bound(rest) : 0ull);
+        group_scan_excl64(accepted ? (room + mask) & ~mask : 0ull, wave_sum, &sum);
         bound_base += sum;
         const bool fits = accepted && first + nb <= cap_blocks;
         if (accepted && !fits) atomicMin(&first_unfit, (uint32_t)i);
@@ -314,15 +321,18 @@ __global__ __launch_bounds__(256) void batch_layout_tables_kernel(BatchItem* __r
     if (threadIdx.x == 0) { *live_blocks = live; if (d_bound) *d_bound = bound_base; }
 }
 
-// Behind batch_layout_tables_kernel: one lane per live block b makes its EncBatchBlock, in slot b % budget of its launch.  The
-// block's item is the last one whose first_block is at or below b (the items without blocks in front of it share its first_block;
-// the ones behind it, and every unfit item, start past b), found by bisection in d_first_block; launch_item[l] = the item that
-// holds block l * budget, for batch_pack_scan_tables_kernel.  Lanes at or past *live_blocks leave: the descriptors and launch_item
-// entries of dead blocks are never written and never read.
+// Behind batch_layout_tables_kernel: one lane per live block b makes its EncBatchBlock, in slot b % budget of its launch: the
+// block_len bytes of its item from (b - first_block) * block_len on, or what is left of the item, and the look-ahead ends with the
+// item.  The block's item is the last one whose first_block is at or below b (the items without blocks in front of it share its
+// first_block; the ones behind it, and every unfit item, start past b), found by bisection in d_first_block; launch_item[l] = the
+// item that holds block l * budget, for batch_pack_scan_tables_kernel; block_item[b] (NULL: not wanted) = the block's item, for
+// the pack scan of short blocks (tsq_batch_split.cuh).  Lanes at or past *live_blocks leave: the descriptors and table entries of
+// dead blocks are never written and never read.
 __global__ __launch_bounds__(256) void batch_enc_blocks_kernel(const BatchItem* __restrict__ items, uint32_t n_items,
                                                                const uint64_t* __restrict__ d_first_block,
-                                                               const uint32_t* __restrict__ live_blocks, uint32_t budget,
-                                                               EncBatchBlock* __restrict__ blocks, uint32_t* __restrict__ launch_item)
+                                                               const uint32_t* __restrict__ live_blocks, uint32_t budget, uint32_t block_len,
+                                                               EncBatchBlock* __restrict__ blocks, uint32_t* __restrict__ launch_item,
+                                                               uint32_t* __restrict__ block_item)
 {
     const uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= *live_blocks) return;
@@ -332,9 +342,10 @@ __global__ __launch_bounds__(256) void batch_enc_blocks_kernel(const BatchItem* 
         if (d_first_block[mid] <= b) lo = mid; else hi = mid;
     }
     const BatchItem it = items[lo];
-    const uint64_t off = (b - it.first_block) * kBlockSize, left = it.in_len - off;
-    blocks[b] = EncBatchBlock{it.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
+    const uint64_t off = (b - it.first_block) * block_len, left = it.in_len - off;
+    blocks[b] = EncBatchBlock{it.in_at + off, left, left < block_len ? (uint32_t)left : block_len, (uint32_t)(b % budget)};
     if (b % budget == 0u) launch_item[b / budget] = lo;
+    if (block_item) block_item[b] = lo;
 }
 
 // Each block stream of the launch from its slot to its frame (pack_copy_piece); the blocks of items that did not fit are skipped.

@@ -121,6 +121,8 @@ struct tsqa_ctx {
     // launch, the item that holds the launch's first block
     tsqa_scratch<tsq::EncBatchBlock> table_blocks;
     tsqa_scratch<uint32_t> table_launch_item;
+    // the packed batches of short blocks (tsq_batch_split.cuh): per block descriptor, the item it belongs to
+    tsqa_scratch<uint32_t> table_block_item;
     // tsqa_join_async: where each item's body starts in the joined container (one more than items)
     tsqa_scratch<uint64_t> join_at;
     // tsqa_cut_async: per range its source place and its header's fields (one more than ranges: where the written output ends)
@@ -161,7 +163,7 @@ struct tsqa_ctx {
     int reserve_duo(size_t n_blocks, hipStream_t s = nullptr);
     int reserve_host_frames(size_t n);
     int reserve_batch(size_t n_items);
-    int reserve_tables(size_t n_blocks, size_t n_launches);
+    int reserve_tables(size_t n_blocks, size_t n_launches, bool want_items = false);
     int reserve_join(size_t n_items);
     int reserve_cut(size_t n_ranges);
     int reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups);

@@ -8,6 +8,7 @@
 #include "tsq_internal.h"
 
 #include "tsq_batch.cuh"
+#include "tsq_batch_split.cuh"
 #include "tsq_common.cuh"
 #include "tsq_container.cuh"
 #include "tsq_format.h"
@@ -243,14 +244,14 @@ int tsqa_ctx::reserve_batch(size_t n_items)
 }
 
 // Scratch of the compress from device tables (tsq_internal.h): the block descriptors doubled from 256, the launch table from 16,
-// each on its own.
-int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches)
+// each on its own; want_items (the packed batches of short blocks): a word per block for its item, as many as descriptors.
+int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches, bool want_items)
 {
     (void)hipSetDevice(device);
-    const size_t blocks = doubled(256, n_blocks), launches = doubled(16, n_launches);
-    if (!table_blocks.needs(blocks) && !table_launch_item.needs(launches)) return TSQA_OK;
+    const size_t blocks = doubled(256, n_blocks), launches = doubled(16, n_launches), owners = want_items ? blocks : 0;
+    if (!table_blocks.needs(blocks) && !table_launch_item.needs(launches) && !table_block_item.needs(owners)) return TSQA_OK;
     (void)hipDeviceSynchronize();                        // (as in reserve_batch: a call enqueued on any stream may still be using them)
-    return table_blocks.grow(this, blocks) && table_launch_item.grow(this, launches) ? TSQA_OK : TSQA_ERR_HIP;
+    return table_blocks.grow(this, blocks) && table_launch_item.grow(this, launches) && table_block_item.grow(this, owners) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
 // Scratch of the join (tsq_internal.h) beside the batch tables: the body places, doubled from 256 items like them.
@@ -1155,14 +1156,14 @@ enum BatchPlan { kPlanCompress, kPlanDecompress, kPlanRangesOnly, kPlanPlaced, k
 // counts are not known yet (first_block is not written).  kPlanPlaced: a decompress batch whose containers are placed by tables on
 // the device (tsqa_decompress_batch_packed_async): the output ranges and the block counts; in_at and in_len are not looked at.
 // kPlanPacked: a compress batch whose output places are made on the device (tsqa_compress_batch_packed_async): kPlanCompress
-// without output ranges; out_at and out_cap are not looked at.
+// without output ranges; out_at and out_cap are not looked at.  block_len: what a compress batch cuts its items into.
 static int plan_batch(const tsqa_batch_item* items, uint32_t n_items, size_t in_size, size_t out_size, const uint32_t* n_blocks,
-                      uint64_t* first_block, const char** why, BatchPlan mode)
+                      uint64_t* first_block, const char** why, BatchPlan mode, uint32_t block_len = kBlockSize)
 {
     *why = "";
     if (!items || n_items == 0) { *why = "no items"; return TSQA_ERR_ARG; }
     auto blocks_of = [&](uint32_t i) -> uint64_t {
-        return mode == kPlanCompress || mode == kPlanPacked ? items[i].in_len / kBlockSize + (items[i].in_len % kBlockSize != 0)
+        return mode == kPlanCompress || mode == kPlanPacked ? items[i].in_len / block_len + (items[i].in_len % block_len != 0)
                : mode == kPlanDecompress || mode == kPlanPlaced ? n_blocks[i] : 0;
     };
     std::vector<std::pair<uint64_t, uint64_t>> dst;
@@ -1378,13 +1379,115 @@ extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t 
     return finish_sync(c, s, "compress_batch_packed");
 }
 
+// ---- packed batches of short blocks: every item cut every block_len bytes, the pack scan parallel over the launch's blocks ----
+
+static bool split_block_len_ok(uint32_t block_len) { return block_len >= 4096u && block_len <= kBlockSize && (block_len & (block_len - 1u)) == 0u; }
+static uint32_t log2_of(uint32_t pow2) { uint32_t k = 0; while ((1u << k) < pow2) ++k; return k; }
+
+extern "C" int tsqa_plan_batch_split(const tsqa_batch_item* items, uint32_t n_items, size_t in_size, uint32_t block_len, uint32_t align,
+                                     uint64_t* first_block, uint64_t* bound)
+{
+    const char* why;
+    if (!first_block || !bound || !split_block_len_ok(block_len) || !packed_align_ok(align)) return TSQA_ERR_ARG;
+    if (int rc = plan_batch(items, n_items, in_size, 0, nullptr, first_block, &why, kPlanPacked, block_len)) return rc;
+    const uint64_t mask = (uint64_t)align - 1;
+    uint64_t room = 0;
+    for (uint32_t i = 0; i < n_items; ++i) room += (split_bound(items[i].in_len, block_len) + mask) & ~mask;
+    *bound = room;
+    return TSQA_OK;
+}
+
+// Both forms of the packed compress of short blocks: the checks of compress_batch_packed_enqueue and the block_len, then the
+// launches.  Only the item table, first_block and the block count are uploaded: the block descriptors and each block's item are
+// made on the device (batch_enc_blocks_kernel), as the compress from device tables makes them.
+static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                               uint32_t ext, uint32_t align, uint32_t block_len, void* d_out, size_t out_size,
+                                               uint64_t* d_offsets, uint64_t* d_sizes, uint32_t* d_block_sizes, int32_t* d_status, hipStream_t s)
+{
+    const char* const who = "compress_batch_packed_split";
+    if (!d_in || !d_out || !d_status || !items) { c->set_error("%s: null pointer", who); return TSQA_ERR_ARG; }
+    if (!batch_encoder_ok(c, who)) return TSQA_ERR_ARG;
+    if (!packed_align_ok(align)) { c->set_error("%s: align %u is not a power of two from 1 to 4096", who, align); return TSQA_ERR_ARG; }
+    if (!split_block_len_ok(block_len)) { c->set_error("%s: block_len %u is not a power of two from 2^12 to 2^22", who, block_len); return TSQA_ERR_ARG; }
+    if (out_size < kHeaderSize) { c->set_error("%s: out_size holds less than a header", who); return TSQA_ERR_ARG; }
+    if (n_items == 0) { c->set_error("%s: no items", who); return TSQA_ERR_ARG; }
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    const char* why;
+    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanPacked, block_len)) { c->set_error("%s: %s", who, why); return TSQA_ERR_ARG; }
+    (void)hipSetDevice(c->device);
+    const uint64_t n_blocks = first[n_items];
+    const uint32_t budget = batch_budget(c);
+    if (budget > kSplitScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kSplitScanBlocks); return TSQA_ERR_HIP; }
+    const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), first_bytes = ((size_t)n_items + 1) * sizeof(uint64_t);
+    const size_t bytes = item_bytes + first_bytes + sizeof(uint32_t);
+    tsqa_uploads::Slot up;
+    if (int rc = c->batch_up.acquire(c, bytes, &up)) return rc;
+    if (int rc = c->reserve(n_blocks < budget ? n_blocks : budget, true, true, true)) return rc;
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    if (int rc = c->reserve_tables(n_blocks, (n_blocks + budget - 1) / budget, true)) return rc;
+    if (!d_offsets) { d_offsets = c->batch_offsets; d_sizes = c->batch_sizes; }
+    BatchItem* const hi = up.host<BatchItem>();
+    for (uint32_t i = 0; i < n_items; ++i) hi[i] = BatchItem{items[i].in_at, items[i].in_len, 0, 0, first[i], (uint32_t)(first[i + 1] - first[i]), 0u};
+    memcpy(up.host<uint8_t>(item_bytes), first.data(), first_bytes);
+    *up.host<uint32_t>(item_bytes + first_bytes) = (uint32_t)n_blocks;
+    const BatchItem* const di = up.dev<BatchItem>();
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    TSQ_HIP(c, up.send(bytes, s));
+    hipLaunchKernelGGL(batch_enc_blocks_kernel, dim3((uint32_t)((n_blocks + 255u) / 256u)), dim3(256), 0, s, di, n_items,
+                       static_cast<const uint64_t*>(up.dev<uint64_t>(item_bytes)), static_cast<const uint32_t*>(up.dev<uint32_t>(item_bytes + first_bytes)),
+                       budget, block_len, c->table_blocks, c->table_launch_item, c->table_block_item);
+    // (no stream of these blocks is longer than block_bound says: short blocks need few copy pieces)
+    const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
+    const int rc = batch_route_enqueue(c, in, c->table_blocks, n_blocks, ext, pack_pieces(max_stream), out, nullptr, d_status, s, [&](uint64_t b0, uint32_t nb, uint32_t) {
+        // the items with blocks in this launch, as compress_batch_enqueue finds them
+        const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
+        const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
+        hipLaunchKernelGGL(batch_split_scan_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, static_cast<const uint32_t*>(c->sizes),
+                           static_cast<const uint32_t*>(c->table_block_item), ext, align, max_stream, out, (uint64_t)out_size, c->batch_at, c->frame_at,
+                           d_offsets, d_sizes, d_block_sizes, d_status);
+    });
+    TSQ_HIP(c, up.commit(s));                            // (behind a refused launch too: those before it may still read the tables)
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_batch_packed_split_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                                      uint32_t ext, uint32_t align, uint32_t block_len, void* d_out, size_t out_size,
+                                                      uint64_t* d_offsets, uint64_t* d_sizes, uint32_t* d_block_sizes, int32_t* d_status,
+                                                      void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed_split: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    return compress_batch_packed_split_enqueue(c, d_in, in_size, items, n_items, ext, align, block_len, d_out, out_size, d_offsets, d_sizes,
+                                               d_block_sizes, d_status, s);
+}
+
+extern "C" int tsqa_compress_batch_packed_split(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                                uint32_t ext, uint32_t align, uint32_t block_len, void* d_out, size_t out_size, uint64_t* offsets,
+                                                uint64_t* sizes, uint32_t* d_block_sizes, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!offsets || !sizes) { c->set_error("compress_batch_packed_split: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    int rc = compress_batch_packed_split_enqueue(c, d_in, in_size, items, n_items, ext, align, block_len, d_out, out_size, nullptr, nullptr,
+                                                 d_block_sizes, c->d_status, s);
+    if (rc) return rc;
+    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    return finish_sync(c, s, "compress_batch_packed_split");
+}
+
 // ---- packed compress whose item table is made on the device from tables in device memory ----
 
 constexpr uint64_t kTablesInMax = 1ull << 48;    // in_size above this is refused: the block sums then stay below 2^59
 
-extern "C" int tsqa_plan_compress_tables(const uint64_t* in_offsets, const uint64_t* in_sizes, uint32_t n_items, uint64_t in_size,
-                                         uint32_t align, uint32_t cap_blocks, uint64_t* first_block, int32_t* item_status, uint64_t* bound,
-                                         uint32_t* n_fit)
+// tsqa_plan_compress_tables and its split form: the items cut every block_len bytes.
+static int plan_compress_tables(const uint64_t* in_offsets, const uint64_t* in_sizes, uint32_t n_items, uint64_t in_size, uint32_t block_len,
+                                uint32_t align, uint32_t cap_blocks, uint64_t* first_block, int32_t* item_status, uint64_t* bound, uint32_t* n_fit)
 {
     if (!in_offsets || !in_sizes || !first_block || !item_status || !bound || !n_fit || n_items == 0 || !packed_align_ok(align) ||
         in_size > kTablesInMax) return TSQA_ERR_ARG;
@@ -1393,13 +1496,14 @@ extern "C" int tsqa_plan_compress_tables(const uint64_t* in_offsets, const uint6
     uint32_t fit = n_items;
     for (uint32_t i = 0; i < n_items; ++i) {
         const uint64_t at = in_offsets[i], n = in_sizes[i];
-        const bool ok = n >= 1 && n <= in_size && at <= in_size - n;
-        const uint64_t nb = ok ? (n + kBlockSize - 1) / kBlockSize : 0;
+        const uint64_t blocks = n / block_len + (n % block_len != 0);
+        const bool ok = n >= 1 && n <= in_size && at <= in_size - n && blocks <= 0xFFFFFFFFull;
+        const uint64_t nb = ok ? blocks : 0;
         first_block[i] = fb;
         if (ok && fit == n_items && fb + nb > cap_blocks) fit = i;           // (the first unfit item ends the prefix)
         item_status[i] = !ok ? TSQA_ERR_ARG : i >= fit ? TSQA_ERR_OVERFLOW : TSQA_OK;
         fb += nb;
-        if (ok) room += (batch_bound(n) + mask) & ~mask;
+        if (ok) room += (split_bound(n, block_len) + mask) & ~mask;
     }
     first_block[n_items] = fb;
     *bound = room;
@@ -1407,14 +1511,31 @@ extern "C" int tsqa_plan_compress_tables(const uint64_t* in_offsets, const uint6
     return TSQA_OK;
 }
 
-extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
-                                                       const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
-                                                       uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
-                                                       uint64_t* d_first_block, uint64_t* d_bound, int32_t* d_item_status, int32_t* d_status,
-                                                       void* hip_stream)
+extern "C" int tsqa_plan_compress_tables(const uint64_t* in_offsets, const uint64_t* in_sizes, uint32_t n_items, uint64_t in_size,
+                                         uint32_t align, uint32_t cap_blocks, uint64_t* first_block, int32_t* item_status, uint64_t* bound,
+                                         uint32_t* n_fit)
 {
-    if (!c) return TSQA_ERR_ARG;
-    const char* const who = "compress_batch_packed_tables";
+    return plan_compress_tables(in_offsets, in_sizes, n_items, in_size, kBlockSize, align, cap_blocks, first_block, item_status, bound, n_fit);
+}
+
+extern "C" int tsqa_plan_compress_tables_split(const uint64_t* in_offsets, const uint64_t* in_sizes, uint32_t n_items, uint64_t in_size,
+                                               uint32_t block_len, uint32_t align, uint32_t cap_blocks, uint64_t* first_block,
+                                               int32_t* item_status, uint64_t* bound, uint32_t* n_fit)
+{
+    if (!split_block_len_ok(block_len)) return TSQA_ERR_ARG;
+    return plan_compress_tables(in_offsets, in_sizes, n_items, in_size, block_len, align, cap_blocks, first_block, item_status, bound, n_fit);
+}
+
+// tsqa_compress_batch_packed_tables_async (block_len == 0: blocks of TSQ_BLOCK_SZ, batch_pack_scan_tables_kernel, no size table) and
+// its split form (the pack scan of tsq_batch_split.cuh).
+static int compress_tables_enqueue(tsqa_ctx* c, const char* who, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
+                                   const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext, uint32_t align,
+                                   uint32_t block_len, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
+                                   uint64_t* d_first_block, uint64_t* d_bound, uint32_t* d_block_sizes, int32_t* d_item_status,
+                                   int32_t* d_status, void* hip_stream)
+{
+    const bool split = block_len != 0u;
+    if (!split) block_len = kBlockSize;
     if (!d_in || !d_in_offsets || !d_in_sizes || !d_offsets || !d_sizes || !d_first_block || !d_item_status || !d_status) {
         c->set_error("%s: null pointer", who);
         return TSQA_ERR_ARG;
@@ -1426,37 +1547,73 @@ extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* 
         c->set_error("%s: an arena needs out_size >= 16 and cap_blocks above 0; measuring takes d_out NULL and out_size 0", who);
         return TSQA_ERR_ARG;
     }
+    if (split && !split_block_len_ok(block_len)) { c->set_error("%s: block_len %u is not a power of two from 2^12 to 2^22", who, block_len); return TSQA_ERR_ARG; }
     if (!batch_encoder_ok(c, who)) return TSQA_ERR_ARG;
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint32_t budget = batch_budget(c);             // (the launches are sized by cap_blocks, not by a planned count)
+    if (split && budget > kSplitScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kSplitScanBlocks); return TSQA_ERR_HIP; }
     if (int rc = c->reserve_batch(n_items)) return rc;
     if (d_out) {
         if (int rc = c->reserve(cap_blocks < budget ? cap_blocks : budget, true, true, true)) return rc;
-        if (int rc = c->reserve_tables(cap_blocks, ((size_t)cap_blocks + budget - 1) / budget)) return rc;
+        if (int rc = c->reserve_tables(cap_blocks, ((size_t)cap_blocks + budget - 1) / budget, split)) return rc;
     }
     const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
+    const uint32_t block_shift = log2_of(block_len);
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(batch_measure_tables_kernel, per_item, dim3(256), 0, s, c->batch_items, n_items, d_in_offsets, d_in_sizes,
-                       (uint64_t)in_size, d_item_status);
+                       (uint64_t)in_size, block_shift, d_item_status);
     // (measuring: nothing fits, and the kernel writes the two arena tables itself)
-    hipLaunchKernelGGL(batch_layout_tables_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, d_out ? cap_blocks : 0u,
+    hipLaunchKernelGGL(batch_layout_tables_kernel, dim3(1), dim3(256), 0, s, c->batch_items, n_items, align, block_shift, d_out ? cap_blocks : 0u,
                        d_out ? (uint64_t*)nullptr : d_offsets, d_sizes, d_first_block, d_bound, d_item_status, c->batch_live, d_status);
     if (!d_out) { TSQ_HIP(c, hipGetLastError()); return TSQA_OK; }
     const BatchItem* const di = c->batch_items;
     const uint32_t* const live = c->batch_live;
     hipLaunchKernelGGL(batch_enc_blocks_kernel, dim3((uint32_t)(((uint64_t)cap_blocks + 255u) / 256u)), dim3(256), 0, s, di, n_items,
-                       static_cast<const uint64_t*>(d_first_block), live, budget, c->table_blocks, c->table_launch_item);
+                       static_cast<const uint64_t*>(d_first_block), live, budget, block_len, c->table_blocks, c->table_launch_item,
+                       split ? (uint32_t*)c->table_block_item : (uint32_t*)nullptr);
     const uint8_t* const in = static_cast<const uint8_t*>(d_in);
     uint8_t* const out = static_cast<uint8_t*>(d_out);
-    const int rc = batch_route_enqueue(c, in, c->table_blocks, cap_blocks, ext, pack_pieces(), out, live, d_status, s, [&](uint64_t, uint32_t, uint32_t launch) {
-        hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
-                           launch, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
-                           d_offsets, d_sizes, d_item_status, d_status);
+    // (no stream of short blocks is longer than block_bound says: they need few copy pieces)
+    const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
+    const int rc = batch_route_enqueue(c, in, c->table_blocks, cap_blocks, ext, pack_pieces(max_stream), out, live, d_status, s, [&](uint64_t, uint32_t, uint32_t launch) {
+        if (split)
+            hipLaunchKernelGGL(batch_split_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
+                               launch, budget, live, static_cast<const uint32_t*>(c->sizes), static_cast<const uint32_t*>(c->table_block_item), ext,
+                               align, max_stream, out, (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_block_sizes,
+                               d_item_status, d_status);
+        else
+            hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
+                               launch, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
+                               d_offsets, d_sizes, d_item_status, d_status);
     });
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
+}
+
+extern "C" int tsqa_compress_batch_packed_tables_async(tsqa_ctx* c, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
+                                                       const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
+                                                       uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
+                                                       uint64_t* d_first_block, uint64_t* d_bound, int32_t* d_item_status, int32_t* d_status,
+                                                       void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    return compress_tables_enqueue(c, "compress_batch_packed_tables", d_in, in_size, d_in_offsets, d_in_sizes, n_items, cap_blocks, ext, align, 0u,
+                                   d_out, out_size, d_offsets, d_sizes, d_first_block, d_bound, nullptr, d_item_status, d_status, hip_stream);
+}
+
+extern "C" int tsqa_compress_batch_packed_tables_split_async(tsqa_ctx* c, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
+                                                             const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext,
+                                                             uint32_t align, uint32_t block_len, void* d_out, size_t out_size,
+                                                             uint64_t* d_offsets, uint64_t* d_sizes, uint64_t* d_first_block, uint64_t* d_bound,
+                                                             uint32_t* d_block_sizes, int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (block_len == 0u) { c->set_error("compress_batch_packed_tables_split: block_len 0"); return TSQA_ERR_ARG; }
+    return compress_tables_enqueue(c, "compress_batch_packed_tables_split", d_in, in_size, d_in_offsets, d_in_sizes, n_items, cap_blocks, ext, align,
+                                   block_len, d_out, out_size, d_offsets, d_sizes, d_first_block, d_bound, d_block_sizes, d_item_status, d_status,
+                                   hip_stream);
 }
 
 // ---- one container of short blocks: the input cut every block_len bytes, encoded by the batch route ----
