@@ -568,7 +568,7 @@ int tsqa_join(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint6
  *   shorter than 6 bytes or a block longer than TSQ_BLOCK_SZ.
  *
  * tsqa_cut_async: idx is an index of ONE item (tsqa_index_items(idx) == 1): tsqa_index_create, tsqa_index_create_sized*, or a batch
- * index of a single item.  d_first and d_count (n_ranges each) are tables in device memory; nothing is uploaded, nothing in them is
+ * index of a single item made by tsqa_index_create_batch (one made by tsqa_index_create_packed* is refused whatever it holds).  d_first and d_count (n_ranges each) are tables in device memory; nothing is uploaded, nothing in them is
  * trusted, and ranges may overlap and repeat.  Per range k, on the device, all arithmetic in 64 bits:
  *   1. Gate: where the index carries a verdict (a sized index) and it is nonzero, every range gets TSQA_ERR_FORMAT, sizes, totals
  *      and offsets are all 0 and not one byte of d_out is written.
@@ -764,6 +764,9 @@ int      tsqa_index_create_batch(tsqa_ctx *ctx, const void *d_in, size_t in_size
 uint32_t tsqa_index_items(const tsqa_index *idx);                   /* 1 for an index made by tsqa_index_create (0 for NULL) */
 uint64_t tsqa_index_item_total(const tsqa_index *idx, uint32_t i);  /* item i's uncompressed size; 0 when refused */
 int      tsqa_index_item_status(const tsqa_index *idx, uint32_t i); /* TSQA_OK or TSQA_ERR_FORMAT (TSQA_ERR_ARG: no such item) */
+/* (An index made by tsqa_index_create_packed*, below: until tsqa_index_fetch the host has none of its tables -- tsqa_index_items
+ * answers n_items, the totals 0, every item status TSQA_ERR_ARG; afterwards an item status may also be TSQA_ERR_ARG or
+ * TSQA_ERR_OVERFLOW.) */
 
 /* bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at */
 typedef struct tsqa_item_range { uint32_t item, pad; uint64_t offset, length, out_at; } tsqa_item_range;
@@ -797,7 +800,7 @@ int tsqa_decompress_item_ranges(tsqa_ctx *ctx, const tsqa_index *idx, const tsqa
  * Gather: record reads whose ranges lie in DEVICE memory -- sampler indices, a filter's result, offsets a kernel has just
  * computed.  Nothing is uploaded, read back or waited for: the plan that the host makes for tsqa_decompress_item_ranges* is made
  * on the device, and the output is dense, each range's place a prefix sum, so no two destinations can overlap.  Any index:
- * tsqa_index_create, tsqa_index_create_batch, tsqa_index_create_sized*.
+ * tsqa_index_create, tsqa_index_create_batch, tsqa_index_create_sized*, tsqa_index_create_packed* (fetched or not: below).
  *
  * Range k is bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) -- of the index's whole data when d_items is NULL (a batch index:
  * the concatenation, as tsqa_decompress_ranges* reads it), else of item d_items[k]'s own data.  Its bytes land at
@@ -841,6 +844,89 @@ int tsqa_gather_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_it
 int tsqa_gather(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
                 const uint64_t *d_lengths, uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void *d_out, size_t out_cap,
                 uint64_t *d_out_offsets, int32_t *d_range_status, uint64_t *d_need_pieces, int32_t *d_status, void *hip_stream);
+
+/*
+ * The index of a packed batch from its tables in DEVICE memory, with no host wait: the last step of packed compress -> index ->
+ * choose -> gather that was not stream-ordered.  tsqa_index_create_batch wants the items' places on the host, reads the headers
+ * back, waits, walks, copies every descriptor back, waits again and closes the gaps of refused items on the host.  Here the arena
+ * and its tables are taken as tsqa_compress_batch_packed*_async and the ..._tables* forms leave them, everything is made on the
+ * device, and tsqa_gather_async takes the result at once, in both addressing modes.
+ *
+ * tsqa_index_create_packed_async: container i is [d_offsets[i], d_offsets[i] + d_sizes[i]) of d_arena (n_items entries each, device
+ * memory).  The call reads no device memory on the host and waits for no stream; it allocates the index's own device memory
+ * (cap_blocks descriptors of 32 B, 20 B per item) and enqueues its launches on hip_stream.  cap_blocks: the blocks the index may
+ * hold; it sizes the descriptors, the context's scratch and the launches of this call and of every gather through the index: pass
+ * a tight value (d_first_block[n_items] of the compress, or a bound the caller knows).  Nothing in the tables or the arena is
+ * trusted.  d_block_sizes == NULL is the plain form (block_len 0, d_table_first NULL, table_words 0); else the sized form.
+ * Plain form, per item, in this order:
+ *   1. Measure: rules 1 and 2 of the dense decompress (the place inside the arena, the header), else TSQA_ERR_FORMAT: no blocks,
+ *      no bytes, and only the 16 header bytes of a well-placed item have been read.
+ *   2. Fit: the accepted headers' block counts are summed; an item fits when the blocks of the accepted items before it and its
+ *      own are at most cap_blocks.  The fitting items are a prefix of the accepted ones (the first unfit item ends it); an accepted
+ *      item outside it gets TSQA_ERR_OVERFLOW and is not walked.  d_blocks_total[2] = the blocks of all accepted items: the
+ *      cap_blocks a retry needs.  Every sum a verdict rests on is a sum of items that fit, so none can wrap.
+ *   3. Walk: every fitting item is walked as tsqa_index_create_batch walks it, ONE lane per item (an item of many short blocks
+ *      costs its serial walk), into provisional descriptors in the context's scratch; a refusal is TSQA_ERR_FORMAT.
+ *   4. Close up: the healthy items' blocks and totals are summed again -- a refused or unfit item owns no blocks -- and their
+ *      descriptors are put behind each other in the index, out_at in the concatenation of the healthy items' data.  Descriptors
+ *      from the live count to cap_blocks are empty and start at the total.
+ *   5. d_item_status[i] (device, may be NULL; the index keeps its own copy) = the item's verdict; *d_status = the largest.
+ *   For every item the status, the first block and the descriptors are what tsqa_index_create_batch makes for the same containers,
+ *   entry for entry; TSQA_ERR_OVERFLOW is the one status that call does not have.
+ * Sized form: step 3 is made from a table of stream lengths, one lane per BLOCK of the whole batch and no workgroup waiting for
+ *   another, as tsqa_index_create_sized_async walks one container.  Item i's words are d_block_sizes[d_table_first[i] ..
+ *   d_table_first[i + 1]) (d_table_first: n_items + 1 entries, device; d_first_block of tsqa_compress_batch_packed_tables_split_async,
+ *   or tsqa_plan_batch_split's first_block uploaded).  Between steps 1 and 2, per accepted item: d_table_first[i] <=
+ *   d_table_first[i + 1] <= table_words, else TSQA_ERR_ARG; the header must state as many blocks as the item has words, and a total
+ *   that this many blocks of block_len hold with the last one not empty, else TSQA_ERR_FORMAT; such an item has no blocks.  Then
+ *   per block: a word outside [3, TSQ_OUTPUT_SZ] counts as 0 in the sums and refuses its item; the frame's place is 16 plus the
+ *   room (3 + length) of the item's words before it; the frame's six bytes must lie inside the item before one is read; the frame
+ *   must pass the plain walk's checks; the length in its frame word must be the table's; and its block is block_len bytes long,
+ *   the item's last what the header's total leaves.  A failing block refuses its item alone (TSQA_ERR_FORMAT); the others are
+ *   delivered.  No word at or past table_words and no byte at or past d_arena + arena_size is read.  For a true table the result
+ *   is the plain form's, entry for entry.
+ * TSQA_ERR_ARG before anything is enqueued, with *out = NULL: a NULL arena, table, out or d_status pointer; n_items == 0;
+ *   cap_blocks == 0; a plain form with block_len, d_table_first or table_words set; a sized form with a NULL d_table_first or a
+ *   block_len that tsqa_plan_split refuses.
+ * The provisional descriptors and the item table live in the context's scratch: calls that share a context are ordered on one
+ * stream (a call with more items or blocks than any before it first waits for the device, then grows the scratch).
+ *
+ * Using the index before tsqa_index_fetch: tsqa_gather_async takes it unchanged, ordered behind the creation (the same stream, or
+ *   an event).  It launches with cap_blocks as the block count and reads the total on the device; the host's size check of that
+ *   call uses the bound cap_blocks * (block_len ? block_len : TSQ_BLOCK_SZ) in place of tsqa_index_total.  Ranges of refused and
+ *   unfit items are TSQA_ERR_ARG.  On the host, tsqa_index_items answers n_items; tsqa_index_blocks, tsqa_index_total and
+ *   tsqa_index_item_total answer 0 and tsqa_index_item_status TSQA_ERR_ARG: the host does not know yet.  The reads the host plans
+ *   (tsqa_decompress_ranges*, tsqa_decompress_item_ranges*) return TSQA_ERR_ARG with a message that names tsqa_index_fetch, and
+ *   tsqa_cut* refuses it as it refuses a batch index -- fetched or not, and an index of one item too.
+ * tsqa_index_fetch: copies the tables and the live descriptors to the host and waits for hip_stream (behind the creation).  From
+ *   then on the index is a tsqa_index_create_batch index in every respect (tsqa_index_item_status may also read TSQA_ERR_ARG or
+ *   TSQA_ERR_OVERFLOW).  TSQA_OK at once for an index whose tables the host already has.
+ * tsqa_index_device_tables: the device tables of an index made by these calls, valid as long as it lives (any pointer may be
+ *   NULL): d_item_first (n_items + 1: item i owns the blocks [d_item_first[i], d_item_first[i + 1])), d_item_status (n_items),
+ *   d_blocks_total (three words: the live blocks, the total, the blocks of all accepted items).  TSQA_ERR_ARG and NULLs for any
+ *   other index.
+ * tsqa_index_create_packed: the async call, then tsqa_index_fetch; item_status (host, may be NULL) is filled.  As
+ *   tsqa_index_create_batch, the index is made whenever the arguments are valid, and the return value is the largest item status.
+ * tsqa_plan_index_packed: host only, steps 2 and 4 from host tables.  head_status[i]: what steps 1 (and, sized, the table check)
+ *   say of item i, blocks[i] and totals[i] its header's fields (looked at where head_status[i] == 0), walk_status[i] what the walk
+ *   says of it (looked at where it fits).  -> item_first (n_items + 1), item_at (n_items: each item's start in the concatenation),
+ *   item_status, blocks_total (three words, as above), *status.  TSQA_ERR_ARG for a NULL pointer, n_items == 0, cap_blocks == 0, or
+ *   an accepted item with no blocks or more than blocks * TSQ_BLOCK_SZ bytes.
+ */
+int tsqa_plan_index_packed(const uint32_t *blocks, const uint64_t *totals, const int32_t *head_status, const int32_t *walk_status,
+                           uint32_t n_items, uint32_t cap_blocks, uint64_t *item_first, uint64_t *item_at, int32_t *item_status,
+                           uint64_t *blocks_total, int32_t *status);
+int tsqa_index_create_packed_async(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets,
+                                   const uint64_t *d_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t block_len,
+                                   const uint64_t *d_table_first, const uint32_t *d_block_sizes, uint64_t table_words, tsqa_index **out,
+                                   int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+int tsqa_index_create_packed(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint64_t *d_offsets, const uint64_t *d_sizes,
+                             uint32_t n_items, uint32_t cap_blocks, uint32_t block_len, const uint64_t *d_table_first,
+                             const uint32_t *d_block_sizes, uint64_t table_words, tsqa_index **out, int32_t *item_status,
+                             void *hip_stream);
+int tsqa_index_fetch(tsqa_ctx *ctx, tsqa_index *idx, void *hip_stream);
+int tsqa_index_device_tables(const tsqa_index *idx, const uint64_t **d_item_first, const int32_t **d_item_status,
+                             const uint64_t **d_blocks_total);
 
 /* =====================================================================================
  * (1) The reference API (turbosqueeze.h:441-674), C-callable subset

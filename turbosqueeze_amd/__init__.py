@@ -10,6 +10,7 @@ from .api import (  # noqa: F401
     BatchIndex,
     BatchItem,
     BlockGroup,
+    DeviceBatchIndex,
     DeviceCodec,
     ItemRange,
     PackedBatch,
@@ -30,6 +31,7 @@ from .api import (  # noqa: F401
     plan_compress_tables_split,
     plan_cut,
     plan_gather,
+    plan_index_packed,
     plan_dense,
     plan_item_ranges,
     plan_join,

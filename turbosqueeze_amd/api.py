@@ -270,6 +270,17 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_decompress_item_ranges_async.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp, vp]
     L.tsqa_decompress_item_ranges.restype = C.c_int
     L.tsqa_decompress_item_ranges.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
+    L.tsqa_plan_index_packed.restype = C.c_int
+    L.tsqa_plan_index_packed.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.tsqa_index_create_packed_async.restype = C.c_int
+    L.tsqa_index_create_packed_async.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.POINTER(vp),
+                                                 vp, vp, vp]
+    L.tsqa_index_create_packed.restype = C.c_int
+    L.tsqa_index_create_packed.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.POINTER(vp), vp, vp]
+    L.tsqa_index_fetch.restype = C.c_int
+    L.tsqa_index_fetch.argtypes = [vp, vp, vp]
+    L.tsqa_index_device_tables.restype = C.c_int
+    L.tsqa_index_device_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.tsqCompress.restype = None
     L.tsqCompress.argtypes = [vp, vp, C.c_bool, C.c_uint32]
     L.tsqDecompress.restype = None
@@ -827,6 +838,87 @@ class BatchIndex(RangeIndex):
         return RangeIndex.read_many(self, ranges, out)
 
 
+def plan_index_packed(blocks, totals, head_status, walk_status, cap_blocks: int):
+    """tsqa_plan_index_packed (host only): the fit and the close-up of DeviceCodec.index_packed_async from host tables -- per item
+    the header's block count and total, the verdict of the header (and, sized form, table) check, and the walk's verdict.
+    -> (item_first (n + 1), item_at (n), item_status (n), [live blocks, total, blocks needed], status)"""
+    import numpy as np
+    n = len(blocks)
+    nb = np.ascontiguousarray(blocks, dtype=np.uint32)
+    tot = np.ascontiguousarray(totals, dtype=np.uint64)
+    hs = np.ascontiguousarray(head_status, dtype=np.int32)
+    ws = np.ascontiguousarray(walk_status, dtype=np.int32)
+    first, at, st, words, worst = (C.c_uint64 * (n + 1))(), (C.c_uint64 * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_uint64 * 3)(), C.c_int32(0)
+    rc = lib().tsqa_plan_index_packed(nb.ctypes.data, tot.ctypes.data, hs.ctypes.data, ws.ctypes.data, n, int(cap_blocks), first, at, st, words,
+                                      C.byref(worst))
+    if rc:
+        raise TsqError(rc, "plan_index_packed: no items, cap_blocks 0, or an accepted item without blocks or with more bytes than its blocks hold")
+    return list(first), list(at)[:n], list(st)[:n], list(words), int(worst.value)
+
+
+class _DeviceWords:
+    """n words at a device address that somebody else owns, for torch.as_tensor: no copy is made.  (torch takes no read-only
+    view: the tables are the index's, and nobody writes to them.)"""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+class DeviceBatchIndex(BatchIndex):
+    """A BatchIndex made on the device from a packed batch's arena and tables (tsqa_index_create_packed_async): on the current
+    stream, nothing read on the host and nothing waited for.  gather() works at once, in both addressing modes; d_item_first
+    (int64, items + 1), d_item_status (int32) and d_blocks_total (int64: the live blocks, the total, the blocks of all accepted
+    items) are the index's own device tables as tensors, to be read behind the creation; they live as long as the index.  Until
+    fetch() the host knows nothing: n_blocks and total are 0, item_total gives 0, item_status 3, and the reads the host plans
+    (read, read_many, read_flat_many) raise TsqError(3).  Holds references to the arena and the tables."""
+
+    def __init__(self, codec: "DeviceCodec", arena, d_offsets, d_sizes, n_items: int, cap_blocks: int, block_len=None, d_table_first=None,
+                 d_block_sizes=None):
+        torch = codec.torch
+        self.codec, self.blob, self.L = codec, arena, codec.L
+        self.tables = (d_offsets, d_sizes, d_table_first, d_block_sizes)
+        self.h = C.c_void_p()
+        n_items, cap_blocks = int(n_items), int(cap_blocks)
+        for name, t, dtype, least in (("d_offsets", d_offsets, torch.int64, n_items), ("d_sizes", d_sizes, torch.int64, n_items),
+                                      ("d_table_first", d_table_first, torch.int64, n_items + 1), ("d_block_sizes", d_block_sizes, torch.int32, 0)):
+            if t is not None and (t.dtype != dtype or t.device != codec.device or not t.is_contiguous() or t.numel() < least):
+                raise TsqError(3, f"{name} must be a contiguous {str(dtype)[6:]} tensor of at least {least} entries on the codec's device")
+        if (d_block_sizes is None) != (d_table_first is None) or (d_block_sizes is None) != (block_len is None):
+            raise TsqError(3, "the sized form takes block_len, d_table_first and d_block_sizes together")
+        sized = d_block_sizes is not None
+        # (an empty table has no address to give; the call reads no word of it)
+        table = d_block_sizes if not sized or d_block_sizes.numel() else torch.zeros(1, dtype=torch.int32, device=codec.device)
+        self.d_item_status = torch.empty(max(n_items, 1), dtype=torch.int32, device=codec.device)[:n_items]
+        rc = self.L.tsqa_index_create_packed_async(codec.h, arena.data_ptr(), arena.numel(), d_offsets.data_ptr(), d_sizes.data_ptr(), n_items,
+                                                   cap_blocks, int(block_len) if sized else 0, d_table_first.data_ptr() if sized else None,
+                                                   table.data_ptr() if sized else None, d_block_sizes.numel() if sized else 0, C.byref(self.h),
+                                                   self.d_item_status.data_ptr(), codec._status.data_ptr(), codec._stream())
+        if rc:
+            raise codec._err(rc)
+        first, words = C.c_void_p(), C.c_void_p()
+        self.L.tsqa_index_device_tables(self.h, C.byref(first), None, C.byref(words))
+        self.d_item_first = torch.as_tensor(_DeviceWords(first.value, n_items + 1, "<i8"), device=codec.device)
+        self.d_blocks_total = torch.as_tensor(_DeviceWords(words.value, 3, "<i8"), device=codec.device)
+        self.n_blocks, self.total, self.items, self.cap_blocks, self.fetched = 0, 0, n_items, cap_blocks, False
+        self.worst_status = None
+
+    def close(self):
+        self.d_item_first = self.d_blocks_total = None      # (views of the index's own memory)
+        BatchIndex.close(self)
+
+    def fetch(self) -> "DeviceBatchIndex":
+        """tsqa_index_fetch: the tables and descriptors come to the host behind the current stream's work, which is waited for.
+        From then on this is a BatchIndex in every respect (item statuses may also read 3 or 6).  -> self"""
+        rc = self.L.tsqa_index_fetch(self.codec.h, self.h, self.codec._stream())
+        if rc:
+            raise self.codec._err(rc)
+        self.n_blocks = int(self.L.tsqa_index_blocks(self.h))
+        self.total = int(self.L.tsqa_index_total(self.h))
+        self.worst_status = max(self.item_status(i) for i in range(self.items))
+        self.fetched = True
+        return self
+
+
 class PackedBatch:
     """What DeviceCodec.compress_batch_packed gives: the containers of a batch one after the other in a dense arena.
     arena: the used bytes (offsets[-1] of them); offsets (n + 1) and sizes (n): host ints, container i = arena[offsets[i]:offsets[i] +
@@ -835,27 +927,57 @@ class PackedBatch:
     first_block[i + 1]] is the table that decompress_sized and index_sized take for views[i]; all three are None otherwise."""
 
     def __init__(self, codec: "DeviceCodec", arena, offsets, sizes, lengths, block_len=None, d_block_sizes=None, first_block=None):
-        self.codec, self.arena, self.offsets, self.sizes, self.lengths = codec, arena, offsets, sizes, lengths
+        self.codec, self.arena, self._host = codec, arena, (offsets, sizes, lengths)
         self.block_len, self.d_block_sizes, self.first_block = block_len, d_block_sizes, first_block
-        self.views = [arena[o:o + n] for o, n in zip(offsets, sizes)]
+        # the tables in device memory, where the batch came with them (from_device); d_first_block: of a batch of short blocks
+        self.d_offsets = self.d_sizes = self.d_first_block = None
+        self._views = None
+        # the blocks of all items, where the host knows them: from first_block, from the plain compress (4 MiB blocks), or from the
+        # headers once a batch from from_device has been measured; None otherwise (a cut's arena)
+        self.n_blocks = first_block[-1] if first_block else None
+
+    def _tables(self):
+        """The host tables.  A batch made by from_device measures its headers on the device when they are first asked for, and
+        waits for them."""
+        if self._host is None:
+            codec, n = self.codec, int(self.d_sizes.numel())
+            tables = codec._dense_tables(n)
+            codec._join()
+            codec.decompress_batch_packed_dense_async(self.arena, self.d_offsets, self.d_sizes, n, 0, 1, None, *tables)
+            codec._join()
+            # (align 1: the differences of the places are the totals)
+            host = codec.torch.cat([self.d_offsets[:n], self.d_sizes[:n], tables[0][1:] - tables[0][:-1], tables[2][n:]]).cpu().tolist()
+            offsets, sizes, lengths = host[:n], host[n:2 * n], host[2 * n:3 * n]
+            if self.n_blocks is None:
+                self.n_blocks = host[3 * n]                  # (the accepted headers' block counts)
+            self._host = (offsets + [max(o + z for o, z in zip(offsets, sizes))], sizes, lengths)
+        return self._host
+
+    offsets = property(lambda self: self._tables()[0])
+    sizes = property(lambda self: self._tables()[1])
+    lengths = property(lambda self: self._tables()[2])
+
+    @property
+    def views(self):
+        if self._views is None:
+            self._views = [self.arena[o:o + n] for o, n in zip(self.offsets, self.sizes)]
+        return self._views
 
     @classmethod
     def from_device(cls, codec: "DeviceCodec", arena, d_offsets, d_sizes) -> "PackedBatch":
         """A packed batch received as an arena and its two tables in device memory (int64 CUDA tensors: a place per item; one more
-        entry in d_offsets is ignored), from whoever made them: no host lengths are needed.  The headers are measured on the
-        device (DeviceCodec.decompress_batch_packed_dense_async without an output) and both tables and the measured sizes come to
-        the host, so that decompress() and index() work as for a batch compressed here; an item whose header is refused has
-        length 0 and is refused again by them (a place outside the arena makes tsqa_decompress_batch refuse the call).  To
-        decompress only, DeviceCodec.decompress_packed needs none of this and takes such places too."""
-        n = int(d_sizes.numel())
-        tables = codec._dense_tables(n)
-        codec._join()
-        codec.decompress_batch_packed_dense_async(arena, d_offsets, d_sizes, n, 0, 1, None, *tables)
-        codec._join()
-        torch = codec.torch
-        host = torch.cat([d_offsets[:n], d_sizes[:n], tables[0][1:] - tables[0][:-1]]).cpu().tolist()   # (align 1: the differences are the totals)
-        offsets, sizes, lengths = host[:n], host[n:2 * n], host[2 * n:]
-        return cls(codec, arena, offsets + [max(o + z for o, z in zip(offsets, sizes))], sizes, lengths)
+        entry in d_offsets is ignored), from whoever made them: no host lengths are needed.  Nothing is read here: index(sync=False)
+        works from the device tables alone.  When offsets, sizes, lengths or views are first asked for -- decompress() and index()
+        ask --, the headers are measured on the device (DeviceCodec.decompress_batch_packed_dense_async without an output) and
+        both tables and the measured sizes come to the host, so that those work as for a batch compressed here; an item whose
+        header is refused has length 0 and is refused again by them (a place outside the arena makes tsqa_decompress_batch refuse
+        the call).  The tables must not change before that.  To decompress only, DeviceCodec.decompress_packed needs none of this
+        and takes such places too."""
+        if int(d_sizes.numel()) < 1 or int(d_offsets.numel()) < int(d_sizes.numel()):
+            raise TsqError(3, "from_device: no items, or fewer places than sizes")
+        self = cls(codec, arena, None, None, None)
+        self._host, self.d_offsets, self.d_sizes = None, d_offsets, d_sizes
+        return self
 
     def decompress(self, out=None, item_status: bool = False):
         """The items back, through tsqa_decompress_batch (which decodes again by itself after TSQA_ERR_STALL): a list of views into
@@ -878,9 +1000,32 @@ class PackedBatch:
             return views
         return [v if st == 0 else None for v, st in zip(views, status)], [int(st) for st in status]
 
-    def index(self) -> "BatchIndex":
-        """One index over the dense arena, for record reads: index().read(item, offset, length)."""
-        return BatchIndex(self.codec, self.arena, list(zip(self.offsets, self.sizes)))
+    def index(self, sync: bool = True, cap_blocks=None):
+        """One index over the dense arena, for record reads: index().read(item, offset, length).  sync=False: a DeviceBatchIndex made
+        on the current stream from the tables in device memory (DeviceCodec.index_packed_async), nothing waited for; the sized form
+        where the batch carries d_block_sizes.  cap_blocks (sync=False only): the blocks the index may hold; by default the batch's
+        own count (n_blocks) where the host knows it.  A batch from from_device that has not been measured, or a cut's arena, has
+        no count on the host, and the only bound there is -- the arena's bytes in frames of six -- would allocate several times
+        the arena: there cap_blocks must be given (TsqError 3 without it; the d_first_block[n] of the compress, or any bound the
+        caller knows)."""
+        if sync:
+            return BatchIndex(self.codec, self.arena, list(zip(self.offsets, self.sizes)))
+        codec, torch = self.codec, self.codec.torch
+        i64 = lambda values: torch.tensor(values, dtype=torch.int64, device=codec.device)
+        if self.d_offsets is None:
+            self.d_offsets, self.d_sizes = i64(self.offsets), i64(self.sizes)
+        n = int(self.d_sizes.numel())
+        sized = self.d_block_sizes is not None
+        if sized and self.d_first_block is None:
+            self.d_first_block = i64(self.first_block)
+        if cap_blocks is None:
+            if self.n_blocks is None:
+                raise TsqError(3, "index(sync=False): the host does not know this batch's block count (a batch from from_device that has "
+                                  "not been measured, or a cut's arena): pass cap_blocks; asking a from_device batch for its lengths "
+                                  "measures it, and waits")
+            cap_blocks = self.n_blocks
+        return codec.index_packed_async(self.arena, self.d_offsets, self.d_sizes, n, max(int(cap_blocks), 1), self.block_len if sized else None,
+                                        self.d_first_block if sized else None, self.d_block_sizes)
 
     def join(self, out=None, block_sizes: bool = False):
         """The batch as ONE .tsq container whose data is the concatenation of the items' data (DeviceCodec.join of the views:
@@ -1161,6 +1306,16 @@ class DeviceCodec:
         say; sync=False runs on the current torch stream with nothing waited for."""
         return SizedIndex(self, blob, total, block_len, block_sizes, sync)
 
+    def index_packed_async(self, arena, d_offsets, d_sizes, n_items: int, cap_blocks: int, block_len=None, d_table_first=None,
+                           d_block_sizes=None) -> DeviceBatchIndex:
+        """tsqa_index_create_packed_async on the current stream, nothing waited for and nothing read on the host: one index over the
+        containers arena[d_offsets[i]:][:d_sizes[i]] (int64 CUDA tensors, as the packed compress calls leave them).  cap_blocks: the
+        blocks the index may hold (it sizes the index and every gather through it: pass a tight value).  Sized form, for a batch
+        of short blocks: block_len, d_block_sizes (int32) and d_table_first (int64, n_items + 1: item i's words are
+        d_block_sizes[d_table_first[i]:d_table_first[i + 1]], the d_first_block of compress_batch_packed_tables_split_async) make
+        the frame walk parallel over the batch's blocks.  -> a DeviceBatchIndex; the largest item status lands in status()."""
+        return DeviceBatchIndex(self, arena, d_offsets, d_sizes, n_items, cap_blocks, block_len, d_table_first, d_block_sizes)
+
     def index_batch(self, blobs) -> "BatchIndex":
         """One index over many .tsq containers (1-D uint8 CUDA tensors), made in one call: index_batch(blobs).read(item, offset,
         length).  Views of one storage are indexed in place; separate allocations are first packed with one torch.cat."""
@@ -1257,7 +1412,9 @@ class DeviceCodec:
                 e.needed = int(offsets[len(items)])
             raise e
         offsets = [int(x) for x in offsets]
-        return PackedBatch(self, out[:offsets[-1]], offsets, [int(x) for x in sizes], [t.numel() for t in srcs])
+        batch = PackedBatch(self, out[:offsets[-1]], offsets, [int(x) for x in sizes], [t.numel() for t in srcs])
+        batch.n_blocks = sum(-(-t.numel() // BLOCK_SZ) for t in srcs)
+        return batch
 
     def decompress_batch(self, blobs, out=None):
         """Decompress many .tsq containers (1-D uint8 CUDA tensors) in one call.  -> a list of views into one output arena, each trimmed
@@ -1565,7 +1722,8 @@ class DeviceCodec:
         used = int(d_offsets[n].item())
         batch = PackedBatch.from_device(self, out[:min(used, out.numel())], d_offsets, d_sizes)
         if block_len is not None:
-            batch.block_len, batch.d_block_sizes, batch.first_block = int(block_len), table, d_first.cpu().tolist()
+            batch.block_len, batch.d_block_sizes, batch.first_block, batch.d_first_block = int(block_len), table, d_first.cpu().tolist(), d_first
+            batch.n_blocks = batch.first_block[-1]
         return (batch, status) if item_status else batch
 
     def decompress_packed(self, arena, d_offsets, d_sizes, align: int = 16, out=None, item_status: bool = False):

@@ -57,14 +57,20 @@ __device__ __forceinline__ uint32_t gather_block_of(const FrameInfo* __restrict_
 // which owns [0, n_blocks)).  The range must end inside its total, compared so that offset + length is never formed.  A refused
 // range gets kErrArg, no bytes and no pieces.  An accepted one its place, its first block and the blocks with bytes from there to
 // its last byte's: on a sized index that is arithmetic, elsewhere the descriptors in between are read (a block may be empty).
+// kLive: a batch index made on the device and not fetched (tsq_index_packed.cuh), whose total the host does not know: it is read
+// from live[1], and n_blocks is the index's cap_blocks -- the descriptors past the live ones start at the total and are empty, so
+// every look-up above finds what it finds over the live ones.  The other instantiation does not look at `live`.
+template <bool kLive>
 __global__ __launch_bounds__(256) void gather_measure_kernel(const FrameInfo* __restrict__ frames, uint32_t n_blocks, uint64_t total, uint32_t shift,
                                                              const int32_t* __restrict__ verdict, const uint64_t* __restrict__ item_first,
                                                              uint32_t n_items, const uint32_t* __restrict__ d_items,
                                                              const uint64_t* __restrict__ d_offsets, const uint64_t* __restrict__ d_lengths,
-                                                             uint32_t n_ranges, GatherRange* __restrict__ ranges, int32_t* __restrict__ range_status)
+                                                             uint32_t n_ranges, GatherRange* __restrict__ ranges, int32_t* __restrict__ range_status,
+                                                             const uint64_t* __restrict__ live)
 {
     const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (k >= n_ranges) return;
+    if constexpr (kLive) total = live[1];
     GatherRange r{0, 0, 0, 0u, 0u};
     int32_t st = kOk;
     if (verdict && *verdict != 0) st = kErrFormat;

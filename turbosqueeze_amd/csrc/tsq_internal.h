@@ -212,6 +212,14 @@ struct tsqa_index {
     // index, item_first on the device (n_items + 1; NULL for an index of one item, which owns every block)
     uint32_t block_shift = 0;
     uint64_t* d_item_first = nullptr;
+    // a batch index made on the device (tsqa_index_create_packed*, tsq_index_packed.cuh): `frames` holds cap_blocks descriptors, and
+    // behind d_item_first in its allocation lie each item's start in the concatenation (n_items), the words {blocks, total, blocks
+    // needed} and the item statuses.  Until tsqa_index_fetch the host tables below are empty, n_blocks and total are 0, and
+    // pending_items says how many items the device tables describe (0: any other index, or fetched).
+    uint32_t cap_blocks = 0, pending_items = 0, packed_block_len = 0;
+    uint64_t* d_item_at = nullptr;
+    uint64_t* d_words = nullptr;
+    int32_t* d_item_status = nullptr;
     std::vector<tsqa_frame> host_frames;       // their host copy
     std::vector<uint64_t> out_start;           // n_blocks + 1: where each block's output starts, then the total
     // items (one for a single container): item i owns the blocks [item_first[i], item_first[i + 1]), none when it was refused

@@ -15,6 +15,7 @@
 #include "tsq_serial.cuh"
 #include "tsq_split.cuh"
 #include "tsq_index.cuh"
+#include "tsq_index_packed.cuh"
 #include "tsq_join.cuh"
 #include "tsq_cut.cuh"
 #include "tsq_launch.cuh"
@@ -921,7 +922,10 @@ extern "C" void tsqa_index_destroy(tsqa_index* idx)
 
 extern "C" uint32_t tsqa_index_blocks(const tsqa_index* idx) { return idx ? idx->n_blocks : 0u; }
 extern "C" uint64_t tsqa_index_total(const tsqa_index* idx) { return idx ? idx->total : 0ull; }
-extern "C" uint32_t tsqa_index_items(const tsqa_index* idx) { return idx ? (uint32_t)idx->item_status.size() : 0u; }
+extern "C" uint32_t tsqa_index_items(const tsqa_index* idx)
+{
+    return !idx ? 0u : idx->pending_items ? idx->pending_items : (uint32_t)idx->item_status.size();
+}
 extern "C" uint64_t tsqa_index_item_total(const tsqa_index* idx, uint32_t i)
 {
     if (!idx || i >= idx->item_status.size()) return 0ull;
@@ -931,6 +935,9 @@ extern "C" int tsqa_index_item_status(const tsqa_index* idx, uint32_t i)
 {
     return idx && i < idx->item_status.size() ? idx->item_status[i] : TSQA_ERR_ARG;
 }
+
+// What a host-planned read says of a batch index made on the device whose tables have not come to the host (tsqa_index_create_packed_async).
+static const char* const kNeedsFetch = "the index was made on the device and the host has none of its tables: call tsqa_index_fetch first (tsqa_gather_async needs none)";
 
 // Two workgroups writing the same bytes would race: the destinations (at, length) of a call may touch, not overlap.  Sorts them.
 static bool destinations_overlap(std::vector<std::pair<uint64_t, uint64_t>>& dst)
@@ -998,6 +1005,7 @@ extern "C" int tsqa_decompress_ranges_async(tsqa_ctx* c, const tsqa_index* idx, 
     if (!c) return TSQA_ERR_ARG;
     if (!idx || !d_out || !d_status || (n_ranges && !ranges)) { c->set_error("decompress_ranges: null pointer"); return TSQA_ERR_ARG; }
     if (idx->device != c->device) { c->set_error("decompress_ranges: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (idx->pending_items) { c->set_error("decompress_ranges: %s", kNeedsFetch); return TSQA_ERR_ARG; }
     const char* why;
     uint32_t n_items = 0;
     if (plan_ranges(idx->out_start.data(), idx->n_blocks, ranges, n_ranges, out_cap, nullptr, 0, &n_items, &why, true)) {
@@ -1105,6 +1113,7 @@ extern "C" int tsqa_decompress_item_ranges_async(tsqa_ctx* c, const tsqa_index* 
     if (!c) return TSQA_ERR_ARG;
     if (!idx || !d_out || !d_status || (n_ranges && !ranges)) { c->set_error("decompress_item_ranges: null pointer"); return TSQA_ERR_ARG; }
     if (idx->device != c->device) { c->set_error("decompress_item_ranges: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (idx->pending_items) { c->set_error("decompress_item_ranges: %s", kNeedsFetch); return TSQA_ERR_ARG; }
     const char* why = "out of host memory";
     std::vector<tsqa_range_item> vi;
     std::vector<tsqa_block_group> vg;
@@ -1996,6 +2005,8 @@ extern "C" int tsqa_cut_async(tsqa_ctx* c, const tsqa_index* idx, const uint64_t
     if (idx->device != c->device) { c->set_error("cut: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
     if (n_ranges == 0) { c->set_error("cut: no ranges"); return TSQA_ERR_ARG; }
     if (!packed_align_ok(align)) { c->set_error("cut: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
+    // (fetched or not, and of one item too: its descriptors count from the arena's start, not from a container's)
+    if (idx->d_words) { c->set_error("cut: a batch index made on the device; its items already are separate containers"); return TSQA_ERR_ARG; }
     if (idx->item_status.size() != 1) { c->set_error("cut: an index of %zu items; its items already are separate containers", idx->item_status.size()); return TSQA_ERR_ARG; }
     if (d_out ? out_size < kHeaderSize : out_size != 0) {
         c->set_error("cut: an output needs out_size of at least 16; measuring takes d_out NULL and out_size 0");
@@ -2117,8 +2128,12 @@ extern "C" int tsqa_gather_async(tsqa_ctx* c, const tsqa_index* idx, const uint3
     if (!packed_align_ok(align)) { c->set_error("gather: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
     if (cap_pieces < 1) { c->set_error("gather: cap_pieces of 0"); return TSQA_ERR_ARG; }
     // (the lengths and the piece counts go through group_scan_excl64, whose sums stay below 2^55)
-    if (!gather_sums_ok(n_ranges, idx->total, idx->n_blocks)) {
-        c->set_error("gather: %u ranges of an index of %llu B in %u blocks", n_ranges, (unsigned long long)idx->total, idx->n_blocks);
+    // (a batch index made on the device and not fetched: its total is the device's, and the host bounds it by what cap_blocks hold)
+    const bool live = idx->pending_items != 0u;
+    const uint32_t n_blocks = live ? idx->cap_blocks : idx->n_blocks;
+    const uint64_t total_bound = live ? (uint64_t)idx->cap_blocks * (idx->packed_block_len ? idx->packed_block_len : kBlockSize) : idx->total;
+    if (!gather_sums_ok(n_ranges, total_bound, n_blocks)) {
+        c->set_error("gather: %u ranges of an index of %s%llu B in %u blocks", n_ranges, live ? "at most " : "", (unsigned long long)total_bound, n_blocks);
         return TSQA_ERR_ARG;
     }
     hipStream_t s = stream_of(c, hip_stream);
@@ -2129,7 +2144,7 @@ extern "C" int tsqa_gather_async(tsqa_ctx* c, const tsqa_index* idx, const uint3
         TSQ_HIP(c, hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
         return TSQA_OK;
     }
-    const uint32_t n_blocks = idx->n_blocks, cap_groups = cap_pieces < n_blocks ? cap_pieces : n_blocks;
+    const uint32_t cap_groups = cap_pieces < n_blocks ? cap_pieces : n_blocks;
     if (int rc = c->reserve_gather(n_ranges, cap_pieces, cap_groups ? cap_groups : 1)) return rc;
     GatherRange* const ranges = c->gather_ranges;
     GatherWords* const words = c->gather_words;
@@ -2138,11 +2153,15 @@ extern "C" int tsqa_gather_async(tsqa_ctx* c, const tsqa_index* idx, const uint3
     uint64_t* const keys = c->gather_keys;
     uint32_t* const slots = c->gather_slots;
     BlockGroup* const groups = c->gather_groups;
-    const uint32_t n_items = (uint32_t)idx->item_status.size();
+    const uint32_t n_items = tsqa_index_items(idx);
     ProfSpan plan(c, 6, s);
-    hipLaunchKernelGGL(gather_measure_kernel, dim3((uint32_t)(((uint64_t)n_ranges + 255u) / 256u)), dim3(256), 0, s,
+    // (two instantiations: the one that reads the total from the index's device words serves the unfetched batch index alone)
+    void (*const measure)(const FrameInfo*, uint32_t, uint64_t, uint32_t, const int32_t*, const uint64_t*, uint32_t, const uint32_t*, const uint64_t*,
+                          const uint64_t*, uint32_t, GatherRange*, int32_t*, const uint64_t*) = live ? gather_measure_kernel<true> : gather_measure_kernel<false>;
+    hipLaunchKernelGGL(measure, dim3((uint32_t)(((uint64_t)n_ranges + 255u) / 256u)), dim3(256), 0, s,
                        static_cast<const FrameInfo*>(idx->frames), n_blocks, idx->total, idx->block_shift, static_cast<const int32_t*>(idx->verdict),
-                       static_cast<const uint64_t*>(idx->d_item_first), n_items, d_items, d_offsets, d_lengths, n_ranges, ranges, d_range_status);
+                       static_cast<const uint64_t*>(idx->d_item_first), n_items, d_items, d_offsets, d_lengths, n_ranges, ranges, d_range_status,
+                       static_cast<const uint64_t*>(idx->d_words));
     hipLaunchKernelGGL(gather_layout_kernel, dim3(1), dim3(256), 0, s, ranges, n_ranges, align, (uint64_t)out_cap, cap_pieces, d_out_offsets,
                        d_range_status, d_need_pieces, words, d_status);
     int rc = TSQA_OK;
@@ -2368,6 +2387,181 @@ extern "C" int tsqa_index_create_batch(tsqa_ctx* c, const void* d_in, size_t in_
     // (the block counts come from the containers' own headers: the host tables may be refused by the allocator)
     try { return index_create_batch(c, d_in, in_size, items, n_items, out, item_status); }
     catch (...) { c->set_error("index_create_batch: out of host memory"); return TSQA_ERR_ARG; }
+}
+
+// ---- the index of a packed batch from its device tables, with no host wait (tsq_index_packed.cuh) ----
+
+extern "C" int tsqa_plan_index_packed(const uint32_t* blocks, const uint64_t* totals, const int32_t* head_status, const int32_t* walk_status,
+                                      uint32_t n_items, uint32_t cap_blocks, uint64_t* item_first, uint64_t* item_at, int32_t* item_status,
+                                      uint64_t* blocks_total, int32_t* status)
+{
+    if (!blocks || !totals || !head_status || !walk_status || !item_first || !item_at || !item_status || !blocks_total || !status ||
+        n_items == 0 || cap_blocks == 0) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (head_status[i] == TSQA_OK && (blocks[i] == 0 || totals[i] > (uint64_t)blocks[i] * kBlockSize)) return TSQA_ERR_ARG;
+    uint64_t accepted = 0, fb = 0, at = 0;
+    bool open = true;                                        // no accepted item has failed to fit yet
+    int32_t worst = TSQA_OK;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        int32_t st = head_status[i];
+        const uint64_t nb = st == TSQA_OK ? blocks[i] : 0;
+        if (st == TSQA_OK && (!open || accepted + nb > cap_blocks)) { open = false; st = TSQA_ERR_OVERFLOW; }
+        accepted += nb;
+        if (st == TSQA_OK && walk_status[i] != TSQA_OK) st = walk_status[i];
+        item_first[i] = fb; item_at[i] = at; item_status[i] = st;
+        if (st == TSQA_OK) { fb += nb; at += totals[i]; }
+        worst = std::max(worst, st);
+    }
+    item_first[n_items] = fb;
+    blocks_total[0] = fb; blocks_total[1] = at; blocks_total[2] = accepted;
+    *status = worst;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_index_create_packed_async(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                                              uint32_t n_items, uint32_t cap_blocks, uint32_t block_len, const uint64_t* d_table_first,
+                                              const uint32_t* d_block_sizes, uint64_t table_words, tsqa_index** out, int32_t* d_item_status,
+                                              int32_t* d_status, void* hip_stream)
+{
+    if (!out) return TSQA_ERR_ARG;
+    *out = nullptr;
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_arena || !d_offsets || !d_sizes || !d_status) { c->set_error("index_create_packed: null pointer"); return TSQA_ERR_ARG; }
+    if (n_items == 0) { c->set_error("index_create_packed: no items"); return TSQA_ERR_ARG; }
+    if (cap_blocks == 0) { c->set_error("index_create_packed: cap_blocks is 0"); return TSQA_ERR_ARG; }
+    const bool sized = d_block_sizes != nullptr;
+    if (!sized && (block_len != 0 || d_table_first || table_words != 0)) {
+        c->set_error("index_create_packed: the plain form (no d_block_sizes) takes block_len 0, no d_table_first and table_words 0");
+        return TSQA_ERR_ARG;
+    }
+    if (sized) {
+        uint32_t nb = 0;
+        size_t bound = 0;
+        if (!d_table_first) { c->set_error("index_create_packed: null d_table_first"); return TSQA_ERR_ARG; }
+        if (tsqa_plan_split(1, block_len, &nb, &bound)) { c->set_error("index_create_packed: block_len %u is no power of two from 2^12 to 2^22", block_len); return TSQA_ERR_ARG; }
+    }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (int rc = c->reserve_batch(n_items)) return rc;
+    if (int rc = c->reserve(cap_blocks, false, false, true)) return rc;
+    c->forget_sharded();                                 // the walk below overwrites c->frames
+    IndexPtr idx = index_begin(c, "index_create_packed", d_arena, arena_size, 0u, 0ull, false, false);
+    if (!idx) return TSQA_ERR_ARG;
+    idx->cap_blocks = cap_blocks; idx->pending_items = n_items; idx->packed_block_len = block_len;
+    // two allocations, the two that tsqa_index_destroy frees: the descriptors; and item_first (n_items + 1), item_at (n_items), the
+    // words, the sized walk's group sums, the item statuses
+    const uint32_t n_groups = sized ? (uint32_t)(((uint64_t)cap_blocks + kPidxGroup - 1u) / kPidxGroup) : 0u;
+    const size_t n_u64 = 2 * (size_t)n_items + 1 + kPidxWords + n_groups;
+    TSQ_HIP(c, hipMalloc(&idx->frames, (size_t)cap_blocks * sizeof(FrameInfo)));
+    TSQ_HIP(c, hipMalloc(&idx->d_item_first, n_u64 * sizeof(uint64_t) + (size_t)n_items * sizeof(int32_t)));
+    idx->d_item_at = idx->d_item_first + n_items + 1;
+    idx->d_words = idx->d_item_at + n_items;
+    uint64_t* const group_sum = idx->d_words + kPidxWords;
+    idx->d_item_status = reinterpret_cast<int32_t*>(idx->d_item_first + n_u64);
+    const uint8_t* const in = static_cast<const uint8_t*>(d_arena);
+    BatchItem* const items = c->batch_items;
+    uint64_t* const first_block = c->batch_offsets;      // the provisional places: the prefix over every item whose header passed
+    const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u)), per_block((uint32_t)(((uint64_t)cap_blocks + 255u) / 256u));
+    TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(batch_measure_kernel, per_item, dim3(256), 0, s, in, items, n_items, d_offsets, d_sizes, (uint64_t)arena_size, idx->d_item_status);
+    if (sized)
+        hipLaunchKernelGGL(pidx_tables_kernel, per_item, dim3(256), 0, s, items, n_items, block_len, d_table_first, table_words, idx->d_item_status);
+    hipLaunchKernelGGL(join_blocks_kernel, dim3(1), dim3(256), 0, s, items, n_items, cap_blocks, first_block, idx->d_item_status);
+    if (sized) {
+        hipLaunchKernelGGL(pidx_sum_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const BatchItem*>(items), n_items,
+                           static_cast<const uint64_t*>(first_block), cap_blocks, d_block_sizes, c->block_owner, group_sum);
+        hipLaunchKernelGGL(pidx_scan_kernel, dim3(1), dim3(256), 0, s, group_sum, n_groups);
+        hipLaunchKernelGGL(pidx_place_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const BatchItem*>(items),
+                           static_cast<const uint32_t*>(c->block_owner), cap_blocks, d_block_sizes, static_cast<const uint64_t*>(group_sum), c->frame_at);
+        hipLaunchKernelGGL(pidx_check_kernel, per_block, dim3(256), 0, s, in, static_cast<const BatchItem*>(items),
+                           static_cast<const uint32_t*>(c->block_owner), cap_blocks, block_len, d_block_sizes,
+                           static_cast<const uint64_t*>(c->frame_at), c->frames, idx->d_item_status);
+    } else {
+        hipLaunchKernelGGL(batch_walk_kernel<kWalkIndex>, per_item, dim3(256), 0, s, in, static_cast<const BatchItem*>(items), n_items, c->frames,
+                           (uint32_t*)nullptr, c->batch_sizes, (int32_t*)nullptr);
+    }
+    hipLaunchKernelGGL(pidx_close_kernel, dim3(1), dim3(256), 0, s, static_cast<const BatchItem*>(items), n_items,
+                       sized ? (const uint64_t*)nullptr : static_cast<const uint64_t*>(c->batch_sizes), static_cast<const uint64_t*>(first_block),
+                       idx->d_item_status, d_item_status, idx->d_item_first, idx->d_item_at, idx->d_words, d_status);
+    hipLaunchKernelGGL(pidx_move_kernel, per_block, dim3(256), 0, s, static_cast<const BatchItem*>(items), n_items,
+                       static_cast<const FrameInfo*>(c->frames), static_cast<const uint64_t*>(idx->d_item_first),
+                       static_cast<const uint64_t*>(idx->d_item_at), static_cast<const uint64_t*>(idx->d_words), cap_blocks, idx->frames);
+    TSQ_HIP(c, hipGetLastError());
+    *out = idx.release();
+    return TSQA_OK;
+}
+
+// tsqa_index_fetch behind its argument checks; a host allocation may throw.
+static int index_fetch(tsqa_ctx* c, tsqa_index* idx, hipStream_t s)
+{
+    const uint32_t n_items = idx->pending_items;
+    std::vector<uint64_t> first((size_t)n_items + 1);
+    std::vector<int32_t> status(n_items);
+    uint64_t words[kPidxWords] = {0, 0, 0};
+    TSQ_HIP(c, hipMemcpyAsync(first.data(), idx->d_item_first, first.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(status.data(), idx->d_item_status, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(words, idx->d_words, sizeof(words), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    const uint64_t live = words[0];
+    if (live > idx->cap_blocks || first[n_items] != live) { c->set_error("index_fetch: the device tables are not an index's (was the creation enqueued on this stream?)"); return TSQA_ERR_ARG; }
+    std::vector<tsqa_frame> frames(live);
+    std::vector<uint64_t> out_start(live + 1);
+    if (live) {
+        TSQ_HIP(c, hipMemcpyAsync(frames.data(), idx->frames, (size_t)live * sizeof(FrameInfo), hipMemcpyDeviceToHost, s));
+        TSQ_HIP(c, hipStreamSynchronize(s));
+    }
+    for (uint64_t b = 0; b < live; ++b) out_start[b] = frames[b].out_at;
+    out_start[live] = words[1];
+    idx->host_frames.swap(frames); idx->out_start.swap(out_start); idx->item_first.swap(first); idx->item_status.swap(status);
+    idx->n_blocks = (uint32_t)live; idx->total = words[1];
+    idx->pending_items = 0;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_index_fetch(tsqa_ctx* c, tsqa_index* idx, void* hip_stream)
+{
+    static_assert(sizeof(tsqa_frame) == sizeof(FrameInfo), "public frame = kernel frame");
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx) { c->set_error("index_fetch: null index"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("index_fetch: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (!idx->pending_items) return TSQA_OK;             // the host has its tables already
+    (void)hipSetDevice(c->device);
+    try { return index_fetch(c, idx, stream_of(c, hip_stream)); }
+    catch (...) { c->set_error("index_fetch: out of host memory"); return TSQA_ERR_ARG; }
+}
+
+extern "C" int tsqa_index_device_tables(const tsqa_index* idx, const uint64_t** d_item_first, const int32_t** d_item_status, const uint64_t** d_blocks_total)
+{
+    const bool made = idx && idx->d_words;
+    if (d_item_first) *d_item_first = made ? idx->d_item_first : nullptr;
+    if (d_item_status) *d_item_status = made ? idx->d_item_status : nullptr;
+    if (d_blocks_total) *d_blocks_total = made ? idx->d_words : nullptr;
+    return made ? TSQA_OK : TSQA_ERR_ARG;
+}
+
+extern "C" int tsqa_index_create_packed(tsqa_ctx* c, const void* d_arena, size_t arena_size, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                                        uint32_t n_items, uint32_t cap_blocks, uint32_t block_len, const uint64_t* d_table_first,
+                                        const uint32_t* d_block_sizes, uint64_t table_words, tsqa_index** out, int32_t* item_status, void* hip_stream)
+{
+    if (!out) return TSQA_ERR_ARG;
+    *out = nullptr;
+    if (!c) return TSQA_ERR_ARG;
+    tsqa_index* made = nullptr;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_index_create_packed_async(c, d_arena, arena_size, d_offsets, d_sizes, n_items, cap_blocks, block_len, d_table_first,
+                                                d_block_sizes, table_words, &made, nullptr, c->d_status, s)) return rc;
+    IndexPtr idx(made);
+    if (int rc = tsqa_index_fetch(c, idx.get(), s)) return rc;
+    int32_t worst = TSQA_OK;
+    uint32_t refused = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const int32_t st = idx->item_status[i];
+        if (item_status) item_status[i] = st;
+        worst = std::max(worst, st); refused += st != TSQA_OK;
+    }
+    if (worst) c->set_error("index_create_packed: %u of %u items refused (worst status %d)", refused, n_items, worst);
+    *out = idx.release();
+    return worst;
 }
 
 // ---- the second roofline denominator: what a plain device copy reaches on this GPU ----
