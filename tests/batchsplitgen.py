@@ -10,14 +10,14 @@ What is restated from the library, and must be re-derived when it changes there:
   measure, layout   batch_measure_tables_kernel and batch_layout_tables_kernel (tsq_batch.cuh) with a block_len, and
                     tsqa_plan_compress_tables_split: an item of more than 2^32 - 1 blocks is refused like a bad place
   packed            tsqa_plan_packed's rule, applied to the container sizes (a size of 0 takes no room)
-  image             the fit rule of batch_split_scan_body (tsq_batch_split.cuh): a header or frame is written only if it ends at or
+  image             the fit rule of batch_pack_scan_packed_body (tsq_batch.cuh): a header or frame is written only if it ends at or
                     before out_size
   DEFAULT_BUDGET    an encode launch takes 2 x CUs blocks (batch_budget, tsq_runtime.hip); the MI355X's 256 CUs.  The GPU tests take
                     the device's
   GROUP, WAVE       the pack scan is ONE workgroup of 256 threads, four wavefronts of 64, that takes the launch's blocks -- and its
                     items -- 256 at a time
   SPLIT             group_scan_excl64 (tsq_container.cuh) sums the low 24 bits and the rest of every value apart; the scan over a
-                    launch's blocks starts from 0 in every launch (E[], batch_split_scan_body)
+                    launch's blocks starts from 0 in every launch (E[], batch_pack_scan_packed_body)
 """
 from __future__ import annotations
 

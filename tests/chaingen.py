@@ -25,7 +25,7 @@ STRIDE = BLOCK + HALO
 FIRST_BATCH_ITEMS = 256              # tsq_runtime.hip, tsqa_ctx::reserve_batch: `size_t want = 256; while (want < n_items) want *= 2;`
 FIRST_UPLOAD_BYTES = 4096            # tsq_runtime.hip, tsqa_uploads::acquire: `size_t want = 4096; while (want < bytes) want *= 2;`
 SIZEOF_BATCH_ITEM = 48               # tsq_runtime.hip, compress_batch_enqueue: static_assert(... sizeof(BatchItem) == 48 ...)
-SIZEOF_ENC_BATCH_BLOCK = 24          # the same static_assert: sizeof(EncBatchBlock) == 24
+SIZEOF_ENC_BATCH_BLOCK = 24          # the same static_assert: sizeof(EncBatchBlock) == 24 (uploaded by tsqa_compress_batch_async alone)
 SIZEOF_RANGE_ITEM = 24               # include/turbosqueeze_amd.h: tsqa_range_item {u32 block, lo, hi, pad; u64 out_at}
 SIZEOF_BLOCK_GROUP = 16              # include/turbosqueeze_amd.h: tsqa_block_group {u32 block, first, count, hi}
 # which entry points write the context's frame descriptors (c->frames) and so forget a sharded decode: tsq_runtime.hip,
@@ -297,7 +297,7 @@ class Gen:
         out_size = offsets[n] - 1 if fail == "room" else offsets[n]     # one byte short of the last container / exactly the bytes used
         return Link("PC", shape, fail, arena=arena, spans=[(o, d.size) for o, d in zip(offs, datas)], datas=datas, ext=ext, want=want,
                     sizes=sizes, offsets=offsets, out_size=out_size, tight=n - 1 if fail else None, items=n, blocks=n,
-                    upload=n * SIZEOF_BATCH_ITEM + n * SIZEOF_ENC_BATCH_BLOCK)
+                    upload=n * SIZEOF_BATCH_ITEM + (n + 1) * 8 + 4)     # the item table, first_block, the block count: no descriptors
 
     def _PD(self, shape, v, fail):
         datas, ext = self.items(shape, v), (v + 1) & 1

@@ -3,9 +3,10 @@ test_packed_edges_cpu.py -- which shows with the oracle and the host-only planne
 the GPU tests, which run the same inputs through the kernels.  Nothing here calls a kernel: the only library code used is host code
 (plan_packed, plan_batch, batch_bound, the synthetic-input helpers).
 
-The constants mirror batch_pack_scan_packed_kernel and compress_batch_enqueue (tsq_batch.cuh, tsq_runtime.hip) and must be re-derived
+The constants mirror batch_pack_scan_packed_kernel and batch_route_enqueue (tsq_batch.cuh, tsq_runtime.hip) and must be re-derived
 with them: an encode launch takes 2 x CUs blocks, the place-making kernel is ONE workgroup of 256 threads (four wavefronts of 64) that
-walks the launch's items 256 at a time, and group_scan_excl64 sums the low 24 bits and the rest of every size separately."""
+takes the launch's blocks, and then its items, 256 at a time, and group_scan_excl64 sums the low 24 bits and the rest of every size
+separately."""
 from __future__ import annotations
 
 import bisect
@@ -56,8 +57,8 @@ def first_blocks(lengths):
 
 
 def launches(lengths, cus):
-    """the encode launches of a compress batch, as compress_batch_enqueue cuts them: (i0, i1, b0, nb) -- items [i0, i1) have blocks
-    among the launch's blocks [b0, b0 + nb)"""
+    """the encode launches of a compress batch, as batch_route_enqueue cuts them and launch_items finds their items: (i0, i1, b0, nb)
+    -- items [i0, i1) have blocks among the launch's blocks [b0, b0 + nb)"""
     first = first_blocks(lengths)
     n, out = len(lengths), []
     for b0 in range(0, first[-1], budget(cus)):

@@ -11,7 +11,7 @@ What is restated from the library, and must be re-derived when it changes there:
   GROUP        batch_layout_tables_kernel and the pack scan are ONE workgroup of 256 threads that takes its items 256 at a time
   budget       an encode launch takes 2 x CUs blocks (tsqa_compress_batch_packed_tables_async); DEFAULT_BUDGET is the MI355X's
   packed       tsqa_plan_packed's rule, applied to the container sizes (a size of 0 takes no room)
-  pieces       a header or frame is written only if it ends at or before out_size (batch_item_frames)
+  pieces       a header or frame is written only if it ends at or before out_size (batch_pack_scan_packed_body)
 """
 from __future__ import annotations
 

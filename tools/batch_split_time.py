@@ -24,7 +24,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MiB = 1 << 20
-KERNELS = ("batch_split_scan_kernel", "enc_batch_kernel", "batch_enc_blocks_kernel", "batch_pack_copy_kernel")
+KERNELS = ("batch_pack_scan_packed_kernel", "enc_batch_kernel", "batch_enc_blocks_kernel", "batch_pack_copy_kernel")
 
 
 def kernel_stats(path, emit):
@@ -39,7 +39,7 @@ def kernel_stats(path, emit):
     avg = {k: round(t / c / 1e3, 2) for k, (c, t) in rows.items()}
     emit({"measurement": "kernel_stats", "source": "rocprofv3 --kernel-trace --stats, one item of 2 x CUs blocks of 4 KiB",
           "kernels": {k: {"calls": rows[k][0], "average_us": avg[k]} for k in sorted(rows)},
-          "scan_below_encode": avg.get("batch_split_scan_kernel", 0) < avg.get("enc_batch_kernel", 0)})
+          "scan_below_encode": avg.get("batch_pack_scan_packed_kernel", 0) < avg.get("enc_batch_kernel", 0)})
 
 
 def main():

@@ -17,27 +17,25 @@ struct BatchItem { uint64_t in_at, in_len, out_at, out_cap, first_block; uint32_
 
 constexpr uint64_t kNoFrame = ~0ull;      // frame_at of a block whose frame does not fit its item: batch_pack_copy_kernel skips it
 
-// The frames of item `it` in the encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0), for both pack scans.
-// The item's frame offsets run on from where its previous launch left them (*run_at; the caller stores what this returns), and its
-// header goes out with its first block.  write: the item's container starts at out + start, and a header or frame is written only
-// if it ends at or before out + limit: frame_at[b - b0] is the frame's offset in `out`, or kNoFrame.  !write: sizing only.
+// The frames of item `it` in the encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0), for
+// batch_pack_scan_kernel.  The item's frame offsets run on from where its previous launch left them (*run_at; the caller stores
+// what this returns), and its header goes out with its first block.  The item's container starts at out + start, and a header or
+// frame is written only if it ends at or before out + limit: frame_at[b - b0] is the frame's offset in `out`, or kNoFrame.
 __device__ __forceinline__ uint64_t batch_item_frames(const BatchItem& it, const uint64_t* run_at, uint64_t b0, uint32_t nb,
-                                                     const uint32_t* __restrict__ sizes, uint32_t ext, bool write, uint8_t* out,
-                                                     uint64_t start, uint64_t limit, uint64_t* frame_at)
+                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint8_t* out, uint64_t start,
+                                                     uint64_t limit, uint64_t* frame_at)
 {
-    if (it.n_blocks == 0u) return 0;                         // (an item that batch_layout_tables_kernel left out: no header either)
+    if (it.n_blocks == 0u) return 0;                         // (the planner refuses an empty item; one without blocks has no header either)
     const uint64_t first = it.first_block, end = first + it.n_blocks, launch_end = b0 + nb;
     const bool begins = first >= b0;
-    if (write && begins && start + kHeaderSize <= limit) write_header(out + start, it.n_blocks, it.in_len);
+    if (begins && start + kHeaderSize <= limit) write_header(out + start, it.n_blocks, it.in_len);
     uint64_t at = begins ? kHeaderSize : *run_at;
     for (uint64_t b = begins ? first : b0; b < end && b < launch_end; ++b) {
         const uint32_t k = (uint32_t)(b - b0), sz = sizes[k];
         const uint64_t next = at + kFrameWordSize + sz;
-        if (write) {
-            const bool fits = start + next <= limit;
-            if (fits) write_frame(out + start + at, sz, ext);
-            frame_at[k] = fits ? start + at : kNoFrame;
-        }
+        const bool fits = start + next <= limit;
+        if (fits) write_frame(out + start + at, sz, ext);
+        frame_at[k] = fits ? start + at : kNoFrame;
         at = next;
     }
     return at;
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* _
     if (j >= ni) return;
     const uint32_t i = i0 + j;
     const BatchItem it = items[i];
-    const uint64_t at = batch_item_frames(it, run_at + i, b0, nb, sizes, ext, true, out, it.out_at, it.out_at + it.out_cap, frame_at);
+    const uint64_t at = batch_item_frames(it, run_at + i, b0, nb, sizes, ext, out, it.out_at, it.out_at + it.out_cap, frame_at);
     run_at[i] = at;
     if (it.first_block + it.n_blocks <= b0 + nb) {
         d_sizes[i] = at;
@@ -64,41 +62,81 @@ __global__ __launch_bounds__(256) void batch_pack_scan_kernel(const BatchItem* _
     }
 }
 
-// batch_pack_scan_kernel for a packed batch (tsqa_compress_batch_packed*): the items' places are made here, not taken from the
-// caller.  Item i starts at offsets[i]; offsets[i + 1] = round_up(offsets[i] + sizes[i], align), the last without the rounding.
-// ONE workgroup per encode launch: a launch holds at most 2 x CUs blocks, hence at most 2 x CUs + 1 items, and every one of them
-// but the last is complete in it, so their starts are offsets[i0] + an exclusive sum of round_up(size, align) over the launch's
-// items (offsets[i] is a multiple of align, so the rounding may be done per item).  offsets[] is the carry between launches: the
-// first launch writes offsets[0] = 0, an item that a launch completes writes its successor's start, and the next launch reads
-// offsets[i0] whether its first item continues (its start) or begins there (what the last complete item left).  Each item is sized
-// first (batch_item_frames without writing), and written once the scan has made its start; a header or frame is written only if it
-// ends inside out_size; sizes[] and offsets[] are complete whatever fits.
-// The body serves both entries below.  item_status == NULL: the batch planned on the host, one word: the places only grow, so the
-// last item tells whether the arena was too small.  Else (the batch made from device tables, whose window may also hold any
-// number of items without blocks: they take no room) each item that ends past out_size gets kErrOverflow for itself.
+constexpr uint32_t kPackScanBlocks = 1024;    // the most blocks of one encode launch that the scan takes (the chip's 2 x CUs is 512)
+
+// The pack scan of a packed batch (tsqa_compress_batch_packed*, the split forms and the calls from device tables, at every block
+// length): the items' places are made here, not taken from the caller.  Item i starts at offsets[i]; offsets[i + 1] =
+// round_up(offsets[i] + sizes[i], align), the last without the rounding.  ONE workgroup per encode launch: a launch holds at most
+// 2 x CUs blocks, hence at most 2 x CUs + 1 items with blocks, and every one of them but the last is complete in it, so their starts
+// are offsets[i0] + an exclusive sum of round_up(size, align) over the launch's items (offsets[i] is a multiple of align, so the
+// rounding may be done per item).  offsets[] is the carry between launches: the first launch writes offsets[0] = 0, an item that a
+// launch completes writes its successor's start, and the next launch reads offsets[i0] whether its first item continues (its
+// start) or begins there (what the last complete item left).  sizes[] and offsets[] are complete whatever fits.
+// item_status == NULL: the batch planned on the host, one word: the places only grow, so the last item tells whether the arena was
+// too small.  Else (the batch made from device tables, whose window may also hold any number of items without blocks: they take
+// no room) each item that ends past out_size gets kErrOverflow for itself.
+//
+// It runs after an encode launch of the batch's blocks [b0, b0 + nb) (block b in slot b - b0, nb <= kPackScanBlocks), whose items
+// with blocks in it -- and, from device tables, the items without blocks among them -- are [i0, i0 + ni).  Exactly 256 threads,
+// three steps, no lane ever walking an item's blocks: with blocks of TSQ_BLOCK_SZ an item rarely owns more than a few of a
+// launch, with short blocks one item can own all 2 x CUs of them, behind an encode that lasts about as long as one 4 KiB chain.
+//   1. E[0 .. nb] in LDS: the exclusive sum of (3 + sizes[k]) over the launch's blocks, 256 per pass.
+//   2. One lane per item, 256 per pass: the item's bytes so far are carry + E[l] - E[f] for its blocks [f, l) of the launch,
+//      carry = 16 where it begins in the launch (its header goes out here), else run_at[i], what its previous launch left.  The
+//      same scan over round_up(size, align) of the items complete in the launch makes the starts.  Only the window's first item
+//      can have begun in an earlier launch, so one word (carry0) keeps the carry that its lane has overwritten.
+//   3. Behind a barrier, one lane per block: frame_at[k] = start + carry + E[k] - E[f] of its item block_item[b0 + k], whose start
+//      is d_offsets[i]: the window's first item found it there, every other one had it written in step 2 by the lane of the item
+//      in front of it (all but the window's last are complete).  Then the fit rule -- a header or frame is written only if it ends
+//      at or before out_size --, write_frame or kNoFrame, and d_block_sizes[b0 + k] (may be NULL) = the stream length, whatever fits.
+// max_stream: the longest stream the copy behind this kernel moves whole (its pieces are counted from block_bound(block_len)); a
+// longer one -- the encoder never makes it -- is kErrOverflow in *status, not a silent cut.  All sums stay below 2^55.
 __device__ __forceinline__ void batch_pack_scan_packed_body(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0, uint32_t ni,
-                                                            uint64_t b0, uint32_t nb, const uint32_t* __restrict__ sizes, uint32_t ext,
-                                                            uint32_t align, uint8_t* __restrict__ out, uint64_t out_size,
-                                                            uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
-                                                            uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
+                                                            uint64_t b0, uint32_t nb, const uint32_t* __restrict__ sizes,
+                                                            const uint32_t* __restrict__ block_item, uint32_t ext, uint32_t align,
+                                                            uint32_t max_stream, uint8_t* __restrict__ out, uint64_t out_size,
+                                                            uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at, uint64_t* d_offsets,
+                                                            uint64_t* __restrict__ d_sizes, uint32_t* __restrict__ d_block_sizes,
                                                             int32_t* __restrict__ item_status, int32_t* __restrict__ status)
 {
     __shared__ uint64_t wave_sum[4];
-    const uint64_t mask = (uint64_t)align - 1u;
-    uint64_t base = b0 == 0 ? 0ull : d_offsets[i0];          // where the launch's first item starts
-    if (b0 == 0 && threadIdx.x == 0) d_offsets[0] = 0;
+    __shared__ uint64_t E[kPackScanBlocks + 1];
+    __shared__ uint64_t carry0;
+    const uint32_t t = threadIdx.x;
+    const uint64_t mask = (uint64_t)align - 1u, launch_end = b0 + nb;
+
+    uint64_t run = 0;
+    for (uint32_t k0 = 0; k0 < nb; k0 += 256u) {             // (no thread leaves a loop early: the scans need them all)
+        const uint32_t k = k0 + t;
+        const bool valid = k < nb;
+        uint64_t sum;
+        const uint64_t e = run + group_scan_excl64(valid ? kFrameWordSize + (uint64_t)sizes[k] : 0ull, wave_sum, &sum);
+        if (valid) E[k] = e;
+        run += sum;
+    }
+    if (t == 0u) E[nb] = run;
+    __syncthreads();
+
+    const uint64_t start0 = b0 == 0 ? 0ull : d_offsets[i0];  // where the launch's first item starts
+    uint64_t base = start0;
+    if (b0 == 0 && t == 0u) d_offsets[0] = 0;
     for (uint32_t j0 = 0; j0 < ni; j0 += 256u) {
-        const uint32_t j = j0 + threadIdx.x, i = i0 + (j < ni ? j : 0u);
+        const uint32_t j = j0 + t, i = i0 + (j < ni ? j : 0u);
         const bool valid = j < ni;
         const BatchItem it = valid ? items[i] : BatchItem{0, 0, 0, 0, 0, 0u, 0u};
-        const uint64_t at = valid ? batch_item_frames(it, run_at + i, b0, nb, sizes, ext, false, nullptr, 0, 0, nullptr) : 0ull;
-        const bool complete = valid && it.first_block + it.n_blocks <= b0 + nb;   // (only the launch's last item can be incomplete: it adds nothing)
+        const uint64_t first = it.first_block, end = first + it.n_blocks;
+        // (an item without blocks: no header either; the window holds no item with blocks that has none in the launch)
+        const bool has = it.n_blocks != 0u && first < launch_end && end > b0, begins = first >= b0;
+        const uint64_t carry = has && !begins ? run_at[i] : (uint64_t)kHeaderSize;
+        const uint64_t at = has ? carry + E[(end < launch_end ? end : launch_end) - b0] - E[begins ? first - b0 : 0u] : 0ull;
+        const bool complete = valid && end <= launch_end;    // (only the launch's last item can be incomplete: it adds nothing)
         uint64_t total;
         const uint64_t start = base + group_scan_excl64(complete ? (at + mask) & ~mask : 0ull, wave_sum, &total);
         base += total;
-        if (valid) {                                         // (no lane leaves the loop early: the scan above needs them all)
-            batch_item_frames(it, run_at + i, b0, nb, sizes, ext, true, out, start, out_size, frame_at);
-            run_at[i] = at;                                  // (only now: the writing pass has read the carry that the sizing pass read)
+        if (valid) {
+            if (has && begins && start + kHeaderSize <= out_size) write_header(out + start, it.n_blocks, it.in_len);
+            if (has && !begins) carry0 = carry;
+            run_at[i] = at;
         }
         if (complete) {
             const bool last = i + 1u == n_items, over = start + at > out_size;
@@ -108,23 +146,38 @@ __device__ __forceinline__ void batch_pack_scan_packed_body(const BatchItem* __r
             if (item_status && over && it.n_blocks != 0u) item_status[i] = kErrOverflow;
         }
     }
+    __syncthreads();                                         // (carry0, and the starts in d_offsets, for the lanes below)
+
+    for (uint32_t k = t; k < nb; k += 256u) {
+        const uint64_t b = b0 + k;
+        const uint32_t i = block_item[b], sz = sizes[k];
+        const uint64_t first = items[i].first_block;
+        const bool begins = first >= b0;
+        const uint64_t at = (i == i0 ? start0 : d_offsets[i]) + (begins ? (uint64_t)kHeaderSize : carry0) + E[k] - E[begins ? first - b0 : 0u];
+        const bool fits = at + kFrameWordSize + sz <= out_size;
+        if (fits) write_frame(out + at, sz, ext);
+        frame_at[k] = fits ? at : kNoFrame;
+        if (d_block_sizes) d_block_sizes[b] = sz;
+        if (sz > max_stream) atomicMax(status, kErrOverflow);
+    }
 }
 
-// The items [i0, i0 + ni) with blocks in the launch of the batch's blocks [b0, b0 + nb), found on the host.
-__global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0,
-                                                                     uint32_t ni, uint64_t b0, uint32_t nb,
-                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
-                                                                     uint8_t* __restrict__ out, uint64_t out_size,
+// The items [i0, i0 + ni) with blocks in the launch of the batch's blocks [b0, b0 + nb), found on the host
+// (tsqa_compress_batch_packed_async, tsqa_compress_batch_packed_split_async).
+__global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const BatchItem* __restrict__ items, uint32_t n_items, uint32_t i0, uint32_t ni,
+                                                                     uint64_t b0, uint32_t nb, const uint32_t* __restrict__ sizes,
+                                                                     const uint32_t* __restrict__ block_item, uint32_t ext, uint32_t align,
+                                                                     uint32_t max_stream, uint8_t* __restrict__ out, uint64_t out_size,
                                                                      uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
-                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
-                                                                     int32_t* __restrict__ status)
+                                                                     uint64_t* d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                     uint32_t* __restrict__ d_block_sizes, int32_t* __restrict__ status)
 {
-    batch_pack_scan_packed_body(items, n_items, i0, ni, b0, nb, sizes, ext, align, out, out_size, run_at, frame_at, d_offsets, d_sizes, nullptr,
-                                status);
+    batch_pack_scan_packed_body(items, n_items, i0, ni, b0, nb, sizes, block_item, ext, align, max_stream, out, out_size, run_at, frame_at,
+                                d_offsets, d_sizes, d_block_sizes, nullptr, status);
 }
 
-// batch_pack_scan_packed_kernel behind launch l (blocks [l * budget, (l + 1) * budget) of the batch) of a batch whose item table was
-// made on the device (tsqa_compress_batch_packed_tables_async): the launch's items are found here, not on the host.  The live blocks
+// The same behind launch l (blocks [l * budget, (l + 1) * budget) of the batch) of a batch whose item table was made on the device
+// (tsqa_compress_batch_packed_tables_async and its split form): the launch's items are found here, not on the host.  The live blocks
 // of the launch end at min((l + 1) * budget, *live_blocks); a launch past them has nothing to do and leaves, and the sizes and
 // frame places of the dead blocks of a live launch are never looked at.  launch_item[l] (batch_enc_blocks_kernel) is the item that
 // holds the launch's first block.  The items without blocks -- refused, or unfit for cap_blocks -- get their size 0 and carry
@@ -136,11 +189,13 @@ __global__ __launch_bounds__(256) void batch_pack_scan_packed_kernel(const Batch
 __global__ __launch_bounds__(256) void batch_pack_scan_tables_kernel(const BatchItem* __restrict__ items, uint32_t n_items,
                                                                      const uint32_t* __restrict__ launch_item, uint32_t l, uint32_t budget,
                                                                      const uint32_t* __restrict__ live_blocks,
-                                                                     const uint32_t* __restrict__ sizes, uint32_t ext, uint32_t align,
-                                                                     uint8_t* __restrict__ out, uint64_t out_size,
+                                                                     const uint32_t* __restrict__ sizes,
+                                                                     const uint32_t* __restrict__ block_item, uint32_t ext, uint32_t align,
+                                                                     uint32_t max_stream, uint8_t* __restrict__ out, uint64_t out_size,
                                                                      uint64_t* __restrict__ run_at, uint64_t* __restrict__ frame_at,
-                                                                     uint64_t* __restrict__ d_offsets, uint64_t* __restrict__ d_sizes,
-                                                                     int32_t* __restrict__ item_status, int32_t* __restrict__ status)
+                                                                     uint64_t* d_offsets, uint64_t* __restrict__ d_sizes,
+                                                                     uint32_t* __restrict__ d_block_sizes, int32_t* __restrict__ item_status,
+                                                                     int32_t* __restrict__ status)
 {
     const uint64_t live = *live_blocks, b0 = (uint64_t)l * budget;
     if (l != 0u && b0 >= live) return;                       // (the whole workgroup, before any barrier)
@@ -148,8 +203,8 @@ __global__ __launch_bounds__(256) void batch_pack_scan_tables_kernel(const Batch
     const uint32_t i0 = l != 0u ? launch_item[l] : 0u;
     uint32_t i1 = n_items;
     if (end < live) { const uint32_t e = launch_item[l + 1u]; i1 = e + (items[e].first_block < end ? 1u : 0u); }
-    batch_pack_scan_packed_body(items, n_items, i0, i1 - i0, b0, (uint32_t)(end - b0), sizes, ext, align, out, out_size, run_at, frame_at,
-                                d_offsets, d_sizes, item_status, status);
+    batch_pack_scan_packed_body(items, n_items, i0, i1 - i0, b0, (uint32_t)(end - b0), sizes, block_item, ext, align, max_stream, out, out_size,
+                                run_at, frame_at, d_offsets, d_sizes, d_block_sizes, item_status, status);
 }
 
 // Before batch_walk_kernel in the packed decompress calls: one lane per item takes its container's place from tables in
@@ -325,8 +380,8 @@ __global__ __launch_bounds__(256) void batch_layout_tables_kernel(BatchItem* __r
 // block_len bytes of its item from (b - first_block) * block_len on, or what is left of the item, and the look-ahead ends with the
 // item.  The block's item is the last one whose first_block is at or below b (the items without blocks in front of it share its
 // first_block; the ones behind it, and every unfit item, start past b), found by bisection in d_first_block; launch_item[l] = the
-// item that holds block l * budget, for batch_pack_scan_tables_kernel; block_item[b] (NULL: not wanted) = the block's item, for
-// the pack scan of short blocks (tsq_batch_split.cuh).  Lanes at or past *live_blocks leave: the descriptors and table entries of
+// item that holds block l * budget, for batch_pack_scan_tables_kernel; block_item[b] = the block's item, for step 3 of the pack
+// scan (batch_pack_scan_packed_body).  Lanes at or past *live_blocks leave: the descriptors and table entries of
 // dead blocks are never written and never read.
 __global__ __launch_bounds__(256) void batch_enc_blocks_kernel(const BatchItem* __restrict__ items, uint32_t n_items,
                                                                const uint64_t* __restrict__ d_first_block,

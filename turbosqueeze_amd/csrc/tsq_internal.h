@@ -117,11 +117,11 @@ struct tsqa_ctx {
     // the item table that tsqa_decompress_batch_packed_dense_async makes on the device, and the block count of its fitting items
     tsqa_scratch<tsq::BatchItem> batch_items;
     tsqa_scratch<uint32_t> batch_live;
-    // tsqa_compress_batch_packed_tables_async: the block descriptors it makes on the device (cap_blocks of them) and, per encode
-    // launch, the item that holds the launch's first block
+    // every packed compress, host-planned or from device tables: the block descriptors made on the device (batch_enc_blocks_kernel)
+    // and, per encode launch, the item that holds the launch's first block
     tsqa_scratch<tsq::EncBatchBlock> table_blocks;
     tsqa_scratch<uint32_t> table_launch_item;
-    // the packed batches of short blocks (tsq_batch_split.cuh): per block descriptor, the item it belongs to
+    // and, per block descriptor, the item it belongs to: step 3 of the pack scan (batch_pack_scan_packed_body) places each frame from it
     tsqa_scratch<uint32_t> table_block_item;
     // tsqa_join_async: where each item's body starts in the joined container (one more than items)
     tsqa_scratch<uint64_t> join_at;

@@ -8,7 +8,6 @@
 #include "tsq_internal.h"
 
 #include "tsq_batch.cuh"
-#include "tsq_batch_split.cuh"
 #include "tsq_common.cuh"
 #include "tsq_container.cuh"
 #include "tsq_format.h"
@@ -244,8 +243,8 @@ int tsqa_ctx::reserve_batch(size_t n_items)
            batch_live.grow(this, one) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
-// Scratch of the compress from device tables (tsq_internal.h): the block descriptors doubled from 256, the launch table from 16,
-// each on its own; want_items (the packed batches of short blocks): a word per block for its item, as many as descriptors.
+// Scratch of the calls whose block descriptors are made on the device (tsq_internal.h): the descriptors doubled from 256, the launch
+// table from 16, each on its own; want_items (every packed batch): a word per block for its item, as many as descriptors.
 int tsqa_ctx::reserve_tables(size_t n_blocks, size_t n_launches, bool want_items)
 {
     (void)hipSetDevice(device);
@@ -1239,12 +1238,18 @@ static int batch_route_enqueue(tsqa_ctx* c, const uint8_t* in, const EncBatchBlo
     return TSQA_OK;
 }
 
-// The launches of a compress batch whose arguments have been checked; first[] is its block plan (tsqa_plan_batch).  align == 0: the
-// caller's output ranges (tsqa_compress_batch_async).  align > 0: a packed batch (tsqa_compress_batch_packed_async): the items'
-// places are made on the device and land in d_offsets.
+// The items with blocks in the launch of blocks [b0, b0 + nb) of a batch planned on the host (first[]: its block plan, no item
+// without blocks): from *i0, the one that holds block b0, to the last that starts before b0 + nb.  Returns their count.
+static uint32_t launch_items(const std::vector<uint64_t>& first, uint32_t n_items, uint64_t b0, uint32_t nb, uint32_t* i0)
+{
+    *i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
+    return (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin()) - *i0;
+}
+
+// The launches of tsqa_compress_batch_async, whose arguments have been checked; first[] is its block plan (tsqa_plan_batch).  The
+// frames go into the caller's output ranges.
 static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batch_item* items, uint32_t n_items, const std::vector<uint64_t>& first,
-                                  uint32_t ext, void* d_out, size_t out_size, uint32_t align, uint64_t* d_offsets, uint64_t* d_sizes,
-                                  int32_t* d_status, hipStream_t s)
+                                  uint32_t ext, void* d_out, uint64_t* d_sizes, int32_t* d_status, hipStream_t s)
 {
     static_assert(sizeof(tsqa_batch_item) == 32 && sizeof(BatchItem) == 48 && sizeof(EncBatchBlock) == 24, "descriptor layouts");
     (void)hipSetDevice(c->device);
@@ -1260,7 +1265,7 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
     for (uint32_t i = 0; i < n_items; ++i) {
         const tsqa_batch_item& x = items[i];
         const uint32_t nb = (uint32_t)(first[i + 1] - first[i]);
-        hi[i] = align ? BatchItem{x.in_at, x.in_len, 0, 0, first[i], nb, 0u} : BatchItem{x.in_at, x.in_len, x.out_at, x.out_cap, first[i], nb, 0u};
+        hi[i] = BatchItem{x.in_at, x.in_len, x.out_at, x.out_cap, first[i], nb, 0u};
         for (uint32_t j = 0; j < nb; ++j) {
             const uint64_t b = first[i] + j, off = (uint64_t)j * kBlockSize, left = x.in_len - off;
             hb[b] = EncBatchBlock{x.in_at + off, left, left < kBlockSize ? (uint32_t)left : kBlockSize, (uint32_t)(b % budget)};
@@ -1273,15 +1278,10 @@ static int compress_batch_enqueue(tsqa_ctx* c, const void* d_in, const tsqa_batc
     TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     TSQ_HIP(c, up.send(bytes, s));
     const int rc = batch_route_enqueue(c, in, db, n_blocks, ext, pack_pieces(), out, nullptr, d_status, s, [&](uint64_t b0, uint32_t nb, uint32_t) {
-        // the items with blocks in this launch: from the one that holds block b0 to the last that starts before b0 + nb
-        const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
-        const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
-        if (align)
-            hipLaunchKernelGGL(batch_pack_scan_packed_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, c->sizes, ext, align, out,
-                               (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_status);
-        else
-            hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((i1 - i0 + 255u) / 256u), dim3(256), 0, s, di, i0, i1 - i0, b0, nb, c->sizes, ext, out,
-                               c->batch_at, c->frame_at, d_sizes, d_status);
+        uint32_t i0;
+        const uint32_t ni = launch_items(first, n_items, b0, nb, &i0);
+        hipLaunchKernelGGL(batch_pack_scan_kernel, dim3((ni + 255u) / 256u), dim3(256), 0, s, di, i0, ni, b0, nb, c->sizes, ext, out, c->batch_at,
+                           c->frame_at, d_sizes, d_status);
     });
     TSQ_HIP(c, up.commit(s));                            // (behind a refused launch too: those before it may still read the descriptors)
     if (rc) return rc;
@@ -1307,7 +1307,7 @@ extern "C" int tsqa_compress_batch_async(tsqa_ctx* c, const void* d_in, size_t i
     const char* why;
     if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanCompress)) { c->set_error("compress_batch: %s", why); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
-    return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, out_size, 0u, nullptr, d_sizes, d_status, s);
+    return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, d_sizes, d_status, s);
 }
 
 extern "C" int tsqa_compress_batch(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items, uint32_t ext,
@@ -1343,52 +1343,7 @@ extern "C" int tsqa_plan_packed(const uint64_t* sizes, uint32_t n_items, uint32_
     return TSQA_OK;
 }
 
-// Both packed compress forms: the argument checks, then the launches.  Nothing is reserved, enqueued or written before the checks
-// pass.  d_offsets, d_sizes: the caller's device tables, or NULL for the context's own (the synchronous form), reserved after the checks.
-static int compress_batch_packed_enqueue(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                                         uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
-                                         int32_t* d_status, hipStream_t s)
-{
-    if (!d_in || !d_out || !d_status || !items) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    if (!batch_encoder_ok(c, "compress_batch_packed")) return TSQA_ERR_ARG;
-    if (!packed_align_ok(align)) { c->set_error("compress_batch_packed: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
-    if (out_size < kHeaderSize) { c->set_error("compress_batch_packed: out_size holds less than a header"); return TSQA_ERR_ARG; }
-    if (n_items == 0) { c->set_error("compress_batch_packed: no items"); return TSQA_ERR_ARG; }
-    std::vector<uint64_t> first((size_t)n_items + 1);
-    const char* why;
-    if (plan_batch(items, n_items, in_size, out_size, nullptr, first.data(), &why, kPlanPacked)) { c->set_error("compress_batch_packed: %s", why); return TSQA_ERR_ARG; }
-    if (!d_offsets) {
-        if (int rc = c->reserve_batch(n_items)) return rc;
-        d_offsets = c->batch_offsets; d_sizes = c->batch_sizes;
-    }
-    return compress_batch_enqueue(c, d_in, items, n_items, first, ext, d_out, out_size, align, d_offsets, d_sizes, d_status, s);
-}
-
-extern "C" int tsqa_compress_batch_packed_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                                                uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets,
-                                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
-{
-    if (!c) return TSQA_ERR_ARG;
-    if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = stream_of(c, hip_stream);
-    return compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, d_offsets, d_sizes, d_status, s);
-}
-
-extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                                          uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes,
-                                          void* hip_stream)
-{
-    if (!c) return TSQA_ERR_ARG;
-    if (!offsets || !sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
-    hipStream_t s = stream_of(c, hip_stream);
-    int rc = compress_batch_packed_enqueue(c, d_in, in_size, items, n_items, ext, align, d_out, out_size, nullptr, nullptr, c->d_status, s);
-    if (rc) return rc;
-    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    return finish_sync(c, s, "compress_batch_packed");
-}
-
-// ---- packed batches of short blocks: every item cut every block_len bytes, the pack scan parallel over the launch's blocks ----
+// ---- the host-planned packed compress: every item cut every block_len bytes, TSQ_BLOCK_SZ or the caller's shorter one ----
 
 static bool split_block_len_ok(uint32_t block_len) { return block_len >= 4096u && block_len <= kBlockSize && (block_len & (block_len - 1u)) == 0u; }
 static uint32_t log2_of(uint32_t pow2) { uint32_t k = 0; while ((1u << k) < pow2) ++k; return k; }
@@ -1406,14 +1361,15 @@ extern "C" int tsqa_plan_batch_split(const tsqa_batch_item* items, uint32_t n_it
     return TSQA_OK;
 }
 
-// Both forms of the packed compress of short blocks: the checks of compress_batch_packed_enqueue and the block_len, then the
-// launches.  Only the item table, first_block and the block count are uploaded: the block descriptors and each block's item are
-// made on the device (batch_enc_blocks_kernel), as the compress from device tables makes them.
-static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
-                                               uint32_t ext, uint32_t align, uint32_t block_len, void* d_out, size_t out_size,
+// Every host-planned packed compress (`who`: the caller, for the error texts; block_len: kBlockSize for tsqa_compress_batch_packed*,
+// which cannot fail its check): the argument checks, then the launches.  Nothing is reserved, enqueued or written before the checks
+// pass.  d_offsets, d_sizes: the caller's device tables, or NULL for the context's own (the waiting forms).  Only the item table,
+// first_block and the block count are uploaded: the block descriptors and each block's item are made on the device
+// (batch_enc_blocks_kernel), as the compress from device tables makes them.
+static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const char* who, const void* d_in, size_t in_size, const tsqa_batch_item* items,
+                                               uint32_t n_items, uint32_t ext, uint32_t align, uint32_t block_len, void* d_out, size_t out_size,
                                                uint64_t* d_offsets, uint64_t* d_sizes, uint32_t* d_block_sizes, int32_t* d_status, hipStream_t s)
 {
-    const char* const who = "compress_batch_packed_split";
     if (!d_in || !d_out || !d_status || !items) { c->set_error("%s: null pointer", who); return TSQA_ERR_ARG; }
     if (!batch_encoder_ok(c, who)) return TSQA_ERR_ARG;
     if (!packed_align_ok(align)) { c->set_error("%s: align %u is not a power of two from 1 to 4096", who, align); return TSQA_ERR_ARG; }
@@ -1426,7 +1382,7 @@ static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const void* d_in, si
     (void)hipSetDevice(c->device);
     const uint64_t n_blocks = first[n_items];
     const uint32_t budget = batch_budget(c);
-    if (budget > kSplitScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kSplitScanBlocks); return TSQA_ERR_HIP; }
+    if (budget > kPackScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kPackScanBlocks); return TSQA_ERR_HIP; }
     const size_t item_bytes = (size_t)n_items * sizeof(BatchItem), first_bytes = ((size_t)n_items + 1) * sizeof(uint64_t);
     const size_t bytes = item_bytes + first_bytes + sizeof(uint32_t);
     tsqa_uploads::Slot up;
@@ -1447,13 +1403,12 @@ static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const void* d_in, si
     hipLaunchKernelGGL(batch_enc_blocks_kernel, dim3((uint32_t)((n_blocks + 255u) / 256u)), dim3(256), 0, s, di, n_items,
                        static_cast<const uint64_t*>(up.dev<uint64_t>(item_bytes)), static_cast<const uint32_t*>(up.dev<uint32_t>(item_bytes + first_bytes)),
                        budget, block_len, c->table_blocks, c->table_launch_item, c->table_block_item);
-    // (no stream of these blocks is longer than block_bound says: short blocks need few copy pieces)
+    // (no stream of these blocks is longer than block_bound says: short blocks need few copy pieces, full ones a slot's: kSlotSize)
     const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
     const int rc = batch_route_enqueue(c, in, c->table_blocks, n_blocks, ext, pack_pieces(max_stream), out, nullptr, d_status, s, [&](uint64_t b0, uint32_t nb, uint32_t) {
-        // the items with blocks in this launch, as compress_batch_enqueue finds them
-        const uint32_t i0 = (uint32_t)(std::upper_bound(first.begin(), first.end(), b0) - first.begin()) - 1u;
-        const uint32_t i1 = (uint32_t)(std::lower_bound(first.begin(), first.begin() + n_items, b0 + nb) - first.begin());
-        hipLaunchKernelGGL(batch_split_scan_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, i1 - i0, b0, nb, static_cast<const uint32_t*>(c->sizes),
+        uint32_t i0;
+        const uint32_t ni = launch_items(first, n_items, b0, nb, &i0);
+        hipLaunchKernelGGL(batch_pack_scan_packed_kernel, dim3(1), dim3(256), 0, s, di, n_items, i0, ni, b0, nb, static_cast<const uint32_t*>(c->sizes),
                            static_cast<const uint32_t*>(c->table_block_item), ext, align, max_stream, out, (uint64_t)out_size, c->batch_at, c->frame_at,
                            d_offsets, d_sizes, d_block_sizes, d_status);
     });
@@ -1461,6 +1416,38 @@ static int compress_batch_packed_split_enqueue(tsqa_ctx* c, const void* d_in, si
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
     return TSQA_OK;
+}
+
+// The waiting tail of the packed calls: the context's own offsets (n_items + 1) and sizes (n_items) back to the host.
+static int finish_packed_sync(tsqa_ctx* c, hipStream_t s, const char* what, uint32_t n_items, uint64_t* offsets, uint64_t* sizes)
+{
+    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    return finish_sync(c, s, what);
+}
+
+extern "C" int tsqa_compress_batch_packed_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                                uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets,
+                                                uint64_t* d_sizes, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    return compress_batch_packed_split_enqueue(c, "compress_batch_packed", d_in, in_size, items, n_items, ext, align, kBlockSize, d_out, out_size,
+                                               d_offsets, d_sizes, nullptr, d_status, s);
+}
+
+extern "C" int tsqa_compress_batch_packed(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
+                                          uint32_t ext, uint32_t align, void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes,
+                                          void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!offsets || !sizes) { c->set_error("compress_batch_packed: null pointer"); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    int rc = compress_batch_packed_split_enqueue(c, "compress_batch_packed", d_in, in_size, items, n_items, ext, align, kBlockSize, d_out, out_size,
+                                                 nullptr, nullptr, nullptr, c->d_status, s);
+    if (rc) return rc;
+    return finish_packed_sync(c, s, "compress_batch_packed", n_items, offsets, sizes);
 }
 
 extern "C" int tsqa_compress_batch_packed_split_async(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
@@ -1471,8 +1458,8 @@ extern "C" int tsqa_compress_batch_packed_split_async(tsqa_ctx* c, const void* d
     if (!c) return TSQA_ERR_ARG;
     if (!d_offsets || !d_sizes) { c->set_error("compress_batch_packed_split: null pointer"); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
-    return compress_batch_packed_split_enqueue(c, d_in, in_size, items, n_items, ext, align, block_len, d_out, out_size, d_offsets, d_sizes,
-                                               d_block_sizes, d_status, s);
+    return compress_batch_packed_split_enqueue(c, "compress_batch_packed_split", d_in, in_size, items, n_items, ext, align, block_len, d_out,
+                                               out_size, d_offsets, d_sizes, d_block_sizes, d_status, s);
 }
 
 extern "C" int tsqa_compress_batch_packed_split(tsqa_ctx* c, const void* d_in, size_t in_size, const tsqa_batch_item* items, uint32_t n_items,
@@ -1482,12 +1469,10 @@ extern "C" int tsqa_compress_batch_packed_split(tsqa_ctx* c, const void* d_in, s
     if (!c) return TSQA_ERR_ARG;
     if (!offsets || !sizes) { c->set_error("compress_batch_packed_split: null pointer"); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
-    int rc = compress_batch_packed_split_enqueue(c, d_in, in_size, items, n_items, ext, align, block_len, d_out, out_size, nullptr, nullptr,
-                                                 d_block_sizes, c->d_status, s);
+    int rc = compress_batch_packed_split_enqueue(c, "compress_batch_packed_split", d_in, in_size, items, n_items, ext, align, block_len, d_out,
+                                                 out_size, nullptr, nullptr, d_block_sizes, c->d_status, s);
     if (rc) return rc;
-    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_items + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_items * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    return finish_sync(c, s, "compress_batch_packed_split");
+    return finish_packed_sync(c, s, "compress_batch_packed_split", n_items, offsets, sizes);
 }
 
 // ---- packed compress whose item table is made on the device from tables in device memory ----
@@ -1535,8 +1520,7 @@ extern "C" int tsqa_plan_compress_tables_split(const uint64_t* in_offsets, const
     return plan_compress_tables(in_offsets, in_sizes, n_items, in_size, block_len, align, cap_blocks, first_block, item_status, bound, n_fit);
 }
 
-// tsqa_compress_batch_packed_tables_async (block_len == 0: blocks of TSQ_BLOCK_SZ, batch_pack_scan_tables_kernel, no size table) and
-// its split form (the pack scan of tsq_batch_split.cuh).
+// tsqa_compress_batch_packed_tables_async (block_len == 0: blocks of TSQ_BLOCK_SZ, no size table) and its split form.
 static int compress_tables_enqueue(tsqa_ctx* c, const char* who, const void* d_in, size_t in_size, const uint64_t* d_in_offsets,
                                    const uint64_t* d_in_sizes, uint32_t n_items, uint32_t cap_blocks, uint32_t ext, uint32_t align,
                                    uint32_t block_len, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
@@ -1561,11 +1545,11 @@ static int compress_tables_enqueue(tsqa_ctx* c, const char* who, const void* d_i
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     const uint32_t budget = batch_budget(c);             // (the launches are sized by cap_blocks, not by a planned count)
-    if (split && budget > kSplitScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kSplitScanBlocks); return TSQA_ERR_HIP; }
+    if (budget > kPackScanBlocks) { c->set_error("%s: %u blocks per launch, the pack scan takes %u", who, budget, kPackScanBlocks); return TSQA_ERR_HIP; }
     if (int rc = c->reserve_batch(n_items)) return rc;
     if (d_out) {
         if (int rc = c->reserve(cap_blocks < budget ? cap_blocks : budget, true, true, true)) return rc;
-        if (int rc = c->reserve_tables(cap_blocks, ((size_t)cap_blocks + budget - 1) / budget, split)) return rc;
+        if (int rc = c->reserve_tables(cap_blocks, ((size_t)cap_blocks + budget - 1) / budget, true)) return rc;
     }
     const dim3 per_item((uint32_t)(((uint64_t)n_items + 255u) / 256u));
     const uint32_t block_shift = log2_of(block_len);
@@ -1580,21 +1564,16 @@ static int compress_tables_enqueue(tsqa_ctx* c, const char* who, const void* d_i
     const uint32_t* const live = c->batch_live;
     hipLaunchKernelGGL(batch_enc_blocks_kernel, dim3((uint32_t)(((uint64_t)cap_blocks + 255u) / 256u)), dim3(256), 0, s, di, n_items,
                        static_cast<const uint64_t*>(d_first_block), live, budget, block_len, c->table_blocks, c->table_launch_item,
-                       split ? (uint32_t*)c->table_block_item : (uint32_t*)nullptr);
+                       c->table_block_item);
     const uint8_t* const in = static_cast<const uint8_t*>(d_in);
     uint8_t* const out = static_cast<uint8_t*>(d_out);
-    // (no stream of short blocks is longer than block_bound says: they need few copy pieces)
+    // (no stream is longer than block_bound says: short blocks need few copy pieces, full ones a slot's: kSlotSize)
     const uint32_t max_stream = (uint32_t)(block_bound(block_len) - kFrameWordSize);
     const int rc = batch_route_enqueue(c, in, c->table_blocks, cap_blocks, ext, pack_pieces(max_stream), out, live, d_status, s, [&](uint64_t, uint32_t, uint32_t launch) {
-        if (split)
-            hipLaunchKernelGGL(batch_split_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
-                               launch, budget, live, static_cast<const uint32_t*>(c->sizes), static_cast<const uint32_t*>(c->table_block_item), ext,
-                               align, max_stream, out, (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_block_sizes,
-                               d_item_status, d_status);
-        else
-            hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
-                               launch, budget, live, static_cast<const uint32_t*>(c->sizes), ext, align, out, (uint64_t)out_size, c->batch_at, c->frame_at,
-                               d_offsets, d_sizes, d_item_status, d_status);
+        hipLaunchKernelGGL(batch_pack_scan_tables_kernel, dim3(1), dim3(256), 0, s, di, n_items, static_cast<const uint32_t*>(c->table_launch_item),
+                           launch, budget, live, static_cast<const uint32_t*>(c->sizes), static_cast<const uint32_t*>(c->table_block_item), ext,
+                           align, max_stream, out, (uint64_t)out_size, c->batch_at, c->frame_at, d_offsets, d_sizes, d_block_sizes, d_item_status,
+                           d_status);
     });
     if (rc) return rc;
     TSQ_HIP(c, hipGetLastError());
@@ -1629,7 +1608,7 @@ extern "C" int tsqa_compress_batch_packed_tables_split_async(tsqa_ctx* c, const 
 
 extern "C" int tsqa_plan_split(size_t n, uint32_t block_len, uint32_t* n_blocks, size_t* bound)
 {
-    if (!n_blocks || !bound || n == 0 || block_len < 4096u || block_len > kBlockSize || (block_len & (block_len - 1u)) != 0u) return TSQA_ERR_ARG;
+    if (!n_blocks || !bound || n == 0 || !split_block_len_ok(block_len)) return TSQA_ERR_ARG;
     const uint64_t nb = (uint64_t)n / block_len + ((uint64_t)n % block_len != 0);
     if (nb > 0xFFFFFFFFull) return TSQA_ERR_ARG;
     *n_blocks = (uint32_t)nb;
