@@ -568,7 +568,7 @@ int tsqa_join(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint6
  *   shorter than 6 bytes or a block longer than TSQ_BLOCK_SZ.
  *
  * tsqa_cut_async: idx is an index of ONE item (tsqa_index_items(idx) == 1): tsqa_index_create, tsqa_index_create_sized*, or a batch
- * index of a single item made by tsqa_index_create_batch (one made by tsqa_index_create_packed* is refused whatever it holds).  d_first and d_count (n_ranges each) are tables in device memory; nothing is uploaded, nothing in them is
+ * index of a single item made by tsqa_index_create_batch (one made by tsqa_index_create_packed* is refused whatever it holds; tsqa_cut_items_async, below, takes every index).  d_first and d_count (n_ranges each) are tables in device memory; nothing is uploaded, nothing in them is
  * trusted, and ranges may overlap and repeat.  Per range k, on the device, all arithmetic in 64 bits:
  *   1. Gate: where the index carries a verdict (a sized index) and it is nonzero, every range gets TSQA_ERR_FORMAT, sizes, totals
  *      and offsets are all 0 and not one byte of d_out is written.
@@ -585,7 +585,7 @@ int tsqa_join(tsqa_ctx *ctx, const void *d_arena, size_t arena_size, const uint6
  *      largest item status.
  *   7. Measure only: d_out == NULL with out_size == 0: the tables are made, every accepted range reads TSQA_ERR_OVERFLOW.
  * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL index, table or status pointer (d_totals and, when
- * measuring, d_out may be NULL), n_ranges == 0, a bad align, an index of several items (they already are separate containers), a
+ * measuring, d_out may be NULL), n_ranges == 0, a bad align, an index of several items (tsqa_cut_items_async cuts those), a
  * NULL d_out with out_size != 0, a non-NULL d_out with out_size < 16, [d_out, d_out + out_size) overlapping the index's container,
  * n_ranges * (container bytes + 4096) >= 2^55.
  * The call must be ordered behind the index's creation, as reads are (a sized index: the same stream).  What it keeps per range
@@ -603,6 +603,55 @@ int tsqa_cut_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint64_t *d_first
 int tsqa_cut(tsqa_ctx *ctx, const tsqa_index *idx, const uint64_t *d_first, const uint64_t *d_count, uint32_t n_ranges,
              uint32_t align, void *d_out, size_t out_size, uint64_t *offsets, uint64_t *sizes, uint64_t *totals,
              int32_t *item_status, void *hip_stream);
+
+/*
+ * Take: items, and block ranges inside items, out of ANY index, each as a container of its own, at copy speed -- the cut with the
+ * item of every range named in device memory.  A batch of containers is filtered, shuffled, compacted or split into pages by a
+ * table of item numbers that a kernel has just made, with nothing decoded and no host read: packed compress -> index -> choose ->
+ * take -> join, dense decompress, index or gather, on one stream.  The output is a dense arena with the packed tables, as the cut's.
+ *
+ * idx: tsqa_index_create, tsqa_index_create_sized*, tsqa_index_create_batch, or tsqa_index_create_packed* fetched or not.
+ * d_items (n_ranges, device): the item of each range; NULL: item 0 for every range, which an index of one item allows.
+ * d_first, d_count (n_ranges each, device): block ranges counted from the item's own first block; both NULL: the whole item.
+ * Nothing is uploaded, nothing in the tables is trusted, ranges may overlap and repeat.  Per range k, on the device, in 64 bits:
+ *   1. Gate: tsqa_cut_async's rule 1.
+ *   2. Item: d_items[k] < tsqa_index_items(idx), and the item owns blocks.  A refused or unfit item owns none: TSQA_ERR_ARG for
+ *      the range, size 0, total 0, no room taken, nothing of it read.  An index of one item made without an item table owns all
+ *      its blocks.  For an index made on the device and not fetched the live block count is read on the device
+ *      (d_blocks_total[0]); descriptors from there to cap_blocks are never read.
+ *   3. Range: with nb = the item's blocks, count >= 1, first < nb and count <= nb - first (first + count is never formed), else
+ *      TSQA_ERR_ARG as above.  The whole-item form is first = 0, count = nb.
+ *   4. Size, layout, fit, status, measure only: tsqa_cut_async's rules 3 to 7, with the frames and totals of the item's blocks.
+ * The layout is made by three launches of which none waits for another (the cut's is ONE workgroup's scan, a pass per 256
+ * ranges); the tables are the ones tsqa_plan_cut_items makes, entry for entry.
+ * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL index, table or status pointer (d_items as above;
+ * d_totals and, when measuring, d_out may be NULL), exactly one of d_first / d_count NULL, d_items NULL with an index of several
+ * items, n_ranges == 0, a bad align, a NULL d_out with out_size != 0, a non-NULL d_out with out_size < 16, [d_out, d_out +
+ * out_size) overlapping the index's buffer (the container, or the whole arena of a batch index), n_ranges * (buffer bytes +
+ * 4096) >= 2^55.
+ * Ordering and scratch: as tsqa_cut_async (behind the index's creation on the same stream or an event; the scratch per range
+ * lives in the context and grows as the cut's).
+ * tsqa_cut_items: the same with host tables, filled after one wait, as tsqa_cut.  Returns the status.
+ * tsqa_plan_cut_items: host only, rules 2 to 4 from host tables.  frame_at (n_blocks + 1): boundaries whose differences inside an
+ *   item are its frames' bytes -- for one container tsqa_plan_cut's frame_at, for a batch the running sum of the healthy items'
+ *   frame bytes from 16 on --; out_start as tsqa_plan_cut; item_first_block (n_items + 1, non-decreasing, ending at or below
+ *   n_blocks; NULL for one item that owns every block); items, first, count: host copies of the device tables, NULL as there.
+ *   Fills what tsqa_plan_cut fills.  TSQA_ERR_ARG for what that refuses (n_blocks == 0 is allowed: every range is refused),
+ *   n_items == 0, one of first / count NULL, and items or item_first_block NULL with several items.
+ */
+int tsqa_plan_cut_items(const uint64_t *frame_at, const uint64_t *out_start, uint32_t n_blocks,
+                        const uint64_t *item_first_block, uint32_t n_items,
+                        const uint32_t *items, const uint64_t *first, const uint64_t *count, uint32_t n_ranges,
+                        uint32_t align, uint64_t out_size,
+                        uint64_t *offsets, uint64_t *sizes, uint64_t *totals, int32_t *item_status, uint32_t *n_fit);
+int tsqa_cut_items_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items,
+                         const uint64_t *d_first, const uint64_t *d_count, uint32_t n_ranges, uint32_t align,
+                         void *d_out, size_t out_size, uint64_t *d_offsets, uint64_t *d_sizes, uint64_t *d_totals,
+                         int32_t *d_item_status, int32_t *d_status, void *hip_stream);
+int tsqa_cut_items(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items,
+                   const uint64_t *d_first, const uint64_t *d_count, uint32_t n_ranges, uint32_t align,
+                   void *d_out, size_t out_size, uint64_t *offsets, uint64_t *sizes, uint64_t *totals,
+                   int32_t *item_status, void *hip_stream);
 
 /*
  * Short blocks: ONE container whose blocks are block_len bytes long instead of TSQ_BLOCK_SZ.  A job's speed follows its block
@@ -897,7 +946,8 @@ int tsqa_gather(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, c
  *   unfit items are TSQA_ERR_ARG.  On the host, tsqa_index_items answers n_items; tsqa_index_blocks, tsqa_index_total and
  *   tsqa_index_item_total answer 0 and tsqa_index_item_status TSQA_ERR_ARG: the host does not know yet.  The reads the host plans
  *   (tsqa_decompress_ranges*, tsqa_decompress_item_ranges*) return TSQA_ERR_ARG with a message that names tsqa_index_fetch, and
- *   tsqa_cut* refuses it as it refuses a batch index -- fetched or not, and an index of one item too.
+ *   tsqa_cut* refuses it as it refuses a batch index -- fetched or not, and an index of one item too.  tsqa_cut_items_async takes
+ *   it, fetched or not: items and their block ranges out of the batch, the live block count read on the device.
  * tsqa_index_fetch: copies the tables and the live descriptors to the host and waits for hip_stream (behind the creation).  From
  *   then on the index is a tsqa_index_create_batch index in every respect (tsqa_index_item_status may also read TSQA_ERR_ARG or
  *   TSQA_ERR_OVERFLOW).  TSQA_OK at once for an index whose tables the host already has.

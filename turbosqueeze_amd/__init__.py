@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     plan_compress_tables,
     plan_compress_tables_split,
     plan_cut,
+    plan_cut_items,
     plan_gather,
     plan_index_packed,
     plan_dense,

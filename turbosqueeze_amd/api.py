@@ -219,6 +219,12 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_cut_async.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.tsqa_cut.restype = C.c_int
     L.tsqa_cut.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.tsqa_plan_cut_items.restype = C.c_int
+    L.tsqa_plan_cut_items.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, u32p]
+    L.tsqa_cut_items_async.restype = C.c_int
+    L.tsqa_cut_items_async.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.tsqa_cut_items.restype = C.c_int
+    L.tsqa_cut_items.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_profile_read_gather.restype = C.c_int
     L.tsqa_profile_read_gather.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_plan_gather.restype = C.c_int
@@ -681,6 +687,34 @@ def plan_cut(frame_at, out_start, ranges, align: int = 16, out_size: int = 0):
     return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
 
 
+def plan_cut_items(frame_at, out_start, item_first_block, items, ranges, align: int = 16, out_size: int = 0):
+    """tsqa_plan_cut_items (host only): plan_cut through an index of several items.  frame_at: n_blocks + 1 boundaries whose
+    differences inside an item are its frames' bytes; item_first_block: n_items + 1, or None for one item that owns every block;
+    items: the item of each range, or None for item 0; ranges: (first, count) pairs counted from the item's own first block, or None
+    for whole items (then items names them).  -> what plan_cut gives.  Raises TsqError(3) when refused."""
+    import numpy as np
+    fa = np.ascontiguousarray(frame_at, dtype=np.uint64)
+    os_ = np.ascontiguousarray(out_start, dtype=np.uint64)
+    if len(fa) != len(os_) or len(fa) < 1:
+        raise TsqError(3, "tsqa_plan_cut_items takes n_blocks + 1 frame boundaries and as many block starts")
+    ifb = None if item_first_block is None else np.ascontiguousarray(item_first_block, dtype=np.uint64)
+    it = None if items is None else np.array([int(i) for i in items], dtype=np.uint32)
+    first = None if ranges is None else np.array([int(f) for f, _ in ranges], dtype=np.uint64)
+    count = None if ranges is None else np.array([int(n) for _, n in ranges], dtype=np.uint64)
+    if ranges is None and items is None:
+        raise TsqError(3, "tsqa_plan_cut_items: neither items nor ranges")
+    n = len(first) if first is not None else len(it)
+    offsets, sizes, totals = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    status, n_fit = np.zeros(max(n, 1), dtype=np.int32), C.c_uint32(0)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    rc = lib().tsqa_plan_cut_items(fa.ctypes.data, os_.ctypes.data, len(fa) - 1, ptr(ifb), 1 if ifb is None else len(ifb) - 1, ptr(it), ptr(first),
+                                   ptr(count), n, align, out_size, offsets.ctypes.data, sizes.ctypes.data, totals.ctypes.data, status.ctypes.data,
+                                   C.byref(n_fit))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_cut_items refused the arguments")
+    return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
+
+
 def plan_gather(out_start, item_first_block, items, offsets, lengths, align: int = 1, out_cap=None, cap_pieces=None):
     """tsqa_plan_gather (host only): the layout and the verdicts of a gather of the ranges [offsets[k], offsets[k] + lengths[k]) --
     of item items[k]'s data, or of the whole data when items is None -- out of an index with these block starts (out_start, as
@@ -782,7 +816,54 @@ class BatchIndex(RangeIndex):
 
     @property
     def cut(self):
-        raise AttributeError("a BatchIndex has no cut: its items already are separate containers")
+        # (RangeIndex.cut takes block ranges of ONE container; hasattr(batch_index, "cut") stays False, as callers may test it)
+        raise AttributeError("a BatchIndex has no cut of block ranges alone: cut_items names the item of every range")
+
+    def cut_items(self, d_items, d_first=None, d_count=None, align: int = 16, out=None) -> "PackedBatch":
+        """The take: item d_items[k] of the batch -- an int32 CUDA tensor, read as unsigned, or a list of ints -- or, with d_first
+        and d_count (int64 CUDA tensors), the blocks [d_first[k], d_first[k] + d_count[k]) of that item counted from its own first
+        block, each as a .tsq container of its own, packed in one arena at multiples of `align` (DeviceCodec.cut_items_async: the
+        frames are copied, nothing is decoded; items may repeat).  A DeviceBatchIndex takes it before fetch().  Without `out` the
+        take is measured first and an arena of exactly the bytes needed is made.  -> a PackedBatch as RangeIndex.cut gives, with the
+        device tables (d_offsets, d_sizes) beside the host's.  A nonzero status raises TsqError with the item statuses in the text
+        and in .item_status -- 3 for an item that does not exist, was refused or has no such blocks --; for an `out` that is too
+        small (6) .needed = the bytes a retry needs."""
+        codec, torch = self.codec, self.codec.torch
+        if not hasattr(d_items, "data_ptr"):
+            import numpy as np
+            d_items = torch.from_numpy(np.array([int(i) for i in d_items], dtype=np.uint32).view(np.int32)).to(codec.device)
+        n = int(d_items.numel())
+        for name, t, dtypes in (("d_items", d_items, (torch.int32, getattr(torch, "uint32", torch.int32))), ("d_first", d_first, (torch.int64,)),
+                                ("d_count", d_count, (torch.int64,))):
+            if t is not None and (t.dtype not in dtypes or t.device != codec.device or not t.is_contiguous() or t.numel() != n):
+                raise TsqError(3, f"{name} must be a contiguous {str(dtypes[0])[6:]} tensor of {n} entries on the codec's device")
+        if n == 0 or (d_first is None) != (d_count is None):
+            raise TsqError(3, "cut_items: no items, or only one of d_first and d_count")
+        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
+        d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
+
+        def call(room):
+            codec._join()
+            codec.cut_items_async(self, d_items, d_first, d_count, n, align, room, d_offsets, d_sizes, d_totals, d_status)
+            codec._join()
+            status, item_status = codec.status(), d_status.cpu().tolist()
+            needed = int(d_offsets[n].item())
+            refused = [st for st in item_status if st not in (0, 6)]
+            if status and (room is not None or refused):     # (measuring: every accepted range reads 6)
+                e = TsqError(max(refused) if refused else status, f"cut_items: item statuses {item_status[:64]}{' ...' if n > 64 else ''}")
+                e.item_status, e.needed = item_status, needed
+                raise e
+            return needed
+
+        if out is None:
+            out = torch.empty(max(call(None), 16), dtype=torch.uint8, device=codec.device)
+        used = call(out)
+        host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
+        batch = PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:])
+        batch.d_offsets, batch.d_sizes = d_offsets, d_sizes
+        return batch
 
     def item_total(self, i: int) -> int:
         return int(self.L.tsqa_index_item_total(self.h, i))
@@ -932,6 +1013,7 @@ class PackedBatch:
         # the tables in device memory, where the batch came with them (from_device); d_first_block: of a batch of short blocks
         self.d_offsets = self.d_sizes = self.d_first_block = None
         self._views = None
+        self._take_index = None                              # the device index that take() makes and keeps
         # the blocks of all items, where the host knows them: from first_block, from the plain compress (4 MiB blocks), or from the
         # headers once a batch from from_device has been measured; None otherwise (a cut's arena)
         self.n_blocks = first_block[-1] if first_block else None
@@ -1026,6 +1108,36 @@ class PackedBatch:
             cap_blocks = self.n_blocks
         return codec.index_packed_async(self.arena, self.d_offsets, self.d_sizes, n, max(int(cap_blocks), 1), self.block_len if sized else None,
                                         self.d_first_block if sized else None, self.d_block_sizes)
+
+    def take(self, d_items, align: int = 16, out=None, sync: bool = True) -> "PackedBatch":
+        """The items d_items[k] of this batch (an int32 CUDA tensor, read as unsigned, or a list of ints; in any order, with
+        repeats) as a new packed batch: BatchIndex.cut_items of whole items through the batch's device index, which is made on the
+        current stream when it is first needed (index(sync=False), with cap_blocks as that chooses it: a batch whose block count
+        the host does not know takes through an index of its own making, index(sync=False, cap_blocks=...).cut_items).  Nothing is decoded.
+        sync=False: nothing is waited for and nothing read on the host.  The output is `out`, or a new arena with room for every
+        selection without repeats (the source arena's bytes and align - 1 per item); -> a PackedBatch.from_device over it, with
+        .d_item_status (int32: 3 for an item that does not exist or was refused, 6 for one that did not fit), .d_totals and
+        d_offsets[n] = the room a retry needs; the largest item status lands in codec.status()."""
+        codec, torch = self.codec, self.codec.torch
+        if self._take_index is None:
+            self._take_index = self.index(sync=False)
+        index = self._take_index
+        if sync:
+            return index.cut_items(d_items, align=align, out=out)
+        if not hasattr(d_items, "data_ptr"):
+            import numpy as np
+            d_items = torch.from_numpy(np.array([int(i) for i in d_items], dtype=np.uint32).view(np.int32)).to(codec.device)
+        n = int(d_items.numel())
+        if n == 0:
+            raise TsqError(3, "take: no items")
+        if out is None:
+            out = torch.empty(max(int(self.arena.numel()) + n * (int(align) - 1), 16), dtype=torch.uint8, device=codec.device)
+        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
+        d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
+        codec.cut_items_async(index, d_items, None, None, n, align, out, d_offsets, d_sizes, d_totals, d_status)
+        batch = PackedBatch.from_device(codec, out, d_offsets, d_sizes)
+        batch.d_item_status, batch.d_totals = d_status, d_totals
+        return batch
 
     def join(self, out=None, block_sizes: bool = False):
         """The batch as ONE .tsq container whose data is the concatenation of the items' data (DeviceCodec.join of the views:
@@ -1587,6 +1699,19 @@ class DeviceCodec:
                                    out.data_ptr() if out is not None else None, out.numel() if out is not None else 0,
                                    d_offsets.data_ptr(), d_sizes.data_ptr(), d_totals.data_ptr() if d_totals is not None else None,
                                    d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def cut_items_async(self, index, d_items, d_first, d_count, n: int, align: int, out, d_offsets, d_sizes, d_totals, d_item_status) -> None:
+        """tsqa_cut_items_async on the current stream, nothing waited for and nothing about the ranges taken from the host: cut_async
+        through ANY index -- a BatchIndex or a DeviceBatchIndex, fetched or not, too -- with the item of range k in d_items[k] (an
+        int32 CUDA tensor, read as unsigned; None: item 0, for an index of one item) and d_first / d_count counted from the item's
+        own first block (both None: the whole item).  The output tables are cut_async's.  An item that does not exist or was
+        refused gets TSQA_ERR_ARG (3) as a range outside its item does.  The largest item status lands in status()."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self.L.tsqa_cut_items_async(self.h, index.h, ptr(d_items), ptr(d_first), ptr(d_count), int(n), int(align), ptr(out),
+                                         out.numel() if out is not None else 0, d_offsets.data_ptr(), d_sizes.data_ptr(), ptr(d_totals),
+                                         d_item_status.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 
