@@ -622,8 +622,8 @@ int tsqa_cut(tsqa_ctx *ctx, const tsqa_index *idx, const uint64_t *d_first, cons
  *   3. Range: with nb = the item's blocks, count >= 1, first < nb and count <= nb - first (first + count is never formed), else
  *      TSQA_ERR_ARG as above.  The whole-item form is first = 0, count = nb.
  *   4. Size, layout, fit, status, measure only: tsqa_cut_async's rules 3 to 7, with the frames and totals of the item's blocks.
- * The layout is made by three launches of which none waits for another (the cut's is ONE workgroup's scan, a pass per 256
- * ranges); the tables are the ones tsqa_plan_cut_items makes, entry for entry.
+ * The kernels are tsqa_cut_async's, which is this call through an index of one item with d_items NULL: the layout is made by
+ * three launches of which none waits for another, and the tables are the ones tsqa_plan_cut_items makes, entry for entry.
  * TSQA_ERR_ARG before anything is enqueued, with nothing written, for: a NULL index, table or status pointer (d_items as above;
  * d_totals and, when measuring, d_out may be NULL), exactly one of d_first / d_count NULL, d_items NULL with an index of several
  * items, n_ranges == 0, a bad align, a NULL d_out with out_size != 0, a non-NULL d_out with out_size < 16, [d_out, d_out +

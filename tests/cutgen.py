@@ -7,12 +7,15 @@ of include/turbosqueeze_amd.h:
 
 What is restated from the library, and must be re-derived when it changes there:
   walk         walk_frames (tsq_format.h), as tsqa_index_create keeps it: every frame's place and every block's output place
-  measure      cut_measure_kernel (tsq_cut.cuh): the gate, the range rule written without first + count, the size and the total
-  layout       cut_layout_kernel: tsqa_plan_packed's rule on the sizes, the fit against out_size, the largest status
+  measure      cut_measure_kernel (tsq_cut.cuh) for the one item of a container: the gate, the range rule written without
+               first + count, the size and the total
+  layout       cut_sum_kernel, cut_scan_kernel, cut_place_kernel: tsqa_plan_packed's rule on the sizes, the fit of every range
+               against out_size by itself, the largest status
   plan_cut     tsqa_plan_cut (tsq_runtime.hip): rules 2 to 5 from host tables, and n_fit
-  expect       the order of the three launches of tsqa_cut_async: what a refused index, a refused range and an unfit range leave
-  GROUP, WAVE, SPLIT   cut_layout_kernel is ONE workgroup of 256 threads (four wavefronts of 64) that takes the ranges 256 at a
-               time; group_scan_excl64 (tsq_container.cuh) sums v & 0xFFFFFF and v >> 24 apart
+  expect       the order of the launches of tsqa_cut_async: what a refused index, a refused range and an unfit range leave
+  GROUP, WAVE, SPLIT   cut_sum_kernel and cut_place_kernel take 256 ranges per workgroup (four wavefronts of 64): a group's places
+               are summed inside it, cut_scan_kernel -- ONE workgroup, 256 groups per pass -- turns the groups' sums into their
+               bases, and the place is base + own; group_scan_excl64 (tsq_container.cuh) sums v & 0xFFFFFF and v >> 24 apart
   WORD16       cut_emit_kernel moves 16-byte words cut at multiples of 16 of the destination address
 """
 from __future__ import annotations
@@ -71,7 +74,7 @@ def measure(frame_at, out_start, first: int, count: int):
 
 
 def layout(sizes, align: int):
-    """RE-DERIVE with cut_layout_kernel and tsqa_plan_packed -> offsets (n + 1): every place a multiple of align, the last entry
+    """RE-DERIVE with cut_sum_kernel, cut_scan_kernel, cut_place_kernel and tsqa_plan_packed -> offsets (n + 1): every place a multiple of align, the last entry
     not rounded"""
     at, out = 0, []
     for k, s in enumerate(sizes):
@@ -287,7 +290,7 @@ def seams(case: Case):
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------
 
-REFUSAL_AT = (0, 256, 299)          # of 300 ranges: the first, the first lane of the second pass, the last
+REFUSAL_AT = (0, 256, 299)          # of 300 ranges: the first, the first lane of the second group, the last
 REFUSALS = {"count_0": (5, 0), "first_is_n_blocks": (TINY_BLOCKS, 1), "one_block_too_many": (TINY_BLOCKS - 2, 3),
             "first_2_to_the_32": (1 << 32, 1), "count_2_to_the_63": (1, 1 << 63), "all_ones": (ALL_ONES, ALL_ONES)}
 

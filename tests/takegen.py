@@ -9,9 +9,9 @@ arena's bytes, by the rule of include/turbosqueeze_amd.h:
 What is restated from the library, and must be re-derived when it changes there:
   Index        what tsqa_index_create_batch and tsqa_index_create_packed* leave (tsq_index_packed.cuh), through packedindexgen's
                measure, fit, walk and close_up: which items are healthy, their first blocks, every live block's frame and output place
-  measure      take_measure_kernel (tsq_take.cuh): the gate, the item rule (an item that does not exist, was refused or is unfit owns
-               no blocks), the range rule of cut_measure_kernel inside the item without first + count, the size and the total
-  layout       take_sum_kernel, take_scan_kernel, take_place_kernel: tsqa_plan_packed's rule on the sizes (cutgen.layout), the fit
+  measure      cut_measure_kernel (tsq_cut.cuh): the gate, the item rule (an item that does not exist, was refused or is unfit owns
+               no blocks), the range rule (cutgen.measure) inside the item without first + count, the size and the total
+  layout       cut_sum_kernel, cut_scan_kernel, cut_place_kernel: tsqa_plan_packed's rule on the sizes (cutgen.layout), the fit
                of every range against out_size by itself, the largest status
   plan         tsqa_plan_cut_items (tsq_runtime.hip): the same from host tables, and n_fit
   expect       the order of the launches of tsqa_cut_items_async: what a refused index, a refused range and an unfit range leave
@@ -80,7 +80,7 @@ class Index:
 
 
 def measure(ix: Index, item: int, first, count):
-    """RE-DERIVE with take_measure_kernel -> (size, total, src_at, end_at, count) of an accepted range, None of a refused one.  item,
+    """RE-DERIVE with cut_measure_kernel -> (size, total, src_at, end_at, count) of an accepted range, None of a refused one.  item,
     first and count are any unsigned values; first and count None: the whole item; first + count is never formed."""
     if item >= ix.n_items:
         return None

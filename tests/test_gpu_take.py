@@ -320,17 +320,23 @@ def test_the_three_launches_lay_out_what_the_host_planner_does(tsq, codec, name)
 
 
 def test_through_one_container_the_take_is_the_cut(tsq, codec):
-    """tsqa_cut_async -- cut_layout_kernel, ONE workgroup -- and tsqa_cut_items_async -- the three launches -- on the same index and
-    the same ranges: the same tables and the same arena, for few ranges and for more than launch (b) takes in a pass"""
+    """tsqa_cut_async and tsqa_cut_items_async with d_items NULL on the same index and the same ranges: the same tables and the same
+    arena, for few ranges and for more than launch (b) takes in a pass.  Both calls run the same kernels, so each of them is also
+    held, entry for entry, to two sources that share nothing with the kernels: the host planner (tsqa_plan_cut) and cutgen's
+    pure-Python layout and containers; every byte of the fenced output outside a fitting container keeps its sentinel."""
     import torch
     case, cut = tk.single("tiny")
     idx = index_of(tsq, codec, case.batch, "plain")
     many = [cut.ranges[k % len(cut.ranges)] for k in range(tk.PASS + 1)]
     for ranges, align in ((cut.ranges, cut.align), (many, 1)):
         n = len(ranges)
+        model = cg.Case(f"tiny_{n}_ranges_through_both_calls", cut.source, ranges, align)
         d_first, d_count = u64_dev(f for f, _ in ranges), u64_dev(c for _, c in ranges)
         need = cg.plan_cut(cut.source.frame_at, cut.source.out_start, ranges, align, 1 << 62)[0][-1]
         for out_size in (need, need // 2, None):
+            e = model.expect(out_size or 0)
+            offsets, sizes, totals, status, n_fit = tsq.plan_cut(cut.source.frame_at, cut.source.out_start, ranges, align, out_size or 0)
+            assert (offsets, sizes, totals, status, n_fit) == (e["offsets"], e["sizes"], e["totals"], e["item_status"], e["n_fit"]), (n, out_size)
             a, b = Room(n, out_size), Room(n, out_size)
             torch.cuda.synchronize()
             rc = codec.L.tsqa_cut_async(codec.h, idx.h, d_first.data_ptr(), d_count.data_ptr(), n, align, a.out_ptr(), out_size or 0, a.offsets.ptr(),
@@ -344,6 +350,14 @@ def test_through_one_container_the_take_is_the_cut(tsq, codec):
                 assert torch.equal(ta.buf, tb.buf), (n, out_size)
             assert out_size is None or torch.equal(a.buf, b.buf), (n, out_size)
             assert a.word.values() == [OK if out_size == need else ERR_OVERFLOW]
+            for room, who in ((a, "tsqa_cut_async"), (b, "tsqa_cut_items_async")):
+                what = f"{who}, {n} ranges, out_size {out_size}"
+                check(model, room, e, what + ", against cutgen")
+                got = (room.offsets.values(), room.sizes.values(), room.totals.values(), room.item_status.values())
+                for name, table, owed in zip(("offsets", "sizes", "totals", "item_status"), got, (offsets, sizes, totals, status)):
+                    assert table == owed, f"{what}: d_{name} against tsqa_plan_cut {first_difference(table, owed)} (range, got, owed)"
+                assert room.word.values() == [max(status)], what
+                assert next((k for k, st in enumerate(got[3]) if st == ERR_OVERFLOW), n) == n_fit, what
     run(tsq, codec, case, case.need, "a plain index, item 0 named", idx=idx)
 
 

@@ -10,7 +10,7 @@ the maximum kept.  One JSON line per shape, printed and appended to --out (profi
   B   the same container cut into 4 096 ranges of 4 blocks: a seam every tenth piece or so
   C   64 MiB of text at block_len 2^12 cut into 16 384 ranges of one block: several seams in every piece
 
-  cut_ms         the whole call: three launches, through a sized index made before
+  cut_ms         the whole call: five launches, through a sized index made before
   emit_ms        its copy kernel alone (tsqa_profile_read_cut: events around that one launch, in runs of their own)
   copy_ms        tsqa_measure_copy's kernel on as many bytes as the cut's arena has, in the same process: its median rate turned into
                  the time for those bytes; emit_over_copy_rate is the ratio of the two rates

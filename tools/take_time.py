@@ -16,9 +16,9 @@ median of --reps with the minimum and the maximum kept.  One JSON line per shape
   layout_ms          the call with no output: the measure and the three layout launches
   copy_ms            tsqa_measure_copy's median rate turned into the time for the taken arena's bytes
   recompress_ms      the decode route, both calls enqueued with no host wait between them
-  one_group_*        the layout alone on ONE container (64 MiB at block_len 2^12) with as many one-block ranges as the shape has:
-                     tsqa_cut_async -- cut_layout_kernel, one workgroup, a pass per 256 ranges -- against tsqa_cut_items_async --
-                     three launches --, both measuring only, alternating
+
+The lines of profiles/take_time.jsonl also hold one_group_* / three_launch_* fields: the layout alone through tsqa_cut_async, which
+then had a one-workgroup layout kernel of its own, against these three launches.  That kernel is gone and both calls share the three.
 """
 import argparse
 import ctypes as C
@@ -193,39 +193,6 @@ def main():
     rr = timed(recompress)
     differing = int((r_sizes != t_sizes).sum().item())
 
-    # the two layouts alone, on one container: as many one-block ranges as the shape has, measuring only, alternating
-    side_total, side_len = 64 << 20, 1 << 12
-    side_nb = side_total // side_len
-    side_src = src[:side_total] if total >= side_total else torch.from_numpy(tsq.synth.text(side_total, seed=6)).cuda()
-    blob = torch.empty(tsq.plan_split(side_total, side_len)[1], dtype=torch.uint8, device="cuda")
-    side_table = i32(side_nb)
-    codec.compress_split_async(side_src, ext, side_len, blob, side_table)
-    s.synchronize()
-    assert codec.last_size_status()[1] == 0
-    side = codec.index_sized(blob, side_total, side_len, side_table, sync=False)
-    s_first = torch.arange(n, dtype=torch.int64, device="cuda") % side_nb
-    s_count = torch.ones(n, dtype=torch.int64, device="cuda")
-    o1, o3 = i64(n + 1), i64(n + 1)
-
-    def one_group():
-        rc = L.tsqa_cut_async(codec.h, side.h, s_first.data_ptr(), s_count.data_ptr(), n, align, None, 0, o1.data_ptr(), t_sizes.data_ptr(), None,
-                              t_status.data_ptr(), t_word.data_ptr(), hs)
-        assert rc == 0, codec.last_error()
-
-    def three_launches():
-        rc = L.tsqa_cut_items_async(codec.h, side.h, None, s_first.data_ptr(), s_count.data_ptr(), n, align, None, 0, o3.data_ptr(), t_sizes.data_ptr(),
-                                    None, t_status.data_ptr(), t_word.data_ptr(), hs)
-        assert rc == 0, codec.last_error()
-
-    l1, l3 = [], []
-    for r in range(args.warmup + args.reps):
-        for call, times in ((one_group, l1), (three_launches, l3)):
-            got = timed_once(torch, s, call)
-            if r >= args.warmup:
-                times.append(got)
-    s.synchronize()
-    layouts_agree = bool(torch.equal(o1, o3))
-
     res = {"shape": name, "items": n_items, "item_bytes": item_len, "block_len": block_len, "ranges": n, "blocks_per_range": blocks_taken // n,
            "arena_bytes": arena_bytes, "taken_arena_bytes": need, "taken_data_bytes": taken_bytes, "reps": args.reps,
            "take_ms": med(t), "take_spread_ms": spread(t), "emit_ms": med(emit), "emit_spread_ms": spread(emit),
@@ -234,24 +201,12 @@ def main():
            "copy_probe_shape": codec.copy_probe_shape(), "emit_over_copy_rate": round(emit_gbps / median, 3),
            "recompress_ms": med(rr), "recompress_spread_ms": spread(rr), "recompress_over_take": round(statistics.median(rr) / statistics.median(t), 1),
            "recompressed_containers_of_another_size": differing,
-           "one_group_layout_ms": med(l1), "one_group_layout_spread_ms": spread(l1), "three_launch_layout_ms": med(l3),
-           "three_launch_layout_spread_ms": spread(l3), "one_group_over_three_launches": round(statistics.median(l1) / statistics.median(l3), 2),
-           "layouts_agree": layouts_agree, "take_decodes_to_the_chosen_data": ok, "recompress_route_ran_clean": same}
+           "take_decodes_to_the_chosen_data": ok, "recompress_route_ran_clean": same}
     line = json.dumps(res)
     print(line, flush=True)
     with open(args.out, "a") as f:
         f.write(line + "\n")
-    side.close()
     index.close()
-
-
-def timed_once(torch, s, call):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    call()
-    e1.record(s)
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 if __name__ == "__main__":

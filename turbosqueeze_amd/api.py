@@ -332,6 +332,36 @@ def plan_ranges(out_start, ranges, out_cap: int, cap_items=None):
     return [(items[k].block, items[k].lo, items[k].hi, items[k].out_at) for k in range(n.value)]
 
 
+def _cut_packed(codec, who: str, n: int, out, enqueue):
+    """What RangeIndex.cut and BatchIndex.cut_items share: enqueue(room, d_offsets, d_sizes, d_totals, d_status) is the async call
+    for n ranges, room None to measure.  Without `out` it measures first and makes the arena.  -> (the PackedBatch, d_offsets,
+    d_sizes); a nonzero status raises TsqError with .item_status and .needed."""
+    torch = codec.torch
+    if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
+        raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+    i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
+    d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
+
+    def call(room):
+        codec._join()
+        enqueue(room, d_offsets, d_sizes, d_totals, d_status)
+        codec._join()
+        status, item_status = codec.status(), d_status.cpu().tolist()
+        needed = int(d_offsets[n].item())
+        refused = [st for st in item_status if st not in (0, 6)]
+        if status and (room is not None or refused):         # (measuring: every accepted range reads 6)
+            e = TsqError(max(refused) if refused else status, f"{who}: item statuses {item_status[:64]}{' ...' if n > 64 else ''}")
+            e.item_status, e.needed = item_status, needed
+            raise e
+        return needed
+
+    if out is None:
+        out = torch.empty(max(call(None), 16), dtype=torch.uint8, device=codec.device)
+    used = call(out)
+    host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
+    return PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:]), d_offsets, d_sizes
+
+
 class RangeIndex:
     """The frame table of a device-resident .tsq container (tsqa_index_create), for reads of byte ranges of its uncompressed data.
     Holds a reference to the container tensor, which must not change while the index is used."""
@@ -419,29 +449,7 @@ class RangeIndex:
             table = np.array([[int(f) for f, _ in ranges], [int(n) for _, n in ranges]], dtype=np.uint64).view(np.int64)
             d_first, d_count = torch.from_numpy(table).to(codec.device)
         n = int(d_first.numel())
-        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
-            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
-        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
-        d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
-
-        def call(room):
-            codec._join()
-            codec.cut_async(self, d_first, d_count, n, align, room, d_offsets, d_sizes, d_totals, d_status)
-            codec._join()
-            status, item_status = codec.status(), d_status.cpu().tolist()
-            needed = int(d_offsets[n].item())
-            refused = [st for st in item_status if st not in (0, 6)]
-            if status and (room is not None or refused):     # (measuring: every accepted range reads 6)
-                e = TsqError(max(refused) if refused else status, f"cut: item statuses {item_status[:64]}{' ...' if n > 64 else ''}")
-                e.item_status, e.needed = item_status, needed
-                raise e
-            return needed
-
-        if out is None:
-            out = torch.empty(max(call(None), 16), dtype=torch.uint8, device=codec.device)
-        used = call(out)
-        host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
-        return PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:])
+        return _cut_packed(codec, "cut", n, out, lambda room, *tables: codec.cut_async(self, d_first, d_count, n, align, room, *tables))[0]
 
     def _gather(self, d_items, d_offsets, d_lengths, align, out, cap_pieces, range_status):
         codec, torch = self.codec, self.codec.torch
@@ -671,19 +679,25 @@ def plan_cut(frame_at, out_start, ranges, align: int = 16, out_size: int = 0):
     it) -> (offsets, then the bytes needed; sizes; totals; item_status: 0, 3 for a range outside the container, 6 for an accepted
     range that does not fit out_size; n_fit).  Raises TsqError(3) when refused."""
     import numpy as np
-    fa = np.ascontiguousarray(frame_at, dtype=np.uint64)
-    os_ = np.ascontiguousarray(out_start, dtype=np.uint64)
     first = np.array([int(f) for f, _ in ranges], dtype=np.uint64)
     count = np.array([int(n) for _, n in ranges], dtype=np.uint64)
-    n = len(first)
+    return _plan_cut("tsqa_plan_cut", frame_at, out_start, (first, count), len(first), align, out_size)
+
+
+def _plan_cut(name: str, frame_at, out_start, tables, n: int, align: int, out_size: int):
+    """What plan_cut and plan_cut_items share: the planner `name` of the C ABI over n ranges.  tables: what it takes between n_blocks
+    and n_ranges, numpy arrays (or None) passed by address and ints as they are."""
+    import numpy as np
+    fa = np.ascontiguousarray(frame_at, dtype=np.uint64)
+    os_ = np.ascontiguousarray(out_start, dtype=np.uint64)
+    if len(fa) != len(os_) or len(fa) < 1:
+        raise TsqError(3, f"{name} takes n_blocks + 1 frame boundaries and as many block starts")
     offsets, sizes, totals = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
     status, n_fit = np.zeros(max(n, 1), dtype=np.int32), C.c_uint32(0)
-    if len(fa) != len(os_) or len(fa) < 1:
-        raise TsqError(3, "tsqa_plan_cut takes n_blocks + 1 frame boundaries and as many block starts")
-    rc = lib().tsqa_plan_cut(fa.ctypes.data, os_.ctypes.data, len(fa) - 1, first.ctypes.data, count.ctypes.data, n, align, out_size,
-                             offsets.ctypes.data, sizes.ctypes.data, totals.ctypes.data, status.ctypes.data, C.byref(n_fit))
+    rc = getattr(lib(), name)(fa.ctypes.data, os_.ctypes.data, len(fa) - 1, *(a.ctypes.data if hasattr(a, "ctypes") else a for a in tables),
+                              n, align, out_size, offsets.ctypes.data, sizes.ctypes.data, totals.ctypes.data, status.ctypes.data, C.byref(n_fit))
     if rc:
-        raise TsqError(rc, "tsqa_plan_cut refused the arguments")
+        raise TsqError(rc, f"{name} refused the arguments")
     return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
 
 
@@ -693,26 +707,14 @@ def plan_cut_items(frame_at, out_start, item_first_block, items, ranges, align: 
     items: the item of each range, or None for item 0; ranges: (first, count) pairs counted from the item's own first block, or None
     for whole items (then items names them).  -> what plan_cut gives.  Raises TsqError(3) when refused."""
     import numpy as np
-    fa = np.ascontiguousarray(frame_at, dtype=np.uint64)
-    os_ = np.ascontiguousarray(out_start, dtype=np.uint64)
-    if len(fa) != len(os_) or len(fa) < 1:
-        raise TsqError(3, "tsqa_plan_cut_items takes n_blocks + 1 frame boundaries and as many block starts")
     ifb = None if item_first_block is None else np.ascontiguousarray(item_first_block, dtype=np.uint64)
     it = None if items is None else np.array([int(i) for i in items], dtype=np.uint32)
     first = None if ranges is None else np.array([int(f) for f, _ in ranges], dtype=np.uint64)
     count = None if ranges is None else np.array([int(n) for _, n in ranges], dtype=np.uint64)
     if ranges is None and items is None:
         raise TsqError(3, "tsqa_plan_cut_items: neither items nor ranges")
-    n = len(first) if first is not None else len(it)
-    offsets, sizes, totals = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
-    status, n_fit = np.zeros(max(n, 1), dtype=np.int32), C.c_uint32(0)
-    ptr = lambda a: a.ctypes.data if a is not None else None
-    rc = lib().tsqa_plan_cut_items(fa.ctypes.data, os_.ctypes.data, len(fa) - 1, ptr(ifb), 1 if ifb is None else len(ifb) - 1, ptr(it), ptr(first),
-                                   ptr(count), n, align, out_size, offsets.ctypes.data, sizes.ctypes.data, totals.ctypes.data, status.ctypes.data,
-                                   C.byref(n_fit))
-    if rc:
-        raise TsqError(rc, "tsqa_plan_cut_items refused the arguments")
-    return [int(x) for x in offsets], [int(x) for x in sizes[:n]], [int(x) for x in totals[:n]], [int(x) for x in status[:n]], int(n_fit.value)
+    return _plan_cut("tsqa_plan_cut_items", frame_at, out_start, (ifb, 1 if ifb is None else len(ifb) - 1, it, first, count),
+                     len(first) if first is not None else len(it), align, out_size)
 
 
 def plan_gather(out_start, item_first_block, items, offsets, lengths, align: int = 1, out_cap=None, cap_pieces=None):
@@ -839,29 +841,8 @@ class BatchIndex(RangeIndex):
                 raise TsqError(3, f"{name} must be a contiguous {str(dtypes[0])[6:]} tensor of {n} entries on the codec's device")
         if n == 0 or (d_first is None) != (d_count is None):
             raise TsqError(3, "cut_items: no items, or only one of d_first and d_count")
-        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
-            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
-        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=codec.device)
-        d_offsets, d_sizes, d_totals, d_status = i64(n + 1), i64(n), i64(n), torch.empty(n, dtype=torch.int32, device=codec.device)
-
-        def call(room):
-            codec._join()
-            codec.cut_items_async(self, d_items, d_first, d_count, n, align, room, d_offsets, d_sizes, d_totals, d_status)
-            codec._join()
-            status, item_status = codec.status(), d_status.cpu().tolist()
-            needed = int(d_offsets[n].item())
-            refused = [st for st in item_status if st not in (0, 6)]
-            if status and (room is not None or refused):     # (measuring: every accepted range reads 6)
-                e = TsqError(max(refused) if refused else status, f"cut_items: item statuses {item_status[:64]}{' ...' if n > 64 else ''}")
-                e.item_status, e.needed = item_status, needed
-                raise e
-            return needed
-
-        if out is None:
-            out = torch.empty(max(call(None), 16), dtype=torch.uint8, device=codec.device)
-        used = call(out)
-        host = torch.cat([d_offsets, d_sizes, d_totals]).cpu().tolist()
-        batch = PackedBatch(codec, out[:used], host[:n + 1], host[n + 1:2 * n + 1], host[2 * n + 1:])
+        batch, d_offsets, d_sizes = _cut_packed(
+            codec, "cut_items", n, out, lambda room, *tables: codec.cut_items_async(self, d_items, d_first, d_count, n, align, room, *tables))
         batch.d_offsets, batch.d_sizes = d_offsets, d_sizes
         return batch
 

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void gather_measure_kernel(const FrameInfo* __
 }
 
 // Behind gather_measure_kernel: tsqa_plan_packed's rule applied to the accepted ranges' lengths, and the piece numbers.  ONE
-// workgroup of exactly 256 threads, 256 ranges per pass, as cut_layout_kernel walks them, with two sums carried: round_up(length,
+// workgroup of exactly 256 threads, 256 ranges per pass as cut_scan_kernel takes its groups, with two sums carried: round_up(length,
 // align) -- every place is a multiple of align, and the last length is not rounded -- and the piece counts.  A refused range counts
 // as nothing.  The places are complete whatever fits.  An accepted range fits when its bytes end at or before out_cap and its pieces
 // at or before cap_pieces (one without bytes asks for neither); both sums only grow, so the fitting ranges are a prefix of the

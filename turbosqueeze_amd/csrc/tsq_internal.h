@@ -125,10 +125,10 @@ struct tsqa_ctx {
     tsqa_scratch<uint32_t> table_block_item;
     // tsqa_join_async: where each item's body starts in the joined container (one more than items)
     tsqa_scratch<uint64_t> join_at;
-    // tsqa_cut_async: per range its source place and its header's fields (one more than ranges: where the written output ends)
+    // tsqa_cut_async and tsqa_cut_items_async (tsq_cut.cuh): per range its source place and its header's fields (one more than
+    // ranges: where the written output ends), and per group of 256 ranges the sum of its padded sizes, then its base
     tsqa_scratch<tsq::CutRange> cut_ranges;
-    // tsqa_cut_items_async (tsq_take.cuh): cut_ranges, and per group of 256 ranges the sum of its padded sizes, then its base
-    tsqa_scratch<uint64_t> take_groups;
+    tsqa_scratch<uint64_t> cut_groups;
     // tsqa_gather_async (tsq_gather.cuh): per range its place and piece count; per piece slot -- cap_pieces of them -- the item as
     // it is cut and as it is sorted (two halves of gather_items), the key and the slot number in front of and behind the sort (two
     // halves each); one group per block that can be touched; the sort's temporary storage, asked for gather_sort_n pairs; the words
@@ -168,7 +168,6 @@ struct tsqa_ctx {
     int reserve_tables(size_t n_blocks, size_t n_launches, bool want_items = false);
     int reserve_join(size_t n_items);
     int reserve_cut(size_t n_ranges);
-    int reserve_take(size_t n_ranges);
     int reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);

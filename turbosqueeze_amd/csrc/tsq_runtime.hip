@@ -17,7 +17,6 @@
 #include "tsq_index_packed.cuh"
 #include "tsq_join.cuh"
 #include "tsq_cut.cuh"
-#include "tsq_take.cuh"
 #include "tsq_launch.cuh"
 #include "tsq_gather.cuh"
 #include "tsq_gather_sort.h"
@@ -265,24 +264,15 @@ int tsqa_ctx::reserve_join(size_t n_items)
     return join_at.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
-// Scratch of the cut (tsq_internal.h): one entry per range and one more, doubled from 256 ranges as the join's grows.
+// Scratch of the cut (tsq_internal.h): one entry per range and one more, doubled from 256 ranges as the join's grows, and one word
+// per group of 256 ranges, doubled with them.
 int tsqa_ctx::reserve_cut(size_t n_ranges)
 {
     (void)hipSetDevice(device);
-    const size_t want = doubled(256, n_ranges) + 1;
-    if (!cut_ranges.needs(want)) return TSQA_OK;
+    const size_t ranges = doubled(256, n_ranges) + 1, groups = doubled(256, n_ranges) / 256;
+    if (!cut_ranges.needs(ranges) && !cut_groups.needs(groups)) return TSQA_OK;
     (void)hipDeviceSynchronize();                        // (as in reserve_batch)
-    return cut_ranges.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
-}
-
-// Scratch of the take (tsq_internal.h): the cut's entries per range, and one word per group of 256 ranges, doubled with them.
-int tsqa_ctx::reserve_take(size_t n_ranges)
-{
-    if (int rc = reserve_cut(n_ranges)) return rc;
-    const size_t want = doubled(256, n_ranges) / 256;
-    if (!take_groups.needs(want)) return TSQA_OK;
-    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
-    return take_groups.grow(this, want) ? TSQA_OK : TSQA_ERR_HIP;
+    return cut_ranges.grow(this, ranges) && cut_groups.grow(this, groups) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
 // Scratch of the gather (tsq_internal.h): the ranges doubled from 256 as the cut's, the piece slots and groups as many as the call
@@ -1954,100 +1944,18 @@ extern "C" int tsqa_join(tsqa_ctx* c, const void* d_arena, size_t arena_size, co
     return rc;
 }
 
-// ---- cut: block ranges of an indexed container, each as a container of its own, nothing decoded (tsq_cut.cuh) ----
+// ---- cut and take: block ranges of an indexed container, or of the items of any index, each as a container of its own, nothing
+// decoded (tsq_cut.cuh) ----
 
+// One container is one item that owns [0, n_blocks); the cut names its ranges and has blocks to cut them from.
 extern "C" int tsqa_plan_cut(const uint64_t* frame_at, const uint64_t* out_start, uint32_t n_blocks, const uint64_t* first, const uint64_t* count,
                              uint32_t n_ranges, uint32_t align, uint64_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals,
                              int32_t* item_status, uint32_t* n_fit)
 {
-    if (!frame_at || !out_start || !first || !count || !offsets || !sizes || !item_status || !n_fit || n_blocks == 0 || n_ranges == 0 ||
-        !packed_align_ok(align)) return TSQA_ERR_ARG;
-    if (frame_at[0] < kHeaderSize) return TSQA_ERR_ARG;
-    for (uint32_t b = 0; b < n_blocks; ++b)
-        if (frame_at[b + 1] < frame_at[b] || frame_at[b + 1] - frame_at[b] < kMinFrameSize || out_start[b + 1] < out_start[b] ||
-            out_start[b + 1] - out_start[b] > kBlockSize) return TSQA_ERR_ARG;
-    const uint64_t mask = (uint64_t)align - 1;
-    uint64_t at = 0;
-    uint32_t fit = n_ranges;
-    for (uint32_t k = 0; k < n_ranges; ++k) {
-        const uint64_t f = first[k], n = count[k];
-        const bool ok = n >= 1 && f < n_blocks && n <= n_blocks - f;
-        const uint64_t size = ok ? kHeaderSize + frame_at[f + n] - frame_at[f] : 0;
-        offsets[k] = at; sizes[k] = size;
-        if (totals) totals[k] = ok ? out_start[f + n] - out_start[f] : 0;
-        const bool fits = ok && size <= out_size && at <= out_size - size;
-        if (ok && !fits && fit == n_ranges) fit = k;
-        item_status[k] = !ok ? TSQA_ERR_ARG : fits ? TSQA_OK : TSQA_ERR_OVERFLOW;
-        at += size;
-        if (k + 1 < n_ranges) at = (at + mask) & ~mask;
-    }
-    offsets[n_ranges] = at;
-    *n_fit = fit;
-    return TSQA_OK;
+    if (!first || !count || n_blocks == 0) return TSQA_ERR_ARG;
+    return tsqa_plan_cut_items(frame_at, out_start, n_blocks, nullptr, 1, nullptr, first, count, n_ranges, align, out_size, offsets, sizes, totals,
+                               item_status, n_fit);
 }
-
-extern "C" int tsqa_cut_async(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges,
-                              uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes, uint64_t* d_totals,
-                              int32_t* d_item_status, int32_t* d_status, void* hip_stream)
-{
-    if (!c) return TSQA_ERR_ARG;
-    if (!idx || !d_first || !d_count || !d_offsets || !d_sizes || !d_item_status || !d_status) { c->set_error("cut: null pointer"); return TSQA_ERR_ARG; }
-    if (idx->device != c->device) { c->set_error("cut: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
-    if (n_ranges == 0) { c->set_error("cut: no ranges"); return TSQA_ERR_ARG; }
-    if (!packed_align_ok(align)) { c->set_error("cut: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
-    // (fetched or not, and of one item too: its descriptors count from the arena's start, not from a container's)
-    if (idx->d_words) { c->set_error("cut: a batch index made on the device; its items already are separate containers"); return TSQA_ERR_ARG; }
-    if (idx->item_status.size() != 1) { c->set_error("cut: an index of %zu items; its items already are separate containers", idx->item_status.size()); return TSQA_ERR_ARG; }
-    if (d_out ? out_size < kHeaderSize : out_size != 0) {
-        c->set_error("cut: an output needs out_size of at least 16; measuring takes d_out NULL and out_size 0");
-        return TSQA_ERR_ARG;
-    }
-    {
-        const uintptr_t a = (uintptr_t)idx->container, o = (uintptr_t)d_out;
-        if (d_out && o < a + idx->n && a < o + out_size) { c->set_error("cut: the output overlaps the index's container"); return TSQA_ERR_ARG; }
-    }
-    // (the sizes go through group_scan_excl64, whose sums stay below 2^55; one source byte may be counted once per range)
-    if ((unsigned __int128)n_ranges * ((unsigned __int128)idx->n + 4096u) >= (unsigned __int128)1 << 55) { c->set_error("cut: %u ranges of a container of %zu B", n_ranges, idx->n); return TSQA_ERR_ARG; }
-    hipStream_t s = stream_of(c, hip_stream);
-    (void)hipSetDevice(c->device);
-    if (int rc = c->reserve_cut(n_ranges)) return rc;
-    CutRange* const ranges = c->cut_ranges;
-    hipLaunchKernelGGL(cut_measure_kernel, dim3((uint32_t)(((uint64_t)n_ranges + 255u) / 256u)), dim3(256), 0, s,
-                       static_cast<const FrameInfo*>(idx->frames), idx->n_blocks, static_cast<const int32_t*>(idx->verdict), d_first, d_count,
-                       n_ranges, ranges, d_sizes, d_totals, d_item_status);
-    hipLaunchKernelGGL(cut_layout_kernel, dim3(1), dim3(256), 0, s, ranges, n_ranges, align, static_cast<uint8_t*>(d_out), (uint64_t)out_size,
-                       static_cast<const uint64_t*>(d_sizes), d_offsets, d_item_status, d_status);
-    if (d_out) {
-        ProfSpan span(c, 5, s);
-        hipLaunchKernelGGL(cut_emit_kernel, dim3(join_emit_groups(c, out_size)), dim3(256), 0, s, idx->container,
-                           static_cast<const CutRange*>(ranges), n_ranges, static_cast<const uint64_t*>(d_offsets),
-                           static_cast<const uint64_t*>(d_sizes), static_cast<uint8_t*>(d_out));
-        span.end();
-    }
-    TSQ_HIP(c, hipGetLastError());
-    return TSQA_OK;
-}
-
-extern "C" int tsqa_cut(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges, uint32_t align,
-                        void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals, int32_t* item_status,
-                        void* hip_stream)
-{
-    if (!c) return TSQA_ERR_ARG;
-    if (!offsets || !sizes || !item_status) { c->set_error("cut: null pointer"); return TSQA_ERR_ARG; }
-    if (n_ranges == 0) { c->set_error("cut: no ranges"); return TSQA_ERR_ARG; }
-    hipStream_t s = stream_of(c, hip_stream);
-    (void)hipSetDevice(c->device);
-    if (int rc = c->reserve_batch(n_ranges)) return rc;      // (the device tables of the waiting form are the batch calls')
-    if (int rc = tsqa_cut_async(c, idx, d_first, d_count, n_ranges, align, d_out, out_size, c->batch_offsets, c->batch_sizes, c->batch_at,
-                                c->batch_status, c->d_status, s)) return rc;
-    TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_ranges + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (totals) TSQ_HIP(c, hipMemcpyAsync(totals, c->batch_at, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    TSQ_HIP(c, hipMemcpyAsync(item_status, c->batch_status, (size_t)n_ranges * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    return finish_sync(c, s, "cut");
-}
-
-// ---- take: items and their block ranges out of any index, each as a container of its own (tsq_take.cuh) ----
 
 extern "C" int tsqa_plan_cut_items(const uint64_t* frame_at, const uint64_t* out_start, uint32_t n_blocks, const uint64_t* item_first_block,
                                    uint32_t n_items, const uint32_t* items, const uint64_t* first, const uint64_t* count, uint32_t n_ranges,
@@ -2088,44 +1996,44 @@ extern "C" int tsqa_plan_cut_items(const uint64_t* frame_at, const uint64_t* out
     return TSQA_OK;
 }
 
-extern "C" int tsqa_cut_items_async(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_first, const uint64_t* d_count,
-                                    uint32_t n_ranges, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
-                                    uint64_t* d_totals, int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+// Both async entry points: the checks, with the caller's name (`who`) and its word for what the index reads (`source`) in the texts,
+// and the five launches.
+static int cut_enqueue(tsqa_ctx* c, const char* who, const char* source, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_first,
+                       const uint64_t* d_count, uint32_t n_ranges, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets,
+                       uint64_t* d_sizes, uint64_t* d_totals, int32_t* d_item_status, int32_t* d_status, hipStream_t s)
 {
-    if (!c) return TSQA_ERR_ARG;
-    if (!idx || !d_offsets || !d_sizes || !d_item_status || !d_status) { c->set_error("cut_items: null pointer"); return TSQA_ERR_ARG; }
-    if (idx->device != c->device) { c->set_error("cut_items: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
-    if (n_ranges == 0) { c->set_error("cut_items: no ranges"); return TSQA_ERR_ARG; }
-    if (!packed_align_ok(align)) { c->set_error("cut_items: align %u is not a power of two from 1 to 4096", align); return TSQA_ERR_ARG; }
-    if ((d_first == nullptr) != (d_count == nullptr)) { c->set_error("cut_items: d_first and d_count go together; both NULL takes whole items"); return TSQA_ERR_ARG; }
+    if (!idx || !d_offsets || !d_sizes || !d_item_status || !d_status) { c->set_error("%s: null pointer", who); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("%s: the index belongs to device %d, the context to %d", who, idx->device, c->device); return TSQA_ERR_ARG; }
+    if (n_ranges == 0) { c->set_error("%s: no ranges", who); return TSQA_ERR_ARG; }
+    if (!packed_align_ok(align)) { c->set_error("%s: align %u is not a power of two from 1 to 4096", who, align); return TSQA_ERR_ARG; }
+    if ((d_first == nullptr) != (d_count == nullptr)) { c->set_error("%s: d_first and d_count go together; both NULL takes whole items", who); return TSQA_ERR_ARG; }
     const uint32_t n_items = tsqa_index_items(idx);
-    if (!d_items && n_items != 1) { c->set_error("cut_items: an index of %u items needs d_items", n_items); return TSQA_ERR_ARG; }
+    if (!d_items && n_items != 1) { c->set_error("%s: an index of %u items needs d_items", who, n_items); return TSQA_ERR_ARG; }
     if (d_out ? out_size < kHeaderSize : out_size != 0) {
-        c->set_error("cut_items: an output needs out_size of at least 16; measuring takes d_out NULL and out_size 0");
+        c->set_error("%s: an output needs out_size of at least 16; measuring takes d_out NULL and out_size 0", who);
         return TSQA_ERR_ARG;
     }
     {
         const uintptr_t a = (uintptr_t)idx->container, o = (uintptr_t)d_out;
-        if (d_out && o < a + idx->n && a < o + out_size) { c->set_error("cut_items: the output overlaps the index's buffer"); return TSQA_ERR_ARG; }
+        if (d_out && o < a + idx->n && a < o + out_size) { c->set_error("%s: the output overlaps the index's %s", who, source); return TSQA_ERR_ARG; }
     }
     // (the sizes go through group_scan_excl64, whose sums stay below 2^55; one source byte may be counted once per range)
-    if ((unsigned __int128)n_ranges * ((unsigned __int128)idx->n + 4096u) >= (unsigned __int128)1 << 55) { c->set_error("cut_items: %u ranges of a buffer of %zu B", n_ranges, idx->n); return TSQA_ERR_ARG; }
-    hipStream_t s = stream_of(c, hip_stream);
+    if ((unsigned __int128)n_ranges * ((unsigned __int128)idx->n + 4096u) >= (unsigned __int128)1 << 55) { c->set_error("%s: %u ranges of a %s of %zu B", who, n_ranges, source, idx->n); return TSQA_ERR_ARG; }
     (void)hipSetDevice(c->device);
-    if (int rc = c->reserve_take(n_ranges)) return rc;
+    if (int rc = c->reserve_cut(n_ranges)) return rc;
     CutRange* const ranges = c->cut_ranges;
-    uint64_t* const groups = c->take_groups;
+    uint64_t* const groups = c->cut_groups;
     uint64_t* const fit_end = &ranges[n_ranges].src_at;  // where cut_emit_kernel looks for the end of the written output
     // (a batch index made on the device and not fetched: cap_blocks descriptors, the live count in its words)
     const bool live = idx->pending_items != 0u;
     const uint32_t n_groups = (uint32_t)(((uint64_t)n_ranges + kTakeGroup - 1u) / kTakeGroup);
-    hipLaunchKernelGGL(take_measure_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const FrameInfo*>(idx->frames),
+    hipLaunchKernelGGL(cut_measure_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const FrameInfo*>(idx->frames),
                        live ? idx->cap_blocks : idx->n_blocks, static_cast<const int32_t*>(idx->verdict),
                        static_cast<const uint64_t*>(idx->d_item_first), n_items, live ? static_cast<const uint64_t*>(idx->d_words) : nullptr, d_items,
                        d_first, d_count, n_ranges, ranges, d_sizes, d_totals, d_item_status);
-    hipLaunchKernelGGL(take_sum_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const uint64_t*>(d_sizes), n_ranges, align, d_offsets, groups);
-    hipLaunchKernelGGL(take_scan_kernel, dim3(1), dim3(256), 0, s, groups, n_groups, fit_end, d_status);
-    hipLaunchKernelGGL(take_place_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const CutRange*>(ranges), n_ranges,
+    hipLaunchKernelGGL(cut_sum_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const uint64_t*>(d_sizes), n_ranges, align, d_offsets, groups);
+    hipLaunchKernelGGL(cut_scan_kernel, dim3(1), dim3(256), 0, s, groups, n_groups, fit_end, d_status);
+    hipLaunchKernelGGL(cut_place_kernel, dim3(n_groups), dim3(256), 0, s, static_cast<const CutRange*>(ranges), n_ranges,
                        static_cast<const uint64_t*>(groups), static_cast<uint8_t*>(d_out), (uint64_t)out_size, static_cast<const uint64_t*>(d_sizes),
                        d_offsets, d_item_status, fit_end, d_status);
     if (d_out) {
@@ -2139,23 +2047,65 @@ extern "C" int tsqa_cut_items_async(tsqa_ctx* c, const tsqa_index* idx, const ui
     return TSQA_OK;
 }
 
-extern "C" int tsqa_cut_items(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_first, const uint64_t* d_count,
-                              uint32_t n_ranges, uint32_t align, void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals,
-                              int32_t* item_status, void* hip_stream)
+extern "C" int tsqa_cut_async(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges,
+                              uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes, uint64_t* d_totals,
+                              int32_t* d_item_status, int32_t* d_status, void* hip_stream)
 {
     if (!c) return TSQA_ERR_ARG;
-    if (!offsets || !sizes || !item_status) { c->set_error("cut_items: null pointer"); return TSQA_ERR_ARG; }
-    if (n_ranges == 0) { c->set_error("cut_items: no ranges"); return TSQA_ERR_ARG; }
+    if (!idx || !d_first || !d_count) { c->set_error("cut: null pointer"); return TSQA_ERR_ARG; }
+    // (fetched or not, and of one item too: its descriptors count from the arena's start, not from a container's)
+    if (idx->d_words) { c->set_error("cut: a batch index made on the device; its items already are separate containers"); return TSQA_ERR_ARG; }
+    if (idx->item_status.size() != 1) { c->set_error("cut: an index of %zu items; its items already are separate containers", idx->item_status.size()); return TSQA_ERR_ARG; }
+    return cut_enqueue(c, "cut", "container", idx, nullptr, d_first, d_count, n_ranges, align, d_out, out_size, d_offsets, d_sizes, d_totals,
+                       d_item_status, d_status, stream_of(c, hip_stream));
+}
+
+extern "C" int tsqa_cut_items_async(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_first, const uint64_t* d_count,
+                                    uint32_t n_ranges, uint32_t align, void* d_out, size_t out_size, uint64_t* d_offsets, uint64_t* d_sizes,
+                                    uint64_t* d_totals, int32_t* d_item_status, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    return cut_enqueue(c, "cut_items", "buffer", idx, d_items, d_first, d_count, n_ranges, align, d_out, out_size, d_offsets, d_sizes, d_totals,
+                       d_item_status, d_status, stream_of(c, hip_stream));
+}
+
+// Both waiting forms: `enqueue` is the async call into the context's batch tables, which are then copied to the host's.
+template <class Enqueue>
+static int cut_wait(tsqa_ctx* c, const char* who, uint32_t n_ranges, uint64_t* offsets, uint64_t* sizes, uint64_t* totals, int32_t* item_status,
+                    void* hip_stream, Enqueue enqueue)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!offsets || !sizes || !item_status) { c->set_error("%s: null pointer", who); return TSQA_ERR_ARG; }
+    if (n_ranges == 0) { c->set_error("%s: no ranges", who); return TSQA_ERR_ARG; }
     hipStream_t s = stream_of(c, hip_stream);
     (void)hipSetDevice(c->device);
     if (int rc = c->reserve_batch(n_ranges)) return rc;      // (the device tables of the waiting form are the batch calls')
-    if (int rc = tsqa_cut_items_async(c, idx, d_items, d_first, d_count, n_ranges, align, d_out, out_size, c->batch_offsets, c->batch_sizes,
-                                      c->batch_at, c->batch_status, c->d_status, s)) return rc;
+    if (int rc = enqueue(s)) return rc;
     TSQ_HIP(c, hipMemcpyAsync(offsets, c->batch_offsets, ((size_t)n_ranges + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipMemcpyAsync(sizes, c->batch_sizes, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     if (totals) TSQ_HIP(c, hipMemcpyAsync(totals, c->batch_at, (size_t)n_ranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipMemcpyAsync(item_status, c->batch_status, (size_t)n_ranges * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    return finish_sync(c, s, "cut_items");
+    return finish_sync(c, s, who);
+}
+
+extern "C" int tsqa_cut(tsqa_ctx* c, const tsqa_index* idx, const uint64_t* d_first, const uint64_t* d_count, uint32_t n_ranges, uint32_t align,
+                        void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals, int32_t* item_status,
+                        void* hip_stream)
+{
+    return cut_wait(c, "cut", n_ranges, offsets, sizes, totals, item_status, hip_stream, [&](hipStream_t s) {
+        return tsqa_cut_async(c, idx, d_first, d_count, n_ranges, align, d_out, out_size, c->batch_offsets, c->batch_sizes, c->batch_at,
+                              c->batch_status, c->d_status, s);
+    });
+}
+
+extern "C" int tsqa_cut_items(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_first, const uint64_t* d_count,
+                              uint32_t n_ranges, uint32_t align, void* d_out, size_t out_size, uint64_t* offsets, uint64_t* sizes, uint64_t* totals,
+                              int32_t* item_status, void* hip_stream)
+{
+    return cut_wait(c, "cut_items", n_ranges, offsets, sizes, totals, item_status, hip_stream, [&](hipStream_t s) {
+        return tsqa_cut_items_async(c, idx, d_items, d_first, d_count, n_ranges, align, d_out, out_size, c->batch_offsets, c->batch_sizes,
+                                    c->batch_at, c->batch_status, c->d_status, s);
+    });
 }
 
 // ---- gather: record reads whose ranges lie in device memory, planned there, into a dense output (tsq_gather.cuh) ----
