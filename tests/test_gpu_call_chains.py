@@ -316,12 +316,13 @@ def check(r, status=None):
     check_buffers(r)
 
 
-def run_chain(codec, links, rng, env, gate, side, key):
-    """prepare every link, open the gate's work on `side`, enqueue every link behind it with no synchronise, wait once -> the runs"""
+def run_chain(codec, links, rng, env, gate, side, key, make=None):
+    """prepare every link (make: a prepare that knows more kinds, test_gpu_call_chains_device.py's), open the gate's work on `side`,
+    enqueue every link behind it with no synchronise, wait once -> the runs"""
     torch = env.torch
     runs = []
     for x in links:
-        runs.append(prepare(x, rng, env, runs))
+        runs.append((make or prepare)(x, rng, env, runs))
     torch.cuda.synchronize()
     stream = C.c_void_p(side.cuda_stream)
     with torch.cuda.stream(side):
