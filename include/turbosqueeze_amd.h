@@ -189,6 +189,8 @@ int tsqa_profile_read_cut(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launche
 /* The same for record reads: the planner of tsqa_gather_async (its launches in front of the decode, as one span per call) and
  * the decode kernel of a record read (tsqa_decompress_item_ranges_async and tsqa_gather_async). */
 int tsqa_profile_read_gather(tsqa_ctx *ctx, double *plan_ms, uint32_t *plan_calls, double *decode_ms, uint32_t *decode_launches);
+/* The pad kernel of tsqa_gather_rows_async (its planner and decode are counted by tsqa_profile_read_gather). */
+int tsqa_profile_read_rows(tsqa_ctx *ctx, double *pad_ms, uint32_t *pad_launches);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -893,6 +895,57 @@ int tsqa_gather_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_it
 int tsqa_gather(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
                 const uint64_t *d_lengths, uint32_t n_ranges, uint32_t align, uint32_t cap_pieces, void *d_out, size_t out_cap,
                 uint64_t *d_out_offsets, int32_t *d_range_status, uint64_t *d_need_pieces, int32_t *d_status, void *hip_stream);
+
+/*
+ * Gather into fixed-stride padded rows: the ranges of tsqa_gather_async, but range k lands in ROW k, at d_out + k * row_stride,
+ * the rest of every row is filled with a pad byte, and d_row_lengths says how many bytes each row got: one [n_rows, row_stride]
+ * tensor of variable-length samples with no host read, no memset and no second pass.  Row k owns
+ * [k * row_stride, (k + 1) * row_stride) whatever the tables say, so a fixed stride is the one layout besides the prefix sum in
+ * which destinations chosen on the device cannot overlap; the trust statement is the gather's.  Any index the gather takes, a batch
+ * index made on the device and not fetched included.
+ *
+ * d_items NULL: offsets into the whole data, else into item d_items[k]'s.  d_offsets NULL: every offset is 0.  d_lengths NULL:
+ * the row runs from its offset to the end of its item (or of the data); with d_items alone every row is a whole item.  Per row, in
+ * this order:
+ *   1. Gate and range: rules 1 and 2 of tsqa_gather_async (TSQA_ERR_FORMAT for every row of a refused sized index, TSQA_ERR_ARG for
+ *      a bad or refused item or a range past its total).  With d_lengths NULL the length is total - offset, and offset > total is
+ *      TSQA_ERR_ARG.
+ *   2. Stride: an accepted length above row_stride gets TSQA_ERR_OVERFLOW for that row ALONE -- this is no prefix: the rows behind
+ *      it are delivered -- and has no pieces; with TSQA_ROWS_TRUNCATE in flags the row reads its first row_stride bytes instead,
+ *      and only those are cut into pieces and decoded.  d_need[1] = the largest accepted length before truncation: the stride at
+ *      which no row is too long.
+ *   3. Pieces: one per block a row's delivered bytes touch, numbered by an exclusive sum over the accepted rows.  The rows whose
+ *      pieces end at or before cap_pieces are a prefix; every accepted row behind it gets TSQA_ERR_OVERFLOW.  d_need[0] = the
+ *      sum: the cap_pieces a retry at this stride and these flags needs (a retry at another stride measures again).
+ *   4. d_row_lengths[k] = the bytes delivered into row k: 0 for any nonzero status.  d_row_status[k] = the row's status.
+ *   5. Padding: pad in 0..255: after the call EVERY byte of [0, n_rows * row_stride) is defined: each row's data, then pad up to
+ *      the stride; a refused or unfit row is all pad.  pad == -1 writes the data bytes alone.
+ * *d_status = the largest row status, raised to TSQA_ERR_STREAM by a decoder exactly as in tsqa_gather_async.  Nothing outside
+ * [d_out, d_out + n_rows * row_stride) is ever written, for any alignment of d_out.  d_out == NULL measures: the lengths, the
+ * statuses and both need words are made, nothing is decoded or padded.
+ * TSQA_ERR_ARG before anything is enqueued for: a NULL among idx, d_row_lengths, d_row_status, d_need and d_status, row_stride == 0,
+ * cap_pieces == 0, an index of another device, unknown flags, pad outside -1..255, d_out != NULL with out_cap < n_rows * row_stride,
+ * or n_rows * (row_stride + 4096) >= 2^55 or n_rows * tsqa_index_blocks >= 2^55.  n_rows == 0 clears *d_status and both need words.
+ * The scratch is the gather's: order the calls of one context on one stream.
+ *
+ * tsqa_gather_rows: the same, then waits for hip_stream and returns *d_status.
+ *
+ * tsqa_plan_gather_rows: host only, rules 1 (without the gate) to 4 on host tables (as tsqa_plan_gather takes them; items, offsets
+ *   and lengths may each be NULL): row_lengths[n_rows], row_status[n_rows], need[2], *n_groups = the blocks the delivered rows touch.
+ */
+#define TSQA_ROWS_TRUNCATE 1u
+int tsqa_plan_gather_rows(const uint64_t *out_start, uint32_t n_blocks, const uint64_t *item_first_block, uint32_t n_items,
+                          const uint32_t *items, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_rows,
+                          uint64_t row_stride, uint32_t flags, uint32_t cap_pieces,
+                          uint64_t *row_lengths, int32_t *row_status, uint64_t *need, uint32_t *n_groups);
+int tsqa_gather_rows_async(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
+                           const uint64_t *d_lengths, uint32_t n_rows, uint64_t row_stride, uint32_t flags, int pad,
+                           uint32_t cap_pieces, void *d_out, size_t out_cap, uint64_t *d_row_lengths, int32_t *d_row_status,
+                           uint64_t *d_need, int32_t *d_status, void *hip_stream);
+int tsqa_gather_rows(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_items, const uint64_t *d_offsets,
+                     const uint64_t *d_lengths, uint32_t n_rows, uint64_t row_stride, uint32_t flags, int pad,
+                     uint32_t cap_pieces, void *d_out, size_t out_cap, uint64_t *d_row_lengths, int32_t *d_row_status,
+                     uint64_t *d_need, int32_t *d_status, void *hip_stream);
 
 /*
  * The index of a packed batch from its tables in DEVICE memory, with no host wait: the last step of packed compress -> index ->

@@ -32,6 +32,7 @@ from .api import (  # noqa: F401
     plan_cut,
     plan_cut_items,
     plan_gather,
+    plan_gather_rows,
     plan_index_packed,
     plan_dense,
     plan_item_ranges,

@@ -227,12 +227,19 @@ def lib(ab=False) -> C.CDLL:
     L.tsqa_cut_items.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_profile_read_gather.restype = C.c_int
     L.tsqa_profile_read_gather.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_profile_read_rows.restype = C.c_int
+    L.tsqa_profile_read_rows.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_plan_gather.restype = C.c_int
     L.tsqa_plan_gather.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, u64p, u32p]
     L.tsqa_gather_async.restype = C.c_int
     L.tsqa_gather_async.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_gather.restype = C.c_int
     L.tsqa_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.tsqa_plan_gather_rows.restype = C.c_int
+    L.tsqa_plan_gather_rows.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, u32p]
+    for f in (L.tsqa_gather_rows_async, L.tsqa_gather_rows):
+        f.restype = C.c_int
+        f.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -495,6 +502,51 @@ class RangeIndex:
         pieces needed -- because no bound on them is known to the host while the lengths are the device's."""
         return self._gather(None, d_offsets, d_lengths, align, out, cap_pieces, range_status)
 
+    def _gather_rows(self, d_items, d_offsets, d_lengths, row_stride, pad, truncate, out, cap_pieces, row_status):
+        codec, torch = self.codec, self.codec.torch
+        first = next((t for t in (d_items, d_offsets, d_lengths) if t is not None), None)
+        if first is None:
+            raise TsqError(3, "gather_rows needs one of d_items, d_offsets and d_lengths: it says how many rows there are")
+        n, row_stride = int(first.numel()), int(row_stride)
+        for name, t, dtypes in (("d_offsets", d_offsets, (torch.int64,)), ("d_lengths", d_lengths, (torch.int64,)),
+                                ("d_items", d_items, (torch.int32, getattr(torch, "uint32", torch.int32)))):
+            if t is not None and (t.dtype not in dtypes or t.device != codec.device or not t.is_contiguous() or t.numel() != n):
+                raise TsqError(3, f"{name} must be a contiguous {str(dtypes[0])[6:]} tensor of {n} entries on the codec's device")
+        if out is not None and (out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != codec.device):
+            raise TsqError(3, "out must be a contiguous uint8 tensor on the codec's device")
+        if row_stride < 1 or (out is not None and out.numel() < n * row_stride):
+            raise TsqError(3, f"gather_rows: {n} rows of {row_stride} B do not fit out")
+        flags = ROWS_TRUNCATE if truncate else 0
+        d_row_lengths = torch.empty(max(n, 1), dtype=torch.int64, device=codec.device)
+        d_status = torch.empty(max(n, 1), dtype=torch.int32, device=codec.device)
+        d_need = torch.empty(2, dtype=torch.int64, device=codec.device)
+        if n == 0:                                           # (an empty tensor has no address to give: the call reads no table entry)
+            d_items = d_offsets = d_lengths = None
+        if cap_pieces is None:
+            # the piece sum, measured: a call without an output makes every table and decodes nothing
+            codec._join()
+            codec.gather_rows_async(self, d_items, d_offsets, d_lengths, n, row_stride, flags, pad, 1, None, d_row_lengths, d_status, d_need)
+            codec._join()
+            cap_pieces = max(min(int(d_need[0].item()), 0xFFFFFFFF), 1)
+        if out is None:
+            out = torch.empty(max(n * row_stride, 1), dtype=torch.uint8, device=codec.device)
+        codec._join()
+        codec.gather_rows_async(self, d_items, d_offsets, d_lengths, n, row_stride, flags, pad, cap_pieces, out, d_row_lengths, d_status, d_need)
+        codec._join()
+        rows = out[:n * row_stride].view(n, row_stride)
+        return (rows, d_row_lengths[:n], d_status[:n]) if row_status else (rows, d_row_lengths[:n])
+
+    def gather_rows(self, d_offsets, d_lengths, row_stride: int, pad: int = 0, truncate: bool = False, out=None, cap_pieces=None,
+                    row_status: bool = False):
+        """gather() into fixed-stride padded rows (DeviceCodec.gather_rows_async): bytes [d_offsets[k], d_offsets[k] + d_lengths[k])
+        land in row k of a [n, row_stride] uint8 tensor -- a view of `out` --, the rest of every row is `pad` (0..255; -1 leaves
+        it as it was), and lengths[k] (an int64 CUDA tensor) is what row k got.  -> (rows, lengths), with row_status=True also the
+        int32 verdict per row: 0; 3 refused; 6 longer than row_stride (that row alone; truncate=True delivers its first row_stride
+        bytes instead) or past cap_pieces.  A row with a nonzero verdict is all pad and has length 0.  d_offsets None: every offset
+        is 0; d_lengths None: to the end of the data.  With `out` and `cap_pieces` given, on a stream of the caller's, nothing is
+        waited for; without cap_pieces the call is measured first and the host WAITS ONCE for the piece sum."""
+        return self._gather_rows(None, d_offsets, d_lengths, row_stride, pad, truncate, out, cap_pieces, row_status)
+
 
 class SizedIndex(RangeIndex):
     """The index of a container of short blocks, made on the device from its table of stream sizes (tsqa_index_create_sized*): the
@@ -742,6 +794,33 @@ def plan_gather(out_start, item_first_block, items, offsets, lengths, align: int
     return [int(x) for x in out_offsets], [int(x) for x in status[:n]], int(pieces.value), int(groups.value)
 
 
+ROWS_TRUNCATE = 1                    # TSQA_ROWS_TRUNCATE
+
+
+def plan_gather_rows(out_start, item_first_block, items, offsets, lengths, row_stride: int, truncate: bool = False, cap_pieces=None, n_rows=None):
+    """tsqa_plan_gather_rows (host only): the verdicts of a gather into rows of row_stride bytes, on host tables as plan_gather
+    takes them; items, offsets and lengths may each be None (n_rows says how many rows when all are).  cap_pieces None: no limit.
+    -> (row_lengths, row_status, [pieces needed, largest accepted length], blocks the delivered rows touch).  Raises TsqError(3)
+    when the arguments are refused."""
+    import numpy as np
+    u64 = lambda v: None if v is None else np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in v], dtype=np.uint64))
+    starts, first, off, ln = u64(out_start), u64(item_first_block), u64(offsets), u64(lengths)
+    it = None if items is None else np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFF for x in items], dtype=np.uint32))
+    tables = [t for t in (it, off, ln) if t is not None]
+    n = len(tables[0]) if tables else int(n_rows or 0)
+    if any(len(t) != n for t in tables) or len(starts) < 1 or len(first) < 2:
+        raise TsqError(3, "tsqa_plan_gather_rows takes tables of one length, n_blocks + 1 block starts and n_items + 1 first blocks")
+    row_lengths, status, need = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32), np.zeros(2, dtype=np.uint64)
+    groups = C.c_uint32(0)
+    ptr = lambda t: None if t is None else t.ctypes.data
+    rc = lib().tsqa_plan_gather_rows(starts.ctypes.data, len(starts) - 1, first.ctypes.data, len(first) - 1, ptr(it), ptr(off), ptr(ln), n,
+                                     int(row_stride), ROWS_TRUNCATE if truncate else 0, 0xFFFFFFFF if cap_pieces is None else int(cap_pieces),
+                                     row_lengths.ctypes.data, status.ctypes.data, need.ctypes.data, C.byref(groups))
+    if rc:
+        raise TsqError(rc, "tsqa_plan_gather_rows refused the arguments")
+    return [int(x) for x in row_lengths[:n]], [int(x) for x in status[:n]], [int(x) for x in need], int(groups.value)
+
+
 class ItemRange(C.Structure):
     """tsqa_item_range: bytes [offset, offset + length) of item `item`'s own data -> d_out + out_at"""
     _fields_ = [("item", C.c_uint32), ("pad", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("out_at", C.c_uint64)]
@@ -856,6 +935,12 @@ class BatchIndex(RangeIndex):
         """RangeIndex.gather addressed by item: range k is bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) of item d_items[k]'s
         own data (d_items: an int32 CUDA tensor, read as unsigned; None: offsets into the concatenation of the healthy items)."""
         return self._gather(d_items, d_offsets, d_lengths, align, out, cap_pieces, range_status)
+
+    def gather_rows(self, d_items, d_offsets=None, d_lengths=None, row_stride: int = 0, pad: int = 0, truncate: bool = False, out=None,
+                    cap_pieces=None, row_status: bool = False):
+        """RangeIndex.gather_rows addressed by item: row k is bytes [d_offsets[k], d_offsets[k] + d_lengths[k]) of item d_items[k]'s
+        own data.  With both tables None every row is a whole item, and with truncate=True the first row_stride bytes of it."""
+        return self._gather_rows(d_items, d_offsets, d_lengths, row_stride, pad, truncate, out, cap_pieces, row_status)
 
     def read_items_into(self, ranges, out, sync: bool = True) -> None:
         """The raw call: ranges = (item, offset, length, out_at), bytes land at out[out_at:].  sync=False: on the current stream,
@@ -1213,6 +1298,13 @@ class DeviceCodec:
         pm, pn, dm, dn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
         self.L.tsqa_profile_read_gather(self.h, C.byref(pm), C.byref(pn), C.byref(dm), C.byref(dn))
         return pm.value, pn.value, dm.value, dn.value
+
+    def profile_read_rows(self):
+        """-> (pad_ms_sum, launches): the pad kernel of gather_rows_async since the last read (its planner and its decode kernel are
+        counted by profile_read_gather)."""
+        pm, pn = C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_rows(self.h, C.byref(pm), C.byref(pn))
+        return pm.value, pn.value
 
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
@@ -1710,6 +1802,21 @@ class DeviceCodec:
                                       out.numel() if out_cap is None else min(int(out_cap), out.numel()),
                                       d_out_offsets.data_ptr(), d_range_status.data_ptr(), d_need_pieces.data_ptr(), self._status.data_ptr(),
                                       self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def gather_rows_async(self, index, d_items, d_offsets, d_lengths, n: int, row_stride: int, flags: int, pad: int, cap_pieces: int, out,
+                          d_row_lengths, d_row_status, d_need) -> None:
+        """tsqa_gather_rows_async on the current stream, nothing waited for: the ranges of gather_async -- d_items, d_offsets and
+        d_lengths may each be None -- land in rows of row_stride bytes, row k at out[k * row_stride:], its tail filled with `pad`
+        (-1: left alone); d_row_lengths (int64, n) = the bytes each row got, d_row_status (int32, n) its verdict, d_need (int64, 2)
+        = the pieces a retry needs and the largest accepted length.  flags: ROWS_TRUNCATE or 0.  out None measures.  The largest
+        row status lands in status()."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self.L.tsqa_gather_rows_async(self.h, index.h, ptr(d_items), ptr(d_offsets), ptr(d_lengths), int(n), int(row_stride), int(flags),
+                                           int(pad), int(cap_pieces), ptr(out), out.numel() if out is not None else 0,
+                                           d_row_lengths.data_ptr(), d_row_status.data_ptr(), d_need.data_ptr(), self._status.data_ptr(),
+                                           self._stream())
         if rc:
             raise self._err(rc)
 

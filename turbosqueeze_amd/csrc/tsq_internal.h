@@ -139,6 +139,9 @@ struct tsqa_ctx {
     tsqa_scratch<tsq::BlockGroup> gather_groups;
     tsqa_scratch<uint8_t> gather_sort;
     tsqa_scratch<tsq::GatherWords> gather_words;
+    // tsqa_gather_rows_async (tsq_rows.cuh) on top of those: per row its place, k * row_stride, and per group of 256 rows its pieces
+    tsqa_scratch<uint64_t> gather_places;
+    tsqa_scratch<uint64_t> gather_row_groups;
     size_t gather_sort_n = 0, gather_sort_bytes = 0;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
@@ -152,8 +155,9 @@ struct tsqa_ctx {
     // switched on (nothing is created or destroyed between the events).  Kinds: 0 encode kernel, 1 decode kernel,
     // 2 whole compress call (encode + container pack), 3 whole decompress call (frame walk + decode), 4 the join's copy kernel,
     // 5 the cut's copy kernel (tsqa_cut_async and tsqa_cut_items_async), 6 the gather's planner (its launches in front of the decode), 7 the decode kernel of a record read
-    // (tsqa_decompress_item_ranges_async and tsqa_gather_async).
-    static constexpr int kProfKinds = 8, kProfPairs = 256;
+    // (tsqa_decompress_item_ranges_async, tsqa_gather_async and tsqa_gather_rows_async, whose planner is kind 6 too), 8 the pad kernel
+    // of tsqa_gather_rows_async.
+    static constexpr int kProfKinds = 9, kProfPairs = 256;
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
     uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -20,6 +20,7 @@
 #include "tsq_launch.cuh"
 #include "tsq_gather.cuh"
 #include "tsq_gather_sort.h"
+#include "tsq_rows.cuh"
 
 #include <algorithm>
 #include <cstdarg>
@@ -277,7 +278,8 @@ int tsqa_ctx::reserve_cut(size_t n_ranges)
 
 // Scratch of the gather (tsq_internal.h): the ranges doubled from 256 as the cut's, the piece slots and groups as many as the call
 // names (cap_pieces is the caller's statement of what the call may hold, and the sort runs over exactly that many pairs), each
-// buffer on its own.  The sort's temporary storage is asked for here, once per cap_pieces, not per call.
+// buffer on its own.  The sort's temporary storage is asked for here, once per cap_pieces, not per call.  The rows' places and
+// group sums (tsqa_gather_rows_async) grow with the ranges.
 int tsqa_ctx::reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups)
 {
     (void)hipSetDevice(device);
@@ -288,11 +290,12 @@ int tsqa_ctx::reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_grou
     }
     const size_t want = doubled(256, n_ranges);
     if (!gather_ranges.needs(want) && !gather_items.needs(2 * cap_pieces) && !gather_keys.needs(2 * cap_pieces) && !gather_slots.needs(2 * cap_pieces) &&
-        !gather_groups.needs(cap_groups) && !gather_sort.needs(gather_sort_bytes) && !gather_words.needs(1)) return TSQA_OK;
+        !gather_groups.needs(cap_groups) && !gather_sort.needs(gather_sort_bytes) && !gather_words.needs(1) && !gather_places.needs(want) &&
+        !gather_row_groups.needs(want / 256)) return TSQA_OK;
     (void)hipDeviceSynchronize();                        // (as in reserve_batch)
     return gather_ranges.grow(this, want) && gather_items.grow(this, 2 * cap_pieces) && gather_keys.grow(this, 2 * cap_pieces) &&
            gather_slots.grow(this, 2 * cap_pieces) && gather_groups.grow(this, cap_groups) && gather_sort.grow(this, gather_sort_bytes) &&
-           gather_words.grow(this, 1) ? TSQA_OK : TSQA_ERR_HIP;
+           gather_words.grow(this, 1) && gather_places.grow(this, want) && gather_row_groups.grow(this, want / 256) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
 // ---- kernel timing ----
@@ -393,6 +396,15 @@ extern "C" int tsqa_profile_read_gather(tsqa_ctx* c, double* plan_ms, uint32_t* 
     if (c->prof_pool.empty()) { if (plan_ms) *plan_ms = 0; if (plan_n) *plan_n = 0; if (dec_ms) *dec_ms = 0; if (dec_n) *dec_n = 0; return TSQA_OK; }
     drain_events(c, 6, plan_ms, plan_n);
     drain_events(c, 7, dec_ms, dec_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_rows(tsqa_ctx* c, double* pad_ms, uint32_t* pad_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (pad_ms) *pad_ms = 0; if (pad_n) *pad_n = 0; return TSQA_OK; }
+    drain_events(c, 8, pad_ms, pad_n);
     return TSQA_OK;
 }
 
@@ -2253,6 +2265,167 @@ extern "C" int tsqa_gather(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d
     TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "gather");
+}
+
+// ---- gather into fixed-stride padded rows: the same ranges, row k at k * row_stride, the tails filled (tsq_rows.cuh) ----
+
+// What keeps the sums of the rows' scans, and n_rows * row_stride itself, below 2^55.
+static bool rows_sums_ok(uint32_t n_rows, uint64_t row_stride, uint32_t n_blocks)
+{
+    const unsigned __int128 limit = (unsigned __int128)1 << 55;
+    return (unsigned __int128)n_rows * ((unsigned __int128)row_stride + 4096u) < limit && (unsigned __int128)n_rows * n_blocks < limit;
+}
+
+extern "C" int tsqa_plan_gather_rows(const uint64_t* out_start, uint32_t n_blocks, const uint64_t* item_first_block, uint32_t n_items,
+                                     const uint32_t* items, const uint64_t* offsets, const uint64_t* lengths, uint32_t n_rows,
+                                     uint64_t row_stride, uint32_t flags, uint32_t cap_pieces, uint64_t* row_lengths, int32_t* row_status,
+                                     uint64_t* need, uint32_t* n_groups)
+{
+    if (!out_start || !item_first_block || !row_lengths || !row_status || !need || !n_groups || n_items == 0 || row_stride == 0 ||
+        (flags & ~(uint32_t)TSQA_ROWS_TRUNCATE) || cap_pieces < 1) return TSQA_ERR_ARG;
+    if (out_start[0] != 0 || item_first_block[0] != 0 || item_first_block[n_items] != n_blocks) return TSQA_ERR_ARG;
+    for (uint32_t b = 0; b < n_blocks; ++b)
+        if (out_start[b + 1] < out_start[b] || out_start[b + 1] - out_start[b] > kBlockSize) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_first_block[i + 1] < item_first_block[i]) return TSQA_ERR_ARG;
+    if (!rows_sums_ok(n_rows, row_stride, n_blocks)) return TSQA_ERR_ARG;
+    uint64_t pieces_at = 0, longest = 0;
+    std::vector<uint32_t> touched;
+    try {
+        for (uint32_t k = 0; k < n_rows; ++k) {
+            uint64_t base = 0, mine = out_start[n_blocks];
+            const uint64_t offset = offsets ? offsets[k] : 0;
+            bool ok = true;
+            if (items) {
+                ok = items[k] < n_items && item_first_block[items[k]] < item_first_block[items[k] + 1];
+                if (ok) { base = out_start[item_first_block[items[k]]]; mine = out_start[item_first_block[items[k] + 1]] - base; }
+            }
+            ok = ok && (lengths ? lengths[k] <= mine && offset <= mine - lengths[k] : offset <= mine);
+            const uint64_t accepted = !ok ? 0 : lengths ? lengths[k] : mine - offset;
+            if (accepted > longest) longest = accepted;
+            const bool too_long = accepted > row_stride && !(flags & TSQA_ROWS_TRUNCATE);
+            const uint64_t len = !ok || too_long ? 0 : accepted < row_stride ? accepted : row_stride, a = base + offset, e = a + len;
+            uint64_t first = 0, pieces = 0;
+            if (len) {
+                first = (uint64_t)(std::upper_bound(out_start, out_start + n_blocks + 1, a) - out_start) - 1;
+                for (uint64_t b = first; b < n_blocks && out_start[b] < e; ++b) pieces += out_start[b + 1] > out_start[b];
+            }
+            const bool fits = ok && !too_long && pieces_at + pieces <= cap_pieces;
+            row_status[k] = !ok ? TSQA_ERR_ARG : fits ? TSQA_OK : TSQA_ERR_OVERFLOW;
+            row_lengths[k] = fits ? len : 0;
+            if (fits && len)
+                for (uint64_t b = first; b < n_blocks && out_start[b] < e; ++b)
+                    if (out_start[b + 1] > out_start[b]) touched.push_back((uint32_t)b);
+            pieces_at += pieces;
+        }
+        std::sort(touched.begin(), touched.end());
+        *n_groups = (uint32_t)(std::unique(touched.begin(), touched.end()) - touched.begin());
+    } catch (...) { return TSQA_ERR_ARG; }
+    need[0] = pieces_at;
+    need[1] = longest;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_gather_rows_async(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_offsets, const uint64_t* d_lengths,
+                                      uint32_t n_rows, uint64_t row_stride, uint32_t flags, int pad, uint32_t cap_pieces, void* d_out, size_t out_cap,
+                                      uint64_t* d_row_lengths, int32_t* d_row_status, uint64_t* d_need, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_row_lengths || !d_row_status || !d_need || !d_status) { c->set_error("gather_rows: null pointer"); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("gather_rows: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    if (row_stride == 0) { c->set_error("gather_rows: row_stride of 0"); return TSQA_ERR_ARG; }
+    if (cap_pieces < 1) { c->set_error("gather_rows: cap_pieces of 0"); return TSQA_ERR_ARG; }
+    if (flags & ~(uint32_t)TSQA_ROWS_TRUNCATE) { c->set_error("gather_rows: unknown flags %#x", flags); return TSQA_ERR_ARG; }
+    if (pad < -1 || pad > 255) { c->set_error("gather_rows: pad %d is neither a byte nor -1", pad); return TSQA_ERR_ARG; }
+    // (a batch index made on the device and not fetched: cap_blocks descriptors, the total in its words)
+    const bool live = idx->pending_items != 0u;
+    const uint32_t n_blocks = live ? idx->cap_blocks : idx->n_blocks;
+    if (!rows_sums_ok(n_rows, row_stride, n_blocks)) {
+        c->set_error("gather_rows: %u rows of %llu B out of an index of %u blocks", n_rows, (unsigned long long)row_stride, n_blocks);
+        return TSQA_ERR_ARG;
+    }
+    if (d_out && (uint64_t)out_cap < (uint64_t)n_rows * row_stride) {
+        c->set_error("gather_rows: %u rows of %llu B need %llu B, out_cap is %zu", n_rows, (unsigned long long)row_stride,
+                     (unsigned long long)((uint64_t)n_rows * row_stride), out_cap);
+        return TSQA_ERR_ARG;
+    }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    if (n_rows == 0) {
+        TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+        TSQ_HIP(c, hipMemsetAsync(d_need, 0, 2 * sizeof(uint64_t), s));
+        return TSQA_OK;
+    }
+    const uint32_t cap_groups = cap_pieces < n_blocks ? cap_pieces : n_blocks;
+    if (int rc = c->reserve_gather(n_rows, cap_pieces, cap_groups ? cap_groups : 1)) return rc;
+    GatherRange* const ranges = c->gather_ranges;
+    GatherWords* const words = c->gather_words;
+    RangeItem* const items = c->gather_items;
+    RangeItem* const sorted = items + cap_pieces;
+    uint64_t* const keys = c->gather_keys;
+    uint32_t* const slots = c->gather_slots;
+    BlockGroup* const groups = c->gather_groups;
+    uint64_t* const places = c->gather_places;
+    uint64_t* const row_groups = c->gather_row_groups;
+    const uint32_t n_items = tsqa_index_items(idx), n_row_groups = (uint32_t)(((uint64_t)n_rows + kRowsGroup - 1u) / kRowsGroup);
+    ProfSpan plan(c, 6, s);
+    void (*const measure)(const FrameInfo*, uint32_t, uint64_t, uint32_t, const int32_t*, const uint64_t*, uint32_t, const uint32_t*, const uint64_t*,
+                          const uint64_t*, uint32_t, uint64_t, uint32_t, GatherRange*, uint64_t*, int32_t*, const uint64_t*) =
+        live ? rows_measure_kernel<true> : rows_measure_kernel<false>;
+    hipLaunchKernelGGL(measure, dim3(n_row_groups), dim3(256), 0, s, static_cast<const FrameInfo*>(idx->frames), n_blocks, idx->total,
+                       idx->block_shift, static_cast<const int32_t*>(idx->verdict), static_cast<const uint64_t*>(idx->d_item_first), n_items, d_items,
+                       d_offsets, d_lengths, n_rows, row_stride, flags, ranges, d_row_lengths, d_row_status, static_cast<const uint64_t*>(idx->d_words));
+    hipLaunchKernelGGL(rows_sum_kernel, dim3(n_row_groups), dim3(256), 0, s, ranges, n_rows, row_groups);
+    hipLaunchKernelGGL(rows_scan_kernel, dim3(1), dim3(256), 0, s, row_groups, n_row_groups, d_need, words);
+    hipLaunchKernelGGL(rows_place_kernel, dim3(n_row_groups), dim3(256), 0, s, ranges, n_rows, static_cast<const uint64_t*>(row_groups), row_stride,
+                       cap_pieces, places, d_row_lengths, d_row_status, d_need, words);
+    int rc = TSQA_OK;
+    if (d_out && n_blocks) {
+        const uint64_t lanes = n_rows > cap_pieces ? n_rows : cap_pieces, piece_groups = ((uint64_t)cap_pieces + 255u) / 256u;
+        hipLaunchKernelGGL(gather_pieces_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, s, static_cast<const FrameInfo*>(idx->frames),
+                           n_blocks, static_cast<const GatherRange*>(ranges), n_rows, static_cast<const int32_t*>(d_row_status),
+                           static_cast<const uint64_t*>(places), static_cast<const GatherWords*>(words), cap_pieces, items, keys, slots);
+        TSQ_HIP(c, gather_sort_pairs(c->gather_sort, c->gather_sort_bytes, keys, keys + cap_pieces, slots, slots + cap_pieces, cap_pieces, s));
+        const uint64_t movers = piece_groups < 4ull * (uint64_t)c->n_cus ? piece_groups : 4ull * (uint64_t)c->n_cus;
+        hipLaunchKernelGGL(gather_groups_kernel, dim3((uint32_t)(1u + movers)), dim3(256), 0, s, static_cast<const RangeItem*>(items),
+                           static_cast<const uint64_t*>(keys + cap_pieces), static_cast<const uint32_t*>(slots + cap_pieces), words, cap_pieces,
+                           sorted, groups, cap_groups);
+        hipLaunchKernelGGL(gather_spans_kernel, dim3((cap_groups + 255u) / 256u), dim3(256), 0, s, static_cast<const RangeItem*>(sorted),
+                           static_cast<const GatherWords*>(words), cap_pieces, groups, cap_groups);
+        plan.end();
+        ProfSpan dec(c, 7, s);
+        rc = launch_read_kernel<dec_group_live_kernel>(c, cap_groups, s, idx->container, static_cast<const FrameInfo*>(idx->frames), n_blocks,
+                                                       static_cast<const RangeItem*>(sorted), cap_pieces, static_cast<const BlockGroup*>(groups),
+                                                       static_cast<uint8_t*>(d_out), &words->stream, static_cast<const uint32_t*>(&words->n_groups));
+        dec.end();
+    } else plan.end();
+    if (d_out && pad >= 0) {
+        // (the decoders write data bytes alone and the pad kernel pad bytes alone: neither order between them matters)
+        const uint64_t n_words = ((uint64_t)n_rows * row_stride + 15u + 15u) >> 4, want = (n_words + 255u) / 256u;
+        const uint64_t most = 16ull * (uint64_t)c->n_cus;
+        ProfSpan span(c, 8, s);
+        hipLaunchKernelGGL(rows_pad_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(256), 0, s, static_cast<uint8_t*>(d_out), n_rows,
+                           row_stride, static_cast<const uint64_t*>(d_row_lengths), (uint32_t)pad);
+        span.end();
+    }
+    hipLaunchKernelGGL(gather_close_kernel, dim3(1), dim3(1), 0, s, static_cast<const GatherWords*>(words), d_status);
+    if (rc) return rc;
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_gather_rows(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d_items, const uint64_t* d_offsets, const uint64_t* d_lengths,
+                                uint32_t n_rows, uint64_t row_stride, uint32_t flags, int pad, uint32_t cap_pieces, void* d_out, size_t out_cap,
+                                uint64_t* d_row_lengths, int32_t* d_row_status, uint64_t* d_need, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_gather_rows_async(c, idx, d_items, d_offsets, d_lengths, n_rows, row_stride, flags, pad, cap_pieces, d_out, out_cap,
+                                        d_row_lengths, d_row_status, d_need, d_status, s)) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "gather_rows");
 }
 
 // The 16-byte headers of a batch's items, to the host with one gather kernel and one copy (and to c->batch_heads).  Waits for `s`.
