@@ -191,6 +191,8 @@ int tsqa_profile_read_cut(tsqa_ctx *ctx, double *emit_ms, uint32_t *emit_launche
 int tsqa_profile_read_gather(tsqa_ctx *ctx, double *plan_ms, uint32_t *plan_calls, double *decode_ms, uint32_t *decode_launches);
 /* The pad kernel of tsqa_gather_rows_async (its planner and decode are counted by tsqa_profile_read_gather). */
 int tsqa_profile_read_rows(tsqa_ctx *ctx, double *pad_ms, uint32_t *pad_launches);
+/* tsqa_records_async: its mark decode (the decoder that writes one bit per byte) and, per call, its table launches together. */
+int tsqa_profile_read_records(tsqa_ctx *ctx, double *mark_ms, uint32_t *mark_launches, double *table_ms, uint32_t *table_calls);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -946,6 +948,70 @@ int tsqa_gather_rows(tsqa_ctx *ctx, const tsqa_index *idx, const uint32_t *d_ite
                      const uint64_t *d_lengths, uint32_t n_rows, uint64_t row_stride, uint32_t flags, int pad,
                      uint32_t cap_pieces, void *d_out, size_t out_cap, uint64_t *d_row_lengths, int32_t *d_row_status,
                      uint64_t *d_need, int32_t *d_status, void *hip_stream);
+
+/*
+ * Record tables from a delimiter byte: where the records of an index's data are -- the tables that tsqa_gather_async and
+ * tsqa_gather_rows_async take -- made on the device with NO decoded copy.  Every block is decoded and validated as in the
+ * whole-block decode, but its bytes are compared with the delimiter instead of being stored: the one thing written per decoded
+ * byte is a bit, into a map in the context's scratch of (tsqa_index_total >> 6) + tsqa_index_blocks + 1 words of 8 bytes: an eighth
+ * of the data and 8 bytes per block.  A count, a scan and a placement over that map make the tables.  Any index but a batch index
+ * made on the device and not yet fetched.
+ *
+ * The rule.  The index has n_items items.  A container index has one item.  Item i has data D_i of T_i bytes.  A refused item,
+ * whose item status is nonzero, has no records.  So does an item with T_i == 0.  The delimiter is one byte value delim, 0..255.
+ *   - A record STARTS at byte 0 of the item.  It also starts at p + 1 for every p with D_i[p] == delim and p + 1 < T_i.
+ *   - A record ENDS in front of the next delimiter at or behind its start.  Where there is none, it ends at T_i: the last record
+ *     needs no terminator.
+ *   - A terminator at T_i - 1 starts no record.
+ *   - Two delimiters side by side give a record of length 0, which is a record.
+ *   - TSQA_RECORDS_KEEP_DELIM (flag 1): a record's length includes its terminating delimiter where it has one.
+ *   - TSQA_RECORDS_FLAT (flag 2): offsets count from the start of the index's whole data, the concatenation that
+ *     tsqa_decompress_ranges* and a gather with d_items == NULL read.  Without the flag they count from the item's own start, which
+ *     is what a gather with d_items takes.
+ *   - Records are numbered item by item in item order, and by start inside an item.  No record crosses an item.
+ * Outputs:
+ *   - d_item_first_record has n_items + 1 entries.  It is the exclusive sum of the items' record counts.  Its last entry is the
+ *     count of all records.  It is always complete, whatever cap_records.
+ *   - d_need[0] is that count, the cap_records a retry needs.
+ *   - d_need[1] is the largest record length under the call's flags.  It is the row_stride at which tsqa_gather_rows_async
+ *     truncates nothing.  It is taken over all records, those beyond cap_records included.
+ *   - Records numbered below cap_records are written to the three tables.  Records at or past it are not.  They are a prefix.
+ *     Nothing of a table is written at or beyond cap_records.
+ *   - d_rec_items may be NULL.  d_rec_offsets and d_rec_lengths may both be NULL together with cap_records == 0.  That call only
+ *     measures.
+ * Status: *d_status is TSQA_OK when every record fits.  It is TSQA_ERR_OVERFLOW when the count of all records exceeds cap_records,
+ * with the prefix written.  It is TSQA_ERR_FORMAT for a sized index whose verdict is nonzero.  Then no descriptor is read, every
+ * entry of d_item_first_record is 0 and both need words are 0.  It is raised to TSQA_ERR_STREAM when a decoder met a malformed
+ * stream (while it is TSQA_ERR_OVERFLOW it stays that, as in tsqa_gather_async).  Then the tables' contents are undefined and
+ * nothing outside them was written.
+ * Trust: nothing in the container is trusted.  Every decoded chunk is validated as in the whole-block decode.  Nothing is written
+ * outside the stated extents of the caller's tables.  The tables are aligned as their element types ask -- 8 bytes for the 64-bit
+ * tables and d_need (which is raised with 64-bit atomics), 4 for d_rec_items and d_status --, and at any such address: nothing
+ * wider than an element is stored.
+ * TSQA_ERR_ARG before anything is enqueued for: a NULL among idx, d_item_first_record, d_need and d_status; delim > 255; unknown
+ * flags; cap_records > 0 with a NULL offsets or lengths table; an index of another device; an index made on the device and not yet
+ * fetched (the host sizes the scratch from the total and the block count: tsqa_index_fetch first).  An index of 0 blocks clears
+ * the three words and the first-record table.  Calls that share a context share its scratch: order them on one stream.
+ *
+ * tsqa_records: the same, then waits for hip_stream and returns *d_status.
+ *
+ * tsqa_plan_records: host only, the same rule on decoded bytes on the host.  data is the concatenation, item_at[n_items + 1]
+ *   holds the items' starts in it, item_status may be NULL (no item is refused).  Fills rec_items (may be NULL), rec_offsets and
+ *   rec_lengths below cap_records, item_first_record[n_items + 1] and need[2].  Returns TSQA_OK whatever fits; TSQA_ERR_ARG for
+ *   NULL or unordered tables, n_items == 0, a bad delim or bad flags.
+ */
+#define TSQA_RECORDS_KEEP_DELIM 1u
+#define TSQA_RECORDS_FLAT 2u
+int tsqa_plan_records(const void *data, const uint64_t *item_at, const int32_t *item_status, uint32_t n_items,
+                      uint32_t delim, uint32_t flags, uint64_t cap_records,
+                      uint32_t *rec_items, uint64_t *rec_offsets, uint64_t *rec_lengths,
+                      uint64_t *item_first_record, uint64_t *need);
+int tsqa_records_async(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t delim, uint32_t flags, uint64_t cap_records,
+                       uint32_t *d_rec_items, uint64_t *d_rec_offsets, uint64_t *d_rec_lengths,
+                       uint64_t *d_item_first_record, uint64_t *d_need, int32_t *d_status, void *hip_stream);
+int tsqa_records(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t delim, uint32_t flags, uint64_t cap_records,
+                 uint32_t *d_rec_items, uint64_t *d_rec_offsets, uint64_t *d_rec_lengths,
+                 uint64_t *d_item_first_record, uint64_t *d_need, int32_t *d_status, void *hip_stream);
 
 /*
  * The index of a packed batch from its tables in DEVICE memory, with no host wait: the last step of packed compress -> index ->

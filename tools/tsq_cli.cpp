@@ -10,6 +10,9 @@
 //                                           range read: the container goes to the device, an index is built
 //                                           (tsqa_index_create) and bytes [offset, offset + length) of its
 //                                           uncompressed data are read (tsqa_decompress_ranges) into <out>.
+//   tsq_cli r <in.tsq> [delim]              records: the container goes to the device and the record count and the longest
+//                                           record for the delimiter byte (default 10, a newline) are printed
+//                                           (tsqa_records with no tables: nothing is decoded into memory).
 // Unlike the reference's benchmark (clock() summed over threads, divided by 1e5) this reports
 // wall-clock MB/s.
 #include <chrono>
@@ -35,7 +38,8 @@ static int usage()
 {
     fprintf(stderr, "usage: tsq_cli c <in> <out> [--no-ext] | d <in> <out> | b [file | --synthetic BYTES] [--no-ext] [--reps N]\n"
                     "       tsq_cli bf <in> <workdir> [--no-ext] [--reps N]   (file -> file -> file with warm contexts)\n"
-                    "       tsq_cli x <in.tsq> <offset> <length> <out>       (uncompressed bytes [offset, offset + length))\n");
+                    "       tsq_cli x <in.tsq> <offset> <length> <out>       (uncompressed bytes [offset, offset + length))\n"
+                    "       tsq_cli r <in.tsq> [delim]                       (record count and longest record for a delimiter byte, default 10)\n");
     return 2;
 }
 
@@ -76,6 +80,44 @@ static int range_read(const std::string& in, uint64_t offset, uint64_t length, c
     return 0;
 }
 
+// r: the record count and the longest record of a container for a delimiter byte, measured on the device
+static int count_records(const std::string& in, uint32_t delim)
+{
+    FILE* f = fopen(in.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", in.c_str()); return 1; }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    std::vector<uint8_t> blob(sz > 0 ? (size_t)sz : 0);
+    const bool read_ok = fread(blob.data(), 1, blob.size(), f) == blob.size();
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "short read\n"); return 1; }
+    tsqa_ctx* ctx = nullptr;
+    if (tsqa_create(-1, &ctx) != TSQA_OK) { fprintf(stderr, "no usable MI355X (gfx950) device\n"); return 1; }
+    void *d_in = nullptr, *d_words = nullptr;                  // d_words: item_first_record[2], need[2], status
+    tsqa_index* idx = nullptr;
+    uint64_t words[5] = {0, 0, 0, 0, 0};
+    int rc = TSQA_OK;
+    if (hipMalloc(&d_in, blob.size() ? blob.size() : 1) != hipSuccess || hipMalloc(&d_words, sizeof(words)) != hipSuccess ||
+        hipMemcpy(d_in, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "device memory: %s\n", hipGetErrorString(hipGetLastError()));
+        rc = TSQA_ERR_HIP;
+    }
+    if (rc == TSQA_OK && (rc = tsqa_index_create(ctx, d_in, blob.size(), &idx)) == TSQA_OK) {
+        uint64_t* const w = static_cast<uint64_t*>(d_words);
+        rc = tsqa_records(ctx, idx, delim, 0, 0, nullptr, nullptr, nullptr, w, w + 2, reinterpret_cast<int32_t*>(w + 4), nullptr);
+        if (rc == TSQA_ERR_OVERFLOW) rc = TSQA_OK;             // (a call without tables only measures: every record is "too many")
+    }
+    if (rc != TSQA_OK && rc != TSQA_ERR_HIP) fprintf(stderr, "records failed (%d): %s\n", rc, tsqa_last_error(ctx));
+    if (rc == TSQA_OK && hipMemcpy(words, d_words, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess) rc = TSQA_ERR_HIP;
+    const uint64_t total = idx ? tsqa_index_total(idx) : 0;
+    tsqa_index_destroy(idx);
+    (void)hipFree(d_in); (void)hipFree(d_words);
+    tsqa_destroy(ctx);
+    if (rc != TSQA_OK) return 1;
+    printf("{\"bytes\": %llu, \"delim\": %u, \"records\": %llu, \"longest_record\": %llu}\n", (unsigned long long)total, delim,
+           (unsigned long long)words[2], (unsigned long long)words[3]);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return usage();
@@ -113,6 +155,12 @@ int main(int argc, char** argv)
     if (mode == "x") {
         if (pos.size() != 4) return usage();
         return range_read(pos[0], strtoull(pos[1].c_str(), nullptr, 10), strtoull(pos[2].c_str(), nullptr, 10), pos[3]);
+    }
+    if (mode == "r") {
+        if (pos.size() != 1 && pos.size() != 2) return usage();
+        const unsigned long delim = pos.size() == 2 ? strtoul(pos[1].c_str(), nullptr, 10) : 10ul;
+        if (delim > 255ul) { fprintf(stderr, "delim is one byte value, 0..255\n"); return 2; }
+        return count_records(pos[0], (uint32_t)delim);
     }
     if (mode == "bf") {
         // file -> .tsq file -> file through the _MT API's file modes with the contexts allocated once (as sample/main.cpp:71-95 keeps

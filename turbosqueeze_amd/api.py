@@ -240,6 +240,13 @@ def lib(ab=False) -> C.CDLL:
     for f in (L.tsqa_gather_rows_async, L.tsqa_gather_rows):
         f.restype = C.c_int
         f.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.tsqa_plan_records.restype = C.c_int
+    L.tsqa_plan_records.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp]
+    for f in (L.tsqa_records_async, L.tsqa_records):
+        f.restype = C.c_int
+        f.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    L.tsqa_profile_read_records.restype = C.c_int
+    L.tsqa_profile_read_records.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -546,6 +553,115 @@ class RangeIndex:
         is 0; d_lengths None: to the end of the data.  With `out` and `cap_pieces` given, on a stream of the caller's, nothing is
         waited for; without cap_pieces the call is measured first and the host WAITS ONCE for the piece sum."""
         return self._gather_rows(None, d_offsets, d_lengths, row_stride, pad, truncate, out, cap_pieces, row_status)
+
+    def records(self, delim: int = 10, keep_delim: bool = False, flat: bool = False, cap_records=None, sync: bool = True) -> "RecordTable":
+        """Where the records of the data are, for a delimiter byte (DeviceCodec.records_async): a record starts at byte 0 of every
+        item and behind every delimiter but one at the item's last byte, and ends in front of the next delimiter or at the item's
+        end.  The data is decoded and compared on the device; no decoded copy is made -- the scratch is a bit per byte.  keep_delim:
+        a record's length includes its terminator; flat: offsets count from the start of the whole data (what gather() without
+        items takes), else from the record's own item.  -> a RecordTable whose tensors gather() and gather_rows() take.
+        cap_records None: the call is run twice -- once with no tables, which only measures, then, after ONE host read of the
+        count, with tables of exactly that many entries: two calls, one host read, two decodes.  cap_records given: ONE enqueue on
+        the current stream with no host read; the tables have cap_records entries, the records below it are written, and
+        table.status reads 6 when there are more (table.need[0] says how many).  sync=False with cap_records: nothing is waited
+        for.  Otherwise the call is waited for and a refused index (4) or a malformed stream (5) raises TsqError."""
+        codec, torch = self.codec, self.codec.torch
+        # (a DeviceBatchIndex before fetch() is refused by the library, with the text that names tsqa_index_fetch)
+        flags = (RECORDS_KEEP_DELIM if keep_delim else 0) | (RECORDS_FLAT if flat else 0)
+        n_items = int(self.L.tsqa_index_items(self.h))
+        i64 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int64, device=codec.device)
+        item_first, need = i64(n_items + 1)[:n_items + 1], i64(2)
+        status = torch.empty(1, dtype=torch.int32, device=codec.device)
+        measured = cap_records is None
+        if measured:
+            codec._join()
+            codec.records_async(self, delim, flags, 0, None, None, None, item_first, need, status)
+            codec._join()
+            cap_records = int(need[0].item())
+        cap_records = int(cap_records)
+        offsets, lengths = i64(cap_records)[:cap_records], i64(cap_records)[:cap_records]
+        items = torch.empty(max(cap_records, 1), dtype=torch.int32, device=codec.device)[:cap_records]
+        codec._join()
+        codec.records_async(self, delim, flags, cap_records, items if cap_records else None, offsets if cap_records else None,
+                            lengths if cap_records else None, item_first, need, status)
+        codec._join()
+        table = RecordTable(self, offsets, lengths, items, item_first, need, status, flat)
+        if sync or measured:
+            st = int(status.item())
+            if st not in (0, 6):
+                raise TsqError(st, "records: the device reported a refused index (4) or a malformed stream (5)")
+        return table
+
+
+class RecordTable:
+    """What RangeIndex.records gives: offsets, lengths (int64) and items (int32) of cap_records entries, of which the first
+    min(n, cap_records) are records; item_first (int64, items + 1: each item's first record number, then the count); need (int64:
+    the count of all records, the largest record length) and status (int32: 0, 6 when there are more records than entries, 4, 5) --
+    all CUDA tensors, valid behind the stream the call was enqueued on.  n and max_length read `need` on the host (they wait)."""
+
+    def __init__(self, index, offsets, lengths, items, item_first, need, status, flat: bool):
+        self.index, self.offsets, self.lengths, self.items, self.item_first, self.need, self.status, self.flat = (
+            index, offsets, lengths, items, item_first, need, status, flat)
+        self._need = None
+
+    def _read_need(self):
+        if self._need is None:
+            self._need = [int(x) for x in self.need.cpu().tolist()]
+        return self._need
+
+    @property
+    def n(self) -> int:
+        return self._read_need()[0]
+
+    @property
+    def max_length(self) -> int:
+        return self._read_need()[1]
+
+    def gather_rows(self, sel, row_stride=None, pad: int = 0, truncate: bool = False, out=None, cap_pieces=None, row_status: bool = False):
+        """The records numbered sel (an int64 CUDA tensor of record numbers below the table's entries) as rows: items[sel],
+        offsets[sel], lengths[sel] go to the index's gather_rows (torch indexing; nothing new on the device).  row_stride None:
+        max_length, which truncates nothing (one host read)."""
+        if row_stride is None:
+            row_stride = max(self.max_length, 1)
+        d_items = None if self.flat else self.items[sel].contiguous()
+        return self.index._gather_rows(d_items, self.offsets[sel].contiguous(), self.lengths[sel].contiguous(), row_stride, pad, truncate, out,
+                                       cap_pieces, row_status)
+
+
+RECORDS_KEEP_DELIM, RECORDS_FLAT = 1, 2          # TSQA_RECORDS_KEEP_DELIM, TSQA_RECORDS_FLAT
+
+
+def plan_records(data, item_at, item_status=None, delim: int = 10, keep_delim: bool = False, flat: bool = False, cap_records=None):
+    """tsqa_plan_records (host only): the rule of RangeIndex.records applied to decoded bytes on the host.  data: the concatenation
+    of the items' data (bytes or a uint8 array); item_at: the items' starts in it, n_items + 1; item_status: nonzero refuses an
+    item.  cap_records None: counts first, then fills tables of that many entries.  -> (items, offsets, lengths: the records below
+    cap_records; item_first_record, n_items + 1; [the count, the largest length]).  Raises TsqError(3) when the arguments are refused."""
+    import numpy as np
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    at = np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in item_at], dtype=np.uint64))
+    n_items = len(at) - 1
+    if n_items >= 1 and int(at[-1]) > buf.size:
+        raise TsqError(3, "tsqa_plan_records: the items end past the data")
+    st = None if item_status is None else np.ascontiguousarray(np.array([int(x) for x in item_status], dtype=np.int32))
+    if st is not None and len(st) != n_items:
+        raise TsqError(3, "tsqa_plan_records takes one status per item")
+    flags = (RECORDS_KEEP_DELIM if keep_delim else 0) | (RECORDS_FLAT if flat else 0)
+    first, need = np.zeros(max(n_items, 0) + 1, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    ptr = lambda t: None if t is None else t.ctypes.data
+
+    def call(cap, items, offsets, lengths):
+        rc = lib().tsqa_plan_records(buf.ctypes.data if buf.size else None, at.ctypes.data, ptr(st), max(n_items, 0), int(delim), flags, cap,
+                                     ptr(items), ptr(offsets), ptr(lengths), first.ctypes.data, need.ctypes.data)
+        if rc:
+            raise TsqError(rc, "tsqa_plan_records refused the arguments")
+    if cap_records is None:
+        call(0, None, None, None)
+        cap_records = int(need[0])
+    cap = int(cap_records)
+    items, offsets, lengths = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+    call(cap, items, offsets, lengths)
+    k = min(cap, int(need[0]))
+    return items[:k], offsets[:k], lengths[:k], first, [int(x) for x in need]
 
 
 class SizedIndex(RangeIndex):
@@ -1306,6 +1422,13 @@ class DeviceCodec:
         self.L.tsqa_profile_read_rows(self.h, C.byref(pm), C.byref(pn))
         return pm.value, pn.value
 
+    def profile_read_records(self):
+        """-> (mark_ms_sum, launches, table_ms_sum, calls): the mark decode of records_async (the decoder that writes one bit per
+        byte) and its table launches since the last read."""
+        mm, mn, tm, tn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_records(self.h, C.byref(mm), C.byref(mn), C.byref(tm), C.byref(tn))
+        return mm.value, mn.value, tm.value, tn.value
+
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
         best, med = C.c_double(0), C.c_double(0)
@@ -1817,6 +1940,21 @@ class DeviceCodec:
                                            int(pad), int(cap_pieces), ptr(out), out.numel() if out is not None else 0,
                                            d_row_lengths.data_ptr(), d_row_status.data_ptr(), d_need.data_ptr(), self._status.data_ptr(),
                                            self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def records_async(self, index, delim: int, flags: int, cap_records: int, d_rec_items, d_rec_offsets, d_rec_lengths, d_item_first_record,
+                      d_need, d_status=None) -> None:
+        """tsqa_records_async on the current stream, nothing waited for: the records of the data behind `index` for the delimiter
+        byte `delim` (flags: RECORDS_KEEP_DELIM | RECORDS_FLAT).  The records numbered below cap_records go to d_rec_items (int32,
+        may be None), d_rec_offsets and d_rec_lengths (int64; both None with cap_records 0: the call only measures);
+        d_item_first_record (int64, items + 1) and d_need (int64, 2: the count of all records, the largest length) are always
+        complete.  The status -- 0, 6 more records than cap_records, 4 a refused sized index, 5 a malformed stream -- lands in
+        d_status (int32, 1) or, when None, in status()."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self.L.tsqa_records_async(self.h, index.h, int(delim), int(flags), int(cap_records), ptr(d_rec_items), ptr(d_rec_offsets),
+                                       ptr(d_rec_lengths), d_item_first_record.data_ptr(), d_need.data_ptr(),
+                                       (self._status if d_status is None else d_status).data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 

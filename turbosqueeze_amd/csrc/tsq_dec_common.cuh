@@ -60,6 +60,7 @@ struct SymCfg {
     static constexpr uint32_t SWORDS = (S + SPAD + 16) / 16;   // 16-byte words of stream staged per chunk
 };
 static_assert(SymCfg::R % 16 == 0, "ring phase");
+static_assert(SymCfg::R == 77888 && SymCfg::R % 64 == 0, "the record scan skews the ring by out_at & 63: the 64-position grid of the bit map falls on the ring's");
 static_assert(SymCfg::OUTC == 12 * SymCfg::T, "twelve bytes per lane");
 static_assert(SymCfg::S % SymCfg::T == 0 && SymCfg::SWORDS <= SymCfg::T, "lane counts");
 static_assert(SymCfg::MAXG <= SymCfg::T / 2 && SymCfg::MAXG % SymCfg::HOP == 0 && SymCfg::MAXG >= SymCfg::S / 13 + 2 * SymCfg::HOP, "group table");
@@ -555,6 +556,45 @@ __device__ __forceinline__ void flush_window(const uint8_t* lds, uint8_t* out, c
     if (a >= b) return;
     uint32_t at = im.at + (a - im.op); at -= at >= C::R ? C::R : 0u;
     flush_image<L>(lds, out, Image{a - lo, b - a, at}, first_tid, n_threads);
+}
+
+// ---------------- P7 of a record scan (dec_mark_kernel): no byte of the image goes to HBM.  Its bytes are compared with `delim`, and
+// one BIT per byte goes to a bit map that the caller has cleared: bit G & 63 of 64-bit word (G >> 6) + blk stands for position G
+// of the concatenation, G = base + p for byte p of block blk (base: the block's out_at).  The block's words are its own: the next
+// block's first word, ((base + len) >> 6) + blk + 1, lies above this block's last, ((base + len - 1) >> 6) + blk.  The ring's skew
+// is base & 63, so the image is walked as flush_image walks it, by the aligned 16-byte ring words it touches, and ring word and
+// 16-bit cell of the map coincide; the ring's size is a multiple of 16, so no cell wraps.  A lane masks its word's bytes outside
+// the image (the first and last cell are shared with the neighbouring images, whose lanes bring the other bits) and ORs the mask
+// into the 32-bit half that holds the cell -- only where a bit is set, which in text is one cell in four.  A cell at or past
+// map_words (a descriptor that lies about its place) is not written.  No barrier inside.
+template <class L>
+__device__ __forceinline__ void flush_mark(const uint8_t* lds, uint32_t* map32, uint64_t map_words, uint64_t base, uint32_t blk, const Image& im,
+                                           uint32_t delim, uint32_t first_tid, uint32_t n_threads)
+{
+    using C = SymCfg;
+    const uint32_t tid = threadIdx.x;
+    const uint8_t* const ring = lds + L::ring;
+    if (im.len == 0 || tid < first_tid) return;
+    const uint32_t skew = im.at & 15u, cells = (skew + im.len + 15u) >> 4;
+    const uint32_t c0 = im.at & ~15u;
+    const uint64_t g0 = (base + im.op) & ~15ull;                                // position of the first cell's byte 0 (base + op = at mod 16)
+    const uint32_t splat = delim * 0x01010101u;
+    for (uint32_t w = tid - first_tid; w < cells; w += n_threads) {
+        uint32_t a = c0 + (w << 4); a -= a >= C::R ? C::R : 0u;
+        const uint4 x = *reinterpret_cast<const uint4*>(ring + a);
+        const uint32_t v[4] = {x.x ^ splat, x.y ^ splat, x.z ^ splat, x.w ^ splat};
+        uint32_t m = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            // bit 7 of every byte of v[i] that is zero, exactly (no borrow runs from byte to byte), then the four bits side by side
+            const uint32_t z = ~(((v[i] & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v[i] | 0x7F7F7F7Fu);
+            m |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4u * i);
+        }
+        const uint32_t lo = w == 0u ? skew : 0u, left = skew + im.len - (w << 4), hi = left < 16u ? left : 16u;   // the image's bytes [lo, hi) of the cell
+        m &= (0xFFFFu << lo) & (0xFFFFu >> (16u - hi));
+        const uint64_t g = g0 + ((uint64_t)w << 4), word = (g >> 6) + blk;
+        if (m != 0u && word < map_words) atomicOr(map32 + 2u * word + ((uint32_t)(g >> 5) & 1u), m << ((uint32_t)g & 16u));
+    }
 }
 
 }  // namespace tsq

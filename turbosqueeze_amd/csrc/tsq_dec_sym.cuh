@@ -46,7 +46,7 @@ struct BlockGroup {
     uint32_t block, first, count, hi;
 };
 
-enum DecMode : int { kDecWhole, kDecWindow, kDecGroup };
+enum DecMode : int { kDecWhole, kDecWindow, kDecGroup, kDecMark };
 
 // ---------------- P7 of a record read: the image's bytes go to every item of the group that they meet (byte p of the block to
 // out[it.out_at + p - it.lo]).  The items are sorted by lo, so those that meet the image are a run of the list that only moves
@@ -174,13 +174,16 @@ __device__ __forceinline__ void flush_group(const uint8_t* lds, uint8_t* out, co
 // (dec_range_kernel): item blockIdx.x -- only the bytes [lo, hi) of its block are written, and the chunk loop ends with the chunk
 // that reaches hi.  kDecGroup (dec_group_kernel): group blockIdx.x -- its block is decoded up to the group's hi, and every chunk's
 // bytes go to each of the group's items that they meet (flush_group).  Every chunk that is decoded is validated as in the
-// whole-block decode.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
+// whole-block decode.  kDecMark (dec_mark_kernel): block blockIdx.x, whole, and nothing of it is written: `outbuf` is the bit map of
+// flush_mark, map_words long, and every chunk's image is compared with `delim` there.  Every use of that mode sits behind
+// `if constexpr`, so the other three are compiled as they were.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
 // inlined function would give dec_sym_kernel other code than before.)
 template <DecMode kMode>
 __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
-                                                 uint8_t* outbuf, int32_t* status, const BlockGroup* groups = nullptr, uint32_t n_items = 0u)
+                                                 uint8_t* outbuf, int32_t* status, const BlockGroup* groups = nullptr, uint32_t n_items = 0u,
+                                                 [[maybe_unused]] uint32_t delim = 0u, [[maybe_unused]] uint64_t map_words = 0ull)
 {
-    constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup;
+    constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup, kMark = kMode == kDecMark;
     using C = SymCfg;
     using L = SymLds;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -228,11 +231,13 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     const uint8_t* const in = container + f.stream_at;
     // window: `out` is where byte lo goes; byte p of the block goes to out + (p - lo)
     // (group: every item has a destination of its own in outbuf; no skew of the ring can serve them all)
-    uint8_t* const out = kGroup ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
+    // (mark: outbuf is the bit map, and no byte of the block has a destination)
+    uint8_t* const out = kGroup || kMark ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
     const uint32_t in_len = f.stream_len, size = f.out_len, ext = f.ext;
     // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM (window: of
     // the block's virtual base out - lo)
-    const uint32_t oskew = kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
+    // (mark: the 64-position grid of the concatenation falls on the ring's 64-byte grid, flush_mark)
+    const uint32_t oskew = kMark ? (uint32_t)(f.out_at & 63u) : kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
 
 #ifdef TSQ_STATS
     const uint32_t lane = tid & 63u, wid = tid >> 6;
@@ -271,7 +276,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         // HBM meanwhile (P7).  (measured in round 5: a build without this flush runs 4.558 against 4.553 ms, the flush beside P3's
         // chain instead 4.572 -- it hides completely)
         if (tid >= C::T / 2) {
-            if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, C::T / 2, C::T / 2);
+            if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, C::T / 2, C::T / 2);
+            else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, C::T / 2, C::T / 2);
             else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
             else flush_image<L>(lds, out, prev, C::T / 2, C::T / 2);
         }
@@ -335,7 +341,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     if constexpr (kGroup) { if (tid == C::T / 2) misc[12] = gcur.cur; }
     __syncthreads();
     if constexpr (kGroup) { if (tid < C::T / 2) gcur.cur = misc[12]; }
-    if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, 0, C::T);
+    if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, 0, C::T);
+    else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, 0, C::T);
     else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
     else flush_image<L>(lds, out, prev, 0, C::T);
 #ifdef TSQ_STATS
@@ -377,6 +384,18 @@ __global__ __launch_bounds__(1024) void dec_group_kernel(const uint8_t* __restri
                                                          uint8_t* __restrict__ outbuf, int32_t* __restrict__ status)
 {
     sym_decode_block<kDecGroup>(container, frames, n_frames, items, outbuf, status, groups, n_items);
+}
+
+// The record scan (tsqa_records_async): one workgroup per block of the index, the block decoded whole and validated as in
+// dec_sym_kernel, and nothing of it written: bit G of `map` (flush_mark's layout, map_words 64-bit words, cleared by the caller) is
+// set where byte G of the index's data equals `delim`.  verdict (may be NULL): a sized index's word; where it is nonzero no
+// descriptor is read.
+__global__ __launch_bounds__(1024) void dec_mark_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                        const int32_t* __restrict__ verdict, uint32_t delim, uint64_t* __restrict__ map,
+                                                        uint64_t map_words, int32_t* __restrict__ status)
+{
+    if (verdict && *verdict != 0) return;
+    sym_decode_block<kDecMark>(container, frames, 0u, nullptr, reinterpret_cast<uint8_t*>(map), status, nullptr, 0u, delim, map_words);
 }
 
 }  // namespace tsq

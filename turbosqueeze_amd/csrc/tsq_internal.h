@@ -9,7 +9,7 @@
 
 #include "../../include/turbosqueeze_amd.h"
 
-namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; struct CutRange; struct GatherRange; struct GatherWords; struct RangeItem; struct BlockGroup; }
+namespace tsq { struct FrameInfo; struct BatchItem; struct EncBatchBlock; struct CutRange; struct GatherRange; struct GatherWords; struct RangeItem; struct BlockGroup; struct RecordBlock; struct RecordWords; }
 
 struct tsqa_ctx;
 
@@ -143,6 +143,13 @@ struct tsqa_ctx {
     tsqa_scratch<uint64_t> gather_places;
     tsqa_scratch<uint64_t> gather_row_groups;
     size_t gather_sort_n = 0, gather_sort_bytes = 0;
+    // tsqa_records_async (tsq_records.cuh): the bit map of the delimiters, (total >> 6) + n_blocks + 1 words -- an eighth of the
+    // data and 8 bytes per block --, per block its record starts and edges, per group of 256 blocks their sum and their last edge
+    // (two halves of records_groups), and the call's words
+    tsqa_scratch<uint64_t> records_map;
+    tsqa_scratch<tsq::RecordBlock> records_blocks;
+    tsqa_scratch<uint64_t> records_groups;
+    tsqa_scratch<tsq::RecordWords> records_words;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     tsqa_scratch<uint32_t> duo_flags;          // and their progress counters
@@ -156,11 +163,11 @@ struct tsqa_ctx {
     // 2 whole compress call (encode + container pack), 3 whole decompress call (frame walk + decode), 4 the join's copy kernel,
     // 5 the cut's copy kernel (tsqa_cut_async and tsqa_cut_items_async), 6 the gather's planner (its launches in front of the decode), 7 the decode kernel of a record read
     // (tsqa_decompress_item_ranges_async, tsqa_gather_async and tsqa_gather_rows_async, whose planner is kind 6 too), 8 the pad kernel
-    // of tsqa_gather_rows_async.
-    static constexpr int kProfKinds = 9, kProfPairs = 256;
+    // of tsqa_gather_rows_async, 9 the mark decode of tsqa_records_async (dec_mark_kernel), 10 its table launches (tsq_records.cuh).
+    static constexpr int kProfKinds = 11, kProfPairs = 256;
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
-    uint32_t prof_used[kProfKinds] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t prof_used[kProfKinds] = {0};
 
     void set_error(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     // what a growing reserve waits for before it frees scratch: the context's own stream and `s`, the stream the call was given
@@ -173,6 +180,7 @@ struct tsqa_ctx {
     int reserve_join(size_t n_items);
     int reserve_cut(size_t n_ranges);
     int reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups);
+    int reserve_records(size_t map_words, size_t n_blocks);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]

@@ -21,6 +21,7 @@
 #include "tsq_gather.cuh"
 #include "tsq_gather_sort.h"
 #include "tsq_rows.cuh"
+#include "tsq_records.cuh"
 
 #include <algorithm>
 #include <cstdarg>
@@ -298,6 +299,19 @@ int tsqa_ctx::reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_grou
            gather_words.grow(this, 1) && gather_places.grow(this, want) && gather_row_groups.grow(this, want / 256) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the record scan (tsq_internal.h): the bit map as many words as the call names -- it is the one buffer here that
+// follows the data's size, an eighth of it, and is not doubled --, the per-block entries doubled from 256 and two words per group of
+// 256 blocks with them.
+int tsqa_ctx::reserve_records(size_t map_words, size_t n_blocks)
+{
+    (void)hipSetDevice(device);
+    const size_t blocks = doubled(256, n_blocks), groups = 2 * (blocks / 256);
+    if (!records_map.needs(map_words) && !records_blocks.needs(blocks) && !records_groups.needs(groups) && !records_words.needs(1)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return records_map.grow(this, map_words) && records_blocks.grow(this, blocks) && records_groups.grow(this, groups) &&
+           records_words.grow(this, 1) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -405,6 +419,16 @@ extern "C" int tsqa_profile_read_rows(tsqa_ctx* c, double* pad_ms, uint32_t* pad
     (void)hipSetDevice(c->device);
     if (c->prof_pool.empty()) { if (pad_ms) *pad_ms = 0; if (pad_n) *pad_n = 0; return TSQA_OK; }
     drain_events(c, 8, pad_ms, pad_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_records(tsqa_ctx* c, double* mark_ms, uint32_t* mark_n, double* table_ms, uint32_t* table_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (mark_ms) *mark_ms = 0; if (mark_n) *mark_n = 0; if (table_ms) *table_ms = 0; if (table_n) *table_n = 0; return TSQA_OK; }
+    drain_events(c, 9, mark_ms, mark_n);
+    drain_events(c, 10, table_ms, table_n);
     return TSQA_OK;
 }
 
@@ -2265,6 +2289,115 @@ extern "C" int tsqa_gather(tsqa_ctx* c, const tsqa_index* idx, const uint32_t* d
     TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "gather");
+}
+
+// ---- record tables from a delimiter byte: a decode that writes one bit per byte, then a count, a scan and a placement (tsq_records.cuh) ----
+
+extern "C" int tsqa_plan_records(const void* data, const uint64_t* item_at, const int32_t* item_status, uint32_t n_items, uint32_t delim,
+                                 uint32_t flags, uint64_t cap_records, uint32_t* rec_items, uint64_t* rec_offsets, uint64_t* rec_lengths,
+                                 uint64_t* item_first_record, uint64_t* need)
+{
+    if (!item_at || !item_first_record || !need || n_items == 0 || delim > 255u || (flags & ~(TSQA_RECORDS_KEEP_DELIM | TSQA_RECORDS_FLAT)) != 0u)
+        return TSQA_ERR_ARG;
+    if (cap_records > 0 && (!rec_offsets || !rec_lengths)) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_at[i + 1] < item_at[i]) return TSQA_ERR_ARG;
+    if (!data && item_at[n_items] != item_at[0]) return TSQA_ERR_ARG;
+    const uint8_t* const bytes = static_cast<const uint8_t*>(data);
+    const uint64_t keep = flags & TSQA_RECORDS_KEEP_DELIM ? 1u : 0u;
+    uint64_t no = 0, longest = 0;
+    auto put = [&](uint32_t item, uint64_t offset, uint64_t len) {
+        if (len > longest) longest = len;
+        if (no < cap_records) { if (rec_items) rec_items[no] = item; rec_offsets[no] = offset; rec_lengths[no] = len; }
+        ++no;
+    };
+    for (uint32_t i = 0; i < n_items; ++i) {
+        item_first_record[i] = no;
+        const uint64_t a = item_at[i], e = item_at[i + 1], origin = flags & TSQA_RECORDS_FLAT ? 0ull : a;
+        if (a == e || (item_status && item_status[i] != 0)) continue;
+        uint64_t start = a;
+        while (start < e) {
+            const uint8_t* const hit = static_cast<const uint8_t*>(memchr(bytes + start, (int)delim, (size_t)(e - start)));
+            if (!hit) { put(i, start - origin, e - start); break; }
+            const uint64_t p = (uint64_t)(hit - bytes);
+            put(i, start - origin, p - start + keep);
+            start = p + 1;                                   // (a terminator at the item's last byte starts no record)
+        }
+    }
+    item_first_record[n_items] = no;
+    need[0] = no; need[1] = longest;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_records_async(tsqa_ctx* c, const tsqa_index* idx, uint32_t delim, uint32_t flags, uint64_t cap_records, uint32_t* d_rec_items,
+                                  uint64_t* d_rec_offsets, uint64_t* d_rec_lengths, uint64_t* d_item_first_record, uint64_t* d_need,
+                                  int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_item_first_record || !d_need || !d_status) { c->set_error("records: null pointer"); return TSQA_ERR_ARG; }
+    if (delim > 255u) { c->set_error("records: delim %u is no byte value", delim); return TSQA_ERR_ARG; }
+    if ((flags & ~(TSQA_RECORDS_KEEP_DELIM | TSQA_RECORDS_FLAT)) != 0u) { c->set_error("records: unknown flags 0x%x", flags); return TSQA_ERR_ARG; }
+    if (cap_records > 0 && (!d_rec_offsets || !d_rec_lengths)) { c->set_error("records: cap_records of %llu with a NULL offsets or lengths table", (unsigned long long)cap_records); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("records: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    // (the host sizes the bit map from the total and the block count, which it does not have before the fetch)
+    if (idx->pending_items != 0u) { c->set_error("records: %s", kNeedsFetch); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    const uint32_t n_blocks = idx->n_blocks, n_items = tsqa_index_items(idx);
+    const uint32_t item_groups = (uint32_t)(((uint64_t)n_items + 1u + 255u) / 256u);
+    if (n_blocks == 0) {
+        TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+        TSQ_HIP(c, hipMemsetAsync(d_need, 0, 2 * sizeof(uint64_t), s));
+        hipLaunchKernelGGL(records_clear_kernel, dim3(item_groups), dim3(256), 0, s, d_item_first_record, n_items);
+        TSQ_HIP(c, hipGetLastError());
+        return TSQA_OK;
+    }
+    const uint64_t map_words = (idx->total >> 6) + n_blocks + 1u;
+    if (int rc = c->reserve_records((size_t)map_words, n_blocks)) return rc;
+    uint64_t* const map = c->records_map;
+    RecordBlock* const blocks = c->records_blocks;
+    const uint32_t n_groups = (n_blocks + kRecordsGroup - 1u) / kRecordsGroup;
+    uint64_t* const group_sum = c->records_groups;
+    uint64_t* const group_edge = group_sum + c->records_groups.cap / 2;
+    RecordWords* const words = c->records_words;
+    const FrameInfo* const frames = idx->frames;
+    const int32_t* const verdict = idx->verdict;
+    const uint64_t* const item_first = idx->d_item_first;
+    TSQ_HIP(c, hipMemsetAsync(words, 0, sizeof(RecordWords), s));
+    TSQ_HIP(c, hipMemsetAsync(map, 0, (size_t)map_words * sizeof(uint64_t), s));
+    ProfSpan mark(c, 9, s);
+    const int rc = launch_read_kernel<dec_mark_kernel>(c, n_blocks, s, idx->container, frames, verdict, delim, map, map_words, &words->stream);
+    if (rc) { mark.cancel(); return rc; }
+    mark.end();
+    ProfSpan table(c, 10, s);
+    hipLaunchKernelGGL(records_count_kernel, dim3(n_blocks), dim3(256), 0, s, frames, n_blocks, idx->total, verdict, item_first, n_items,
+                       static_cast<const uint64_t*>(map), map_words, blocks);
+    hipLaunchKernelGGL(records_sum_kernel, dim3(n_groups), dim3(256), 0, s, blocks, n_blocks, group_sum, group_edge);
+    hipLaunchKernelGGL(records_scan_kernel, dim3(1), dim3(256), 0, s, group_sum, group_edge, n_groups, verdict, cap_records, d_need, words);
+    hipLaunchKernelGGL(records_place_kernel, dim3(n_groups), dim3(256), 0, s, blocks, n_blocks, static_cast<const uint64_t*>(group_sum),
+                       static_cast<const uint64_t*>(group_edge));
+    hipLaunchKernelGGL(records_items_kernel, dim3(item_groups), dim3(256), 0, s, static_cast<const RecordBlock*>(blocks), n_blocks, item_first, n_items,
+                       static_cast<const uint64_t*>(d_need), d_item_first_record);
+    hipLaunchKernelGGL(records_emit_kernel, dim3(n_blocks), dim3(256), 0, s, frames, verdict, static_cast<const uint64_t*>(map), map_words,
+                       static_cast<const RecordBlock*>(blocks), flags, cap_records, d_rec_items, d_rec_offsets, d_rec_lengths, d_need);
+    hipLaunchKernelGGL(records_close_kernel, dim3(1), dim3(1), 0, s, static_cast<const RecordWords*>(words), d_status);
+    table.end();
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_records(tsqa_ctx* c, const tsqa_index* idx, uint32_t delim, uint32_t flags, uint64_t cap_records, uint32_t* d_rec_items,
+                            uint64_t* d_rec_offsets, uint64_t* d_rec_lengths, uint64_t* d_item_first_record, uint64_t* d_need, int32_t* d_status,
+                            void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_records_async(c, idx, delim, flags, cap_records, d_rec_items, d_rec_offsets, d_rec_lengths, d_item_first_record, d_need,
+                                    d_status, s)) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "records");
 }
 
 // ---- gather into fixed-stride padded rows: the same ranges, row k at k * row_stride, the tails filled (tsq_rows.cuh) ----
