@@ -193,6 +193,8 @@ int tsqa_profile_read_gather(tsqa_ctx *ctx, double *plan_ms, uint32_t *plan_call
 int tsqa_profile_read_rows(tsqa_ctx *ctx, double *pad_ms, uint32_t *pad_launches);
 /* tsqa_records_async: its mark decode (the decoder that writes one bit per byte) and, per call, its table launches together. */
 int tsqa_profile_read_records(tsqa_ctx *ctx, double *mark_ms, uint32_t *mark_launches, double *table_ms, uint32_t *table_calls);
+/* tsqa_find_async: its find decode (the decoder that compares with the needle) and, per call, its seam and table launches together. */
+int tsqa_profile_read_find(tsqa_ctx *ctx, double *find_ms, uint32_t *find_launches, double *table_ms, uint32_t *table_calls);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -1012,6 +1014,62 @@ int tsqa_records_async(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t delim, uin
 int tsqa_records(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t delim, uint32_t flags, uint64_t cap_records,
                  uint32_t *d_rec_items, uint64_t *d_rec_offsets, uint64_t *d_rec_lengths,
                  uint64_t *d_item_first_record, uint64_t *d_need, int32_t *d_status, void *hip_stream);
+
+/*
+ * Find a byte string: where a needle of 1 .. TSQA_FIND_MAX_NEEDLE bytes occurs in an index's data, made on the device with NO
+ * decoded copy.  Every block is decoded and validated as in the whole-block decode, and its bytes are compared with the needle
+ * instead of being stored: the one thing written per hit is a bit, into the map that tsqa_records_async uses (an eighth of the
+ * data and 8 bytes per block, cleared by every call), and 32 bytes per block keep the blocks' first and last 15 bytes, from
+ * which a small launch decides the hits that lie across block seams.  The records' scan over the map makes the tables.  Any
+ * index but a batch index made on the device and not yet fetched.
+ *
+ * The rule.  The index has n_items items.  A container index has one item.  Item i has data D_i of T_i bytes.  The needle has m
+ * bytes, 1 <= m <= TSQA_FIND_MAX_NEEDLE.
+ *   - A HIT is a pair (i, p) with p + m <= T_i and D_i[p .. p + m) == needle.
+ *   - Overlapping hits all count: "aa" occurs twice in "aaa".
+ *   - A hit never runs from one item into the next.
+ *   - A refused item, whose item status is nonzero, has no hits.
+ *   - Hits are numbered item by item in item order, and by p inside an item.
+ *   - TSQA_FIND_FLAT (flag 2, the value of TSQA_RECORDS_FLAT): offsets count from the start of the index's whole data.  Without the
+ *     flag they count from the item's own start.
+ * Outputs:
+ *   - d_item_first_hit has n_items + 1 entries.  It is the exclusive sum of the items' hit counts.  Its last entry is the count of
+ *     all hits.  It is always complete, whatever cap_hits.
+ *   - d_need[0] is that count, the cap_hits a retry needs.  d_need is ONE word.
+ *   - Hits numbered below cap_hits are written to d_hit_offsets (the hit's first byte) and d_hit_items (may be NULL).  They are a
+ *     prefix.  Nothing of a table is written at or beyond cap_hits.
+ *   - d_hit_offsets may be NULL together with cap_hits == 0.  That call only measures.
+ * Status: *d_status is TSQA_OK when every hit fits.  It is TSQA_ERR_OVERFLOW when the count of all hits exceeds cap_hits, with the
+ * prefix written.  It is TSQA_ERR_FORMAT for a sized index whose verdict is nonzero.  Then no descriptor is read, every entry of
+ * d_item_first_hit is 0 and the need word is 0.  It is raised to TSQA_ERR_STREAM when a decoder met a malformed stream (while it
+ * is TSQA_ERR_OVERFLOW it stays that, as in tsqa_records_async).  Then the tables' contents are undefined and nothing outside
+ * them was written.
+ * The needle is read on the host during the call and travels as kernel arguments: there is no upload and no wait, and the
+ * caller's buffer may be reused as soon as the call returns.
+ * Trust and alignment: as tsqa_records_async.
+ * TSQA_ERR_ARG before anything is enqueued for: a NULL among idx, needle, d_item_first_hit, d_need and d_status; needle_len == 0 or
+ * needle_len > TSQA_FIND_MAX_NEEDLE; unknown flags; cap_hits > 0 with a NULL offsets table; an index of another device; an index made
+ * on the device and not yet fetched.  An index of 0 blocks clears the status, the need word and the first-hit table.  Calls that
+ * share a context share its scratch -- a records call and a find call share the map --: order them on one stream.
+ *
+ * tsqa_find: the same, then waits for hip_stream and returns *d_status.
+ *
+ * tsqa_plan_find: host only, the same rule on decoded bytes on the host, with tsqa_plan_records' shape: data is the concatenation,
+ *   item_at[n_items + 1] holds the items' starts in it, item_status may be NULL.  Fills hit_items (may be NULL) and hit_offsets
+ *   below cap_hits, item_first_hit[n_items + 1] and need[1].  Returns TSQA_OK whatever fits; TSQA_ERR_ARG for NULL or unordered
+ *   tables, n_items == 0, a bad needle length or bad flags.
+ */
+#define TSQA_FIND_FLAT 2u
+#define TSQA_FIND_MAX_NEEDLE 16u
+int tsqa_plan_find(const void *data, const uint64_t *item_at, const int32_t *item_status, uint32_t n_items,
+                   const void *needle, uint32_t needle_len, uint32_t flags, uint64_t cap_hits,
+                   uint32_t *hit_items, uint64_t *hit_offsets, uint64_t *item_first_hit, uint64_t *need);
+int tsqa_find_async(tsqa_ctx *ctx, const tsqa_index *idx, const void *needle, uint32_t needle_len, uint32_t flags,
+                    uint64_t cap_hits, uint32_t *d_hit_items, uint64_t *d_hit_offsets,
+                    uint64_t *d_item_first_hit, uint64_t *d_need, int32_t *d_status, void *hip_stream);
+int tsqa_find(tsqa_ctx *ctx, const tsqa_index *idx, const void *needle, uint32_t needle_len, uint32_t flags,
+              uint64_t cap_hits, uint32_t *d_hit_items, uint64_t *d_hit_offsets,
+              uint64_t *d_item_first_hit, uint64_t *d_need, int32_t *d_status, void *hip_stream);
 
 /*
  * The index of a packed batch from its tables in DEVICE memory, with no host wait: the last step of packed compress -> index ->

@@ -13,6 +13,9 @@
 //   tsq_cli r <in.tsq> [delim]              records: the container goes to the device and the record count and the longest
 //                                           record for the delimiter byte (default 10, a newline) are printed
 //                                           (tsqa_records with no tables: nothing is decoded into memory).
+//   tsq_cli f <in.tsq> <needle>             find: the container goes to the device and the number of places at which the bytes
+//                                           of <needle> (1 .. 16) occur, and the first place's offset, are printed (tsqa_find
+//                                           with a table of one entry: nothing is decoded into memory).
 // Unlike the reference's benchmark (clock() summed over threads, divided by 1e5) this reports
 // wall-clock MB/s.
 #include <chrono>
@@ -39,7 +42,8 @@ static int usage()
     fprintf(stderr, "usage: tsq_cli c <in> <out> [--no-ext] | d <in> <out> | b [file | --synthetic BYTES] [--no-ext] [--reps N]\n"
                     "       tsq_cli bf <in> <workdir> [--no-ext] [--reps N]   (file -> file -> file with warm contexts)\n"
                     "       tsq_cli x <in.tsq> <offset> <length> <out>       (uncompressed bytes [offset, offset + length))\n"
-                    "       tsq_cli r <in.tsq> [delim]                       (record count and longest record for a delimiter byte, default 10)\n");
+                    "       tsq_cli r <in.tsq> [delim]                       (record count and longest record for a delimiter byte, default 10)\n"
+                    "       tsq_cli f <in.tsq> <needle>                      (how often the needle's bytes, 1 .. 16, occur, and where first)\n");
     return 2;
 }
 
@@ -118,6 +122,46 @@ static int count_records(const std::string& in, uint32_t delim)
     return 0;
 }
 
+// f: how often a byte string occurs in a container's data and where it occurs first, found on the device
+static int find_needle(const std::string& in, const std::string& needle)
+{
+    FILE* f = fopen(in.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", in.c_str()); return 1; }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    std::vector<uint8_t> blob(sz > 0 ? (size_t)sz : 0);
+    const bool read_ok = fread(blob.data(), 1, blob.size(), f) == blob.size();
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "short read\n"); return 1; }
+    tsqa_ctx* ctx = nullptr;
+    if (tsqa_create(-1, &ctx) != TSQA_OK) { fprintf(stderr, "no usable MI355X (gfx950) device\n"); return 1; }
+    void *d_in = nullptr, *d_words = nullptr;                  // d_words: item_first_hit[2], need, the first hit's offset, status
+    tsqa_index* idx = nullptr;
+    uint64_t words[5] = {0, 0, 0, 0, 0};
+    int rc = TSQA_OK;
+    if (hipMalloc(&d_in, blob.size() ? blob.size() : 1) != hipSuccess || hipMalloc(&d_words, sizeof(words)) != hipSuccess ||
+        hipMemset(d_words, 0, sizeof(words)) != hipSuccess || hipMemcpy(d_in, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "device memory: %s\n", hipGetErrorString(hipGetLastError()));
+        rc = TSQA_ERR_HIP;
+    }
+    if (rc == TSQA_OK && (rc = tsqa_index_create(ctx, d_in, blob.size(), &idx)) == TSQA_OK) {
+        uint64_t* const w = static_cast<uint64_t*>(d_words);
+        rc = tsqa_find(ctx, idx, needle.data(), (uint32_t)needle.size(), TSQA_FIND_FLAT, 1, nullptr, w + 3, w, w + 2, reinterpret_cast<int32_t*>(w + 4),
+                       nullptr);
+        if (rc == TSQA_ERR_OVERFLOW) rc = TSQA_OK;             // (a table of one entry: every hit but the first is "too many")
+    }
+    if (rc != TSQA_OK && rc != TSQA_ERR_HIP) fprintf(stderr, "find failed (%d): %s\n", rc, tsqa_last_error(ctx));
+    if (rc == TSQA_OK && hipMemcpy(words, d_words, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess) rc = TSQA_ERR_HIP;
+    const uint64_t total = idx ? tsqa_index_total(idx) : 0;
+    tsqa_index_destroy(idx);
+    (void)hipFree(d_in); (void)hipFree(d_words);
+    tsqa_destroy(ctx);
+    if (rc != TSQA_OK) return 1;
+    if (words[2] != 0) printf("{\"bytes\": %llu, \"needle_bytes\": %zu, \"hits\": %llu, \"first_hit\": %llu}\n", (unsigned long long)total, needle.size(),
+                              (unsigned long long)words[2], (unsigned long long)words[3]);
+    else printf("{\"bytes\": %llu, \"needle_bytes\": %zu, \"hits\": 0, \"first_hit\": null}\n", (unsigned long long)total, needle.size());
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return usage();
@@ -161,6 +205,11 @@ int main(int argc, char** argv)
         const unsigned long delim = pos.size() == 2 ? strtoul(pos[1].c_str(), nullptr, 10) : 10ul;
         if (delim > 255ul) { fprintf(stderr, "delim is one byte value, 0..255\n"); return 2; }
         return count_records(pos[0], (uint32_t)delim);
+    }
+    if (mode == "f") {
+        if (pos.size() != 2) return usage();
+        if (pos[1].empty() || pos[1].size() > TSQA_FIND_MAX_NEEDLE) { fprintf(stderr, "the needle is 1 .. %u bytes\n", TSQA_FIND_MAX_NEEDLE); return 2; }
+        return find_needle(pos[0], pos[1]);
     }
     if (mode == "bf") {
         // file -> .tsq file -> file through the _MT API's file modes with the contexts allocated once (as sample/main.cpp:71-95 keeps

@@ -247,6 +247,13 @@ def lib(ab=False) -> C.CDLL:
         f.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.tsqa_profile_read_records.restype = C.c_int
     L.tsqa_profile_read_records.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_plan_find.restype = C.c_int
+    L.tsqa_plan_find.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp]
+    for f in (L.tsqa_find_async, L.tsqa_find):
+        f.restype = C.c_int
+        f.argtypes = [vp, vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp]
+    L.tsqa_profile_read_find.restype = C.c_int
+    L.tsqa_profile_read_find.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -592,6 +599,59 @@ class RangeIndex:
                 raise TsqError(st, "records: the device reported a refused index (4) or a malformed stream (5)")
         return table
 
+    def find(self, needle: bytes, flat: bool = False, cap_hits=None, sync: bool = True) -> "HitTable":
+        """Where the byte string `needle` (1 .. FIND_MAX_NEEDLE bytes) occurs in the data (DeviceCodec.find_async): every p with
+        data[p : p + len(needle)] == needle inside one item, overlapping occurrences included.  The data is decoded and compared on
+        the device; no decoded copy is made -- the scratch is a bit per byte and 32 bytes per block.  flat: offsets count from the
+        start of the whole data, else from the hit's own item.  -> a HitTable.  cap_hits None: the call is run twice -- once with
+        no tables, which only measures, then, after ONE host read of the count, with tables of exactly that many entries.
+        cap_hits given: ONE enqueue on the current stream with no host read; the hits below it are written, and table.status
+        reads 6 when there are more (table.need[0] says how many).  sync=False with cap_hits: nothing is waited for.  Otherwise
+        the call is waited for and a refused index (4) or a malformed stream (5) raises TsqError."""
+        codec, torch = self.codec, self.codec.torch
+        needle = bytes(needle)
+        flags = FIND_FLAT if flat else 0
+        n_items = int(self.L.tsqa_index_items(self.h))
+        i64 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int64, device=codec.device)
+        item_first, need = i64(n_items + 1)[:n_items + 1], i64(1)
+        status = torch.empty(1, dtype=torch.int32, device=codec.device)
+        measured = cap_hits is None
+        if measured:
+            codec._join()
+            codec.find_async(self, needle, flags, 0, None, None, item_first, need, status)
+            codec._join()
+            cap_hits = int(need[0].item())
+        cap_hits = int(cap_hits)
+        offsets = i64(cap_hits)[:cap_hits]
+        items = torch.empty(max(cap_hits, 1), dtype=torch.int32, device=codec.device)[:cap_hits]
+        codec._join()
+        codec.find_async(self, needle, flags, cap_hits, items if cap_hits else None, offsets if cap_hits else None, item_first, need, status)
+        codec._join()
+        table = HitTable(self, offsets, items, item_first, need, status, flat, len(needle))
+        if sync or measured:
+            st = int(status.item())
+            if st not in (0, 6):
+                raise TsqError(st, "find: the device reported a refused index (4) or a malformed stream (5)")
+        return table
+
+
+class HitTable:
+    """What RangeIndex.find gives: offsets (int64, each hit's first byte) and items (int32) of cap_hits entries, of which the first
+    min(n, cap_hits) are hits; item_first (int64, items + 1: each item's first hit number, then the count); need (int64, 1: the count
+    of all hits) and status (int32: 0, 6 when there are more hits than entries, 4, 5) -- all CUDA tensors, valid behind the stream the
+    call was enqueued on.  needle_len is the needle's length; n reads `need` on the host (it waits)."""
+
+    def __init__(self, index, offsets, items, item_first, need, status, flat: bool, needle_len: int):
+        self.index, self.offsets, self.items, self.item_first, self.need, self.status, self.flat, self.needle_len = (
+            index, offsets, items, item_first, need, status, flat, needle_len)
+        self._n = None
+
+    @property
+    def n(self) -> int:
+        if self._n is None:
+            self._n = int(self.need[0].item())
+        return self._n
+
 
 class RecordTable:
     """What RangeIndex.records gives: offsets, lengths (int64) and items (int32) of cap_records entries, of which the first
@@ -627,8 +687,63 @@ class RecordTable:
         return self.index._gather_rows(d_items, self.offsets[sel].contiguous(), self.lengths[sel].contiguous(), row_stride, pad, truncate, out,
                                        cap_pieces, row_status)
 
+    def containing(self, hits: "HitTable"):
+        """The sorted unique numbers of the records that hold a whole hit of `hits`: offsets[r] <= hit and hit + needle_len <=
+        offsets[r] + lengths[r] (torch only: a searchsorted of the hits in the records' flat offsets, which grow with the record
+        number; nothing new on the device).  Both tables must have been made with flat=True; ValueError otherwise.  Entries at
+        or past either table's count (room to spare behind cap_records or cap_hits) are left out on the device, from the need
+        words, with no host read; what a table that overflowed (status 6) lacks is lacking here too."""
+        if not (self.flat and hits.flat):
+            raise ValueError("RecordTable.containing needs both tables made with flat=True")
+        torch = self.index.codec.torch
+        if self.offsets.numel() == 0 or hits.offsets.numel() == 0:
+            return torch.empty(0, dtype=torch.int64, device=self.offsets.device)
+        live = lambda t, need: torch.arange(t.numel(), device=t.device) < need[0]
+        rec_live = live(self.offsets, self.need)
+        starts = torch.where(rec_live, self.offsets, torch.full_like(self.offsets, (1 << 63) - 1))        # (sorted still)
+        # the last record that starts at or before the hit is the only one that can hold it (starts are strictly increasing)
+        r = torch.searchsorted(starts, hits.offsets, right=True) - 1
+        ok = (r >= 0) & live(hits.offsets, hits.need)
+        r = r.clamp(min=0)
+        ok &= rec_live[r] & (hits.offsets + hits.needle_len <= self.offsets[r] + self.lengths[r])
+        return torch.unique(r[ok])
+
 
 RECORDS_KEEP_DELIM, RECORDS_FLAT = 1, 2          # TSQA_RECORDS_KEEP_DELIM, TSQA_RECORDS_FLAT
+FIND_FLAT, FIND_MAX_NEEDLE = 2, 16               # TSQA_FIND_FLAT, TSQA_FIND_MAX_NEEDLE
+
+
+def plan_find(data, item_at, needle, item_status=None, flat: bool = False, cap_hits=None):
+    """tsqa_plan_find (host only): the rule of RangeIndex.find applied to decoded bytes on the host.  data, item_at, item_status: as
+    in plan_records.  cap_hits None: counts first, then fills tables of that many entries.  -> (items, offsets: the hits below
+    cap_hits; item_first_hit, n_items + 1; the count).  Raises TsqError(3) when the arguments are refused."""
+    import numpy as np
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    at = np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in item_at], dtype=np.uint64))
+    n_items = len(at) - 1
+    if n_items >= 1 and int(at[-1]) > buf.size:
+        raise TsqError(3, "tsqa_plan_find: the items end past the data")
+    st = None if item_status is None else np.ascontiguousarray(np.array([int(x) for x in item_status], dtype=np.int32))
+    if st is not None and len(st) != n_items:
+        raise TsqError(3, "tsqa_plan_find takes one status per item")
+    needle = bytes(needle)
+    nd = np.frombuffer(needle + b"\0", dtype=np.uint8)       # (never empty: the length says how much of it counts)
+    first, need = np.zeros(max(n_items, 0) + 1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    ptr = lambda t: None if t is None else t.ctypes.data
+
+    def call(cap, items, offsets):
+        rc = lib().tsqa_plan_find(buf.ctypes.data if buf.size else None, at.ctypes.data, ptr(st), max(n_items, 0), nd.ctypes.data, len(needle),
+                                  FIND_FLAT if flat else 0, cap, ptr(items), ptr(offsets), first.ctypes.data, need.ctypes.data)
+        if rc:
+            raise TsqError(rc, "tsqa_plan_find refused the arguments")
+    if cap_hits is None:
+        call(0, None, None)
+        cap_hits = int(need[0])
+    cap = int(cap_hits)
+    items, offsets = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64)
+    call(cap, items, offsets)
+    k = min(cap, int(need[0]))
+    return items[:k], offsets[:k], first, int(need[0])
 
 
 def plan_records(data, item_at, item_status=None, delim: int = 10, keep_delim: bool = False, flat: bool = False, cap_records=None):
@@ -1429,6 +1544,13 @@ class DeviceCodec:
         self.L.tsqa_profile_read_records(self.h, C.byref(mm), C.byref(mn), C.byref(tm), C.byref(tn))
         return mm.value, mn.value, tm.value, tn.value
 
+    def profile_read_find(self):
+        """-> (find_ms_sum, launches, table_ms_sum, calls): the find decode of find_async (the decoder that compares with the
+        needle) and its seam and table launches since the last read."""
+        fm, fn, tm, tn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_find(self.h, C.byref(fm), C.byref(fn), C.byref(tm), C.byref(tn))
+        return fm.value, fn.value, tm.value, tn.value
+
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
         best, med = C.c_double(0), C.c_double(0)
@@ -1955,6 +2077,21 @@ class DeviceCodec:
         rc = self.L.tsqa_records_async(self.h, index.h, int(delim), int(flags), int(cap_records), ptr(d_rec_items), ptr(d_rec_offsets),
                                        ptr(d_rec_lengths), d_item_first_record.data_ptr(), d_need.data_ptr(),
                                        (self._status if d_status is None else d_status).data_ptr(), self._stream())
+        if rc:
+            raise self._err(rc)
+
+    def find_async(self, index, needle, flags: int, cap_hits: int, d_hit_items, d_hit_offsets, d_item_first_hit, d_need, d_status=None) -> None:
+        """tsqa_find_async on the current stream, nothing waited for: where `needle` (bytes, 1 .. FIND_MAX_NEEDLE of them) occurs in
+        the data behind `index` (flags: FIND_FLAT).  The hits numbered below cap_hits go to d_hit_items (int32, may be None) and
+        d_hit_offsets (int64, each hit's first byte; None with cap_hits 0: the call only measures); d_item_first_hit (int64,
+        items + 1) and d_need (int64, 1: the count of all hits) are always complete.  The status -- 0, 6 more hits than cap_hits, 4
+        a refused sized index, 5 a malformed stream -- lands in d_status (int32, 1) or, when None, in status().  The needle is read
+        during the call."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        needle = bytes(needle)
+        rc = self.L.tsqa_find_async(self.h, index.h, needle, len(needle), int(flags), int(cap_hits), ptr(d_hit_items), ptr(d_hit_offsets),
+                                    d_item_first_hit.data_ptr(), d_need.data_ptr(),
+                                    (self._status if d_status is None else d_status).data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
 

@@ -597,4 +597,88 @@ __device__ __forceinline__ void flush_mark(const uint8_t* lds, uint32_t* map32, 
     }
 }
 
+// ---------------- P7 of a find (dec_find_kernel): flush_mark with a needle of m bytes, 1 <= m <= 16, in place of one byte.  The
+// needle travels in two 64-bit words (byte k of the needle is byte k of lo, k < 8, of hi behind that).  The map's layout, the
+// ring's skew and the walk by aligned 16-byte cells are flush_mark's; bit G stands for a hit that ENDS at position G of the
+// concatenation.  A hit that ends in a cell starts in it or in the cell in front, so a lane reads that one too (with the ring's
+// wrap): the bytes in front of the image are earlier images of the same block, which the ring keeps (64 KiB of history, and
+// write_ring of the next chunk comes behind this flush).  Ends at block positions p < m - 1 would start in front of the block:
+// they are left to the seam launch (tsq_find.cuh), which has the neighbouring blocks' edges.
+// The comparison: the equality mask of the needle's LAST byte over the cell is the filter -- in text most cells end here --, and
+// only a cell that passes it takes the other bytes' masks over the 32-byte window, each shifted to the hit's end and ANDed, until
+// nothing is left.
+// Edge bytes: edges[32 blk + j], j < 15, is byte j of the block, and edges[32 blk + 16 + j] is byte size - 15 + j (the last 15
+// bytes, right-aligned; positions in front of the block are not written).  Each flush writes those that lie in its image.
+// No barrier inside.
+struct FindNeedle { uint64_t lo, hi; uint32_t m; };
+
+__device__ __forceinline__ uint32_t find_needle_byte(const FindNeedle& nd, uint32_t k)
+{
+    return (uint32_t)((k < 8u ? nd.lo >> (8u * k) : nd.hi >> (8u * (k - 8u))) & 0xFFull);
+}
+
+// bit j: byte j of the cell equals the byte that `splat` repeats (flush_mark's zero-byte test)
+__device__ __forceinline__ uint32_t find_cell_mask(const uint4& x, uint32_t splat)
+{
+    const uint32_t v[4] = {x.x ^ splat, x.y ^ splat, x.z ^ splat, x.w ^ splat};
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        const uint32_t z = ~(((v[i] & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v[i] | 0x7F7F7F7Fu);
+        m |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4u * i);
+    }
+    return m;
+}
+
+template <class L>
+__device__ __forceinline__ void flush_find(const uint8_t* lds, uint32_t* map32, uint64_t map_words, uint64_t base, uint32_t blk, const Image& im,
+                                           const FindNeedle& nd, uint32_t size, uint8_t* edges, uint32_t first_tid, uint32_t n_threads)
+{
+    using C = SymCfg;
+    const uint32_t tid = threadIdx.x;
+    const uint8_t* const ring = lds + L::ring;
+    if (im.len == 0 || tid < first_tid) return;
+    const uint32_t t = tid - first_tid;
+    if (t < 31u && t != 15u) {                               // the block's edges: lanes 0..14 its head, 16..30 its tail
+        const uint32_t j = t & 15u;
+        uint32_t p = 0xFFFFFFFFu;
+        if (t < 15u) { if (j < size) p = j; }
+        else if (size + j >= 15u) p = size + j - 15u;
+        if (p != 0xFFFFFFFFu && p >= im.op && p - im.op < im.len) {
+            uint32_t a = im.at + (p - im.op); a -= a >= C::R ? C::R : 0u;
+            edges[((size_t)blk << 5) + t] = ring[a];
+        }
+    }
+    const uint32_t skew = im.at & 15u, cells = (skew + im.len + 15u) >> 4;
+    const uint32_t c0 = im.at & ~15u;
+    const uint64_t g0 = (base + im.op) & ~15ull;
+    const uint32_t m = nd.m;
+    const uint32_t last = find_needle_byte(nd, m - 1u) * 0x01010101u;
+    for (uint32_t w = t; w < cells; w += n_threads) {
+        uint32_t a = c0 + (w << 4); a -= a >= C::R ? C::R : 0u;
+        const uint4 x = *reinterpret_cast<const uint4*>(ring + a);
+        uint32_t ends = find_cell_mask(x, last);
+        // the image's bytes [lo, hi) of the cell, less the ends in front of block position m - 1: byte j of the cell is block
+        // position op + 16 w + j - skew
+        uint32_t lo = w == 0u ? skew : 0u;
+        const uint32_t left = skew + im.len - (w << 4), hi = left < 16u ? left : 16u;
+        const int32_t from = (int32_t)(m - 1u + skew) - (int32_t)(im.op + (w << 4));
+        if (from > (int32_t)lo) lo = from < 16 ? (uint32_t)from : 16u;
+        ends &= ((0xFFFFu << lo) & 0xFFFFu) & (0xFFFFu >> (16u - hi));
+        if (ends != 0u && m > 1u) {
+            const uint32_t b = a == 0u ? C::R - 16u : a - 16u;                // the cell in front (the ring's size is a multiple of 16)
+            const uint4 y = *reinterpret_cast<const uint4*>(ring + b);
+            uint32_t acc = ends << 16;                                        // bits 16..31: this cell, 0..15: the one in front
+            for (uint32_t k = m - 1u; k-- > 0u && acc != 0u; ) {
+                const uint32_t splat = find_needle_byte(nd, k) * 0x01010101u;
+                const uint32_t eq = find_cell_mask(y, splat) | (find_cell_mask(x, splat) << 16);
+                acc &= eq << (m - 1u - k);                                    // needle byte k lies m - 1 - k in front of the end
+            }
+            ends = acc >> 16;
+        }
+        const uint64_t g = g0 + ((uint64_t)w << 4), word = (g >> 6) + blk;
+        if (ends != 0u && word < map_words) atomicOr(map32 + 2u * word + ((uint32_t)(g >> 5) & 1u), ends << ((uint32_t)g & 16u));
+    }
+}
+
 }  // namespace tsq

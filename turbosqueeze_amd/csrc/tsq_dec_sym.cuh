@@ -46,7 +46,7 @@ struct BlockGroup {
     uint32_t block, first, count, hi;
 };
 
-enum DecMode : int { kDecWhole, kDecWindow, kDecGroup, kDecMark };
+enum DecMode : int { kDecWhole, kDecWindow, kDecGroup, kDecMark, kDecFind };
 
 // ---------------- P7 of a record read: the image's bytes go to every item of the group that they meet (byte p of the block to
 // out[it.out_at + p - it.lo]).  The items are sorted by lo, so those that meet the image are a run of the list that only moves
@@ -176,14 +176,17 @@ __device__ __forceinline__ void flush_group(const uint8_t* lds, uint8_t* out, co
 // bytes go to each of the group's items that they meet (flush_group).  Every chunk that is decoded is validated as in the
 // whole-block decode.  kDecMark (dec_mark_kernel): block blockIdx.x, whole, and nothing of it is written: `outbuf` is the bit map of
 // flush_mark, map_words long, and every chunk's image is compared with `delim` there.  Every use of that mode sits behind
-// `if constexpr`, so the other three are compiled as they were.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
+// `if constexpr`, so the other three are compiled as they were.  kDecFind (dec_find_kernel): kDecMark with a needle of up to 16
+// bytes in place of the delimiter (flush_find), and the block's first and last 15 bytes left in `edges`; it sits behind
+// `if constexpr` in the same places.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
 // inlined function would give dec_sym_kernel other code than before.)
 template <DecMode kMode>
 __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
                                                  uint8_t* outbuf, int32_t* status, const BlockGroup* groups = nullptr, uint32_t n_items = 0u,
-                                                 [[maybe_unused]] uint32_t delim = 0u, [[maybe_unused]] uint64_t map_words = 0ull)
+                                                 [[maybe_unused]] uint32_t delim = 0u, [[maybe_unused]] uint64_t map_words = 0ull,
+                                                 [[maybe_unused]] FindNeedle needle = {0ull, 0ull, 0u}, [[maybe_unused]] uint8_t* edges = nullptr)
 {
-    constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup, kMark = kMode == kDecMark;
+    constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup, kMark = kMode == kDecMark, kFind = kMode == kDecFind;
     using C = SymCfg;
     using L = SymLds;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -232,12 +235,12 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     // window: `out` is where byte lo goes; byte p of the block goes to out + (p - lo)
     // (group: every item has a destination of its own in outbuf; no skew of the ring can serve them all)
     // (mark: outbuf is the bit map, and no byte of the block has a destination)
-    uint8_t* const out = kGroup || kMark ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
+    uint8_t* const out = kGroup || kMark || kFind ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
     const uint32_t in_len = f.stream_len, size = f.out_len, ext = f.ext;
     // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM (window: of
     // the block's virtual base out - lo)
     // (mark: the 64-position grid of the concatenation falls on the ring's 64-byte grid, flush_mark)
-    const uint32_t oskew = kMark ? (uint32_t)(f.out_at & 63u) : kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
+    const uint32_t oskew = kMark || kFind ? (uint32_t)(f.out_at & 63u) : kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
 
 #ifdef TSQ_STATS
     const uint32_t lane = tid & 63u, wid = tid >> 6;
@@ -276,7 +279,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         // HBM meanwhile (P7).  (measured in round 5: a build without this flush runs 4.558 against 4.553 ms, the flush beside P3's
         // chain instead 4.572 -- it hides completely)
         if (tid >= C::T / 2) {
-            if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, C::T / 2, C::T / 2);
+            if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, C::T / 2, C::T / 2);
+            else if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, C::T / 2, C::T / 2);
             else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, C::T / 2, C::T / 2);
             else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
             else flush_image<L>(lds, out, prev, C::T / 2, C::T / 2);
@@ -341,7 +345,8 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     if constexpr (kGroup) { if (tid == C::T / 2) misc[12] = gcur.cur; }
     __syncthreads();
     if constexpr (kGroup) { if (tid < C::T / 2) gcur.cur = misc[12]; }
-    if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, 0, C::T);
+    if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, 0, C::T);
+    else if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, 0, C::T);
     else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, 0, C::T);
     else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
     else flush_image<L>(lds, out, prev, 0, C::T);
@@ -396,6 +401,19 @@ __global__ __launch_bounds__(1024) void dec_mark_kernel(const uint8_t* __restric
 {
     if (verdict && *verdict != 0) return;
     sym_decode_block<kDecMark>(container, frames, 0u, nullptr, reinterpret_cast<uint8_t*>(map), status, nullptr, 0u, delim, map_words);
+}
+
+// The find (tsqa_find_async): dec_mark_kernel with a needle of m bytes (n0..n3: its bytes, little-endian, zeros behind m) in place
+// of the delimiter.  Bit G of `map` is set where a hit ENDS at byte G of the index's data and starts inside the same block; the
+// block's first and last 15 bytes go to edges + 32 * block for the seam launch (tsq_find.cuh).
+__global__ __launch_bounds__(1024) void dec_find_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                        const int32_t* __restrict__ verdict, uint32_t n0, uint32_t n1, uint32_t n2, uint32_t n3,
+                                                        uint32_t m, uint64_t* __restrict__ map, uint64_t map_words, uint8_t* __restrict__ edges,
+                                                        int32_t* __restrict__ status)
+{
+    if (verdict && *verdict != 0) return;
+    const FindNeedle needle = {((uint64_t)n1 << 32) | n0, ((uint64_t)n3 << 32) | n2, m};
+    sym_decode_block<kDecFind>(container, frames, 0u, nullptr, reinterpret_cast<uint8_t*>(map), status, nullptr, 0u, 0u, map_words, needle, edges);
 }
 
 }  // namespace tsq

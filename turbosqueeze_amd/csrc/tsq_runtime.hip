@@ -22,6 +22,7 @@
 #include "tsq_gather_sort.h"
 #include "tsq_rows.cuh"
 #include "tsq_records.cuh"
+#include "tsq_find.cuh"
 
 #include <algorithm>
 #include <cstdarg>
@@ -312,6 +313,16 @@ int tsqa_ctx::reserve_records(size_t map_words, size_t n_blocks)
            records_words.grow(this, 1) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the find: the records' (the map is shared; every call clears it), 32 edge bytes per block and the scan's two words.
+int tsqa_ctx::reserve_find(size_t map_words, size_t n_blocks)
+{
+    if (int rc = reserve_records(map_words, n_blocks)) return rc;
+    const size_t edges = 32 * doubled(256, n_blocks);
+    if (!find_edges.needs(edges) && !find_need.needs(2)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return find_edges.grow(this, edges) && find_need.grow(this, 2) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -429,6 +440,16 @@ extern "C" int tsqa_profile_read_records(tsqa_ctx* c, double* mark_ms, uint32_t*
     if (c->prof_pool.empty()) { if (mark_ms) *mark_ms = 0; if (mark_n) *mark_n = 0; if (table_ms) *table_ms = 0; if (table_n) *table_n = 0; return TSQA_OK; }
     drain_events(c, 9, mark_ms, mark_n);
     drain_events(c, 10, table_ms, table_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_find(tsqa_ctx* c, double* find_ms, uint32_t* find_n, double* table_ms, uint32_t* table_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (find_ms) *find_ms = 0; if (find_n) *find_n = 0; if (table_ms) *table_ms = 0; if (table_n) *table_n = 0; return TSQA_OK; }
+    drain_events(c, 11, find_ms, find_n);
+    drain_events(c, 12, table_ms, table_n);
     return TSQA_OK;
 }
 
@@ -2398,6 +2419,124 @@ extern "C" int tsqa_records(tsqa_ctx* c, const tsqa_index* idx, uint32_t delim, 
     TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "records");
+}
+
+// ---- where a byte string occurs: a decode that compares with the needle and writes one bit per hit's end, the seams between the
+// blocks from their edge bytes, then the records' count, scan and placement over the map (tsq_find.cuh) ----
+
+extern "C" int tsqa_plan_find(const void* data, const uint64_t* item_at, const int32_t* item_status, uint32_t n_items, const void* needle,
+                              uint32_t needle_len, uint32_t flags, uint64_t cap_hits, uint32_t* hit_items, uint64_t* hit_offsets,
+                              uint64_t* item_first_hit, uint64_t* need)
+{
+    if (!item_at || !item_first_hit || !need || !needle || n_items == 0 || needle_len == 0 || needle_len > TSQA_FIND_MAX_NEEDLE ||
+        (flags & ~TSQA_FIND_FLAT) != 0u)
+        return TSQA_ERR_ARG;
+    if (cap_hits > 0 && !hit_offsets) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_at[i + 1] < item_at[i]) return TSQA_ERR_ARG;
+    if (!data && item_at[n_items] != item_at[0]) return TSQA_ERR_ARG;
+    const uint8_t* const bytes = static_cast<const uint8_t*>(data);
+    const uint8_t* const nd = static_cast<const uint8_t*>(needle);
+    const uint64_t m = needle_len;
+    uint64_t no = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        item_first_hit[i] = no;
+        const uint64_t a = item_at[i], e = item_at[i + 1], origin = flags & TSQA_FIND_FLAT ? 0ull : a;
+        if (e - a < m || (item_status && item_status[i] != 0)) continue;
+        for (uint64_t p = a; p + m <= e; ++p) {
+            // (the first byte is the filter; overlapping hits all count, so the walk advances by one)
+            const uint8_t* const hit = static_cast<const uint8_t*>(memchr(bytes + p, nd[0], (size_t)(e - m + 1 - p)));
+            if (!hit) break;
+            p = (uint64_t)(hit - bytes);
+            if (memcmp(bytes + p, nd, (size_t)m) != 0) continue;
+            if (no < cap_hits) { if (hit_items) hit_items[no] = i; hit_offsets[no] = p - origin; }
+            ++no;
+        }
+    }
+    item_first_hit[n_items] = no;
+    need[0] = no;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_find_async(tsqa_ctx* c, const tsqa_index* idx, const void* needle, uint32_t needle_len, uint32_t flags, uint64_t cap_hits,
+                               uint32_t* d_hit_items, uint64_t* d_hit_offsets, uint64_t* d_item_first_hit, uint64_t* d_need, int32_t* d_status,
+                               void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !needle || !d_item_first_hit || !d_need || !d_status) { c->set_error("find: null pointer"); return TSQA_ERR_ARG; }
+    if (needle_len == 0u || needle_len > TSQA_FIND_MAX_NEEDLE) { c->set_error("find: a needle of %u bytes (1 .. %u)", needle_len, TSQA_FIND_MAX_NEEDLE); return TSQA_ERR_ARG; }
+    if ((flags & ~TSQA_FIND_FLAT) != 0u) { c->set_error("find: unknown flags 0x%x", flags); return TSQA_ERR_ARG; }
+    if (cap_hits > 0 && !d_hit_offsets) { c->set_error("find: cap_hits of %llu with a NULL offsets table", (unsigned long long)cap_hits); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("find: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    // (the host sizes the bit map from the total and the block count, which it does not have before the fetch)
+    if (idx->pending_items != 0u) { c->set_error("find: %s", kNeedsFetch); return TSQA_ERR_ARG; }
+    // the needle is read here and travels as kernel arguments: the caller's buffer is free when the call returns
+    uint32_t nw[4] = {0u, 0u, 0u, 0u};
+    memcpy(nw, needle, needle_len);
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    const uint32_t n_blocks = idx->n_blocks, n_items = tsqa_index_items(idx);
+    const uint32_t item_groups = (uint32_t)(((uint64_t)n_items + 1u + 255u) / 256u);
+    if (n_blocks == 0) {
+        TSQ_HIP(c, hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
+        TSQ_HIP(c, hipMemsetAsync(d_need, 0, sizeof(uint64_t), s));
+        hipLaunchKernelGGL(records_clear_kernel, dim3(item_groups), dim3(256), 0, s, d_item_first_hit, n_items);
+        TSQ_HIP(c, hipGetLastError());
+        return TSQA_OK;
+    }
+    const uint64_t map_words = (idx->total >> 6) + n_blocks + 1u;
+    if (int rc = c->reserve_find((size_t)map_words, n_blocks)) return rc;
+    uint64_t* const map = c->records_map;
+    RecordBlock* const blocks = c->records_blocks;
+    const uint32_t n_groups = (n_blocks + kRecordsGroup - 1u) / kRecordsGroup;
+    uint64_t* const group_sum = c->records_groups;
+    uint64_t* const group_edge = group_sum + c->records_groups.cap / 2;
+    RecordWords* const words = c->records_words;
+    uint8_t* const edges = c->find_edges;
+    uint64_t* const count = c->find_need;
+    const FrameInfo* const frames = idx->frames;
+    const int32_t* const verdict = idx->verdict;
+    const uint64_t* const item_first = idx->d_item_first;
+    TSQ_HIP(c, hipMemsetAsync(words, 0, sizeof(RecordWords), s));
+    TSQ_HIP(c, hipMemsetAsync(map, 0, (size_t)map_words * sizeof(uint64_t), s));
+    ProfSpan find(c, 11, s);
+    const int rc = launch_read_kernel<dec_find_kernel>(c, n_blocks, s, idx->container, frames, verdict, nw[0], nw[1], nw[2], nw[3], needle_len, map,
+                                                       map_words, edges, &words->stream);
+    if (rc) { find.cancel(); return rc; }
+    find.end();
+    ProfSpan table(c, 12, s);
+    if (needle_len > 1u)
+        hipLaunchKernelGGL(find_seam_kernel, dim3(n_groups), dim3(256), 0, s, frames, n_blocks, idx->total, idx->block_shift, verdict, item_first, n_items,
+                           nw[0], nw[1], nw[2], nw[3], needle_len, static_cast<const uint8_t*>(edges), map, map_words);
+    hipLaunchKernelGGL(find_count_kernel, dim3(n_blocks), dim3(256), 0, s, frames, n_blocks, idx->total, verdict, item_first, n_items,
+                       static_cast<const uint64_t*>(map), map_words, blocks);
+    hipLaunchKernelGGL(records_sum_kernel, dim3(n_groups), dim3(256), 0, s, blocks, n_blocks, group_sum, group_edge);
+    hipLaunchKernelGGL(records_scan_kernel, dim3(1), dim3(256), 0, s, group_sum, group_edge, n_groups, verdict, cap_hits, count, words);
+    hipLaunchKernelGGL(records_place_kernel, dim3(n_groups), dim3(256), 0, s, blocks, n_blocks, static_cast<const uint64_t*>(group_sum),
+                       static_cast<const uint64_t*>(group_edge));
+    hipLaunchKernelGGL(records_items_kernel, dim3(item_groups), dim3(256), 0, s, static_cast<const RecordBlock*>(blocks), n_blocks, item_first, n_items,
+                       static_cast<const uint64_t*>(count), d_item_first_hit);
+    hipLaunchKernelGGL(find_emit_kernel, dim3(n_blocks), dim3(256), 0, s, frames, verdict, static_cast<const uint64_t*>(map), map_words,
+                       static_cast<const RecordBlock*>(blocks), needle_len, flags, cap_hits, d_hit_items, d_hit_offsets);
+    hipLaunchKernelGGL(find_close_kernel, dim3(1), dim3(1), 0, s, static_cast<const RecordWords*>(words), static_cast<const uint64_t*>(count), d_need,
+                       d_status);
+    table.end();
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_find(tsqa_ctx* c, const tsqa_index* idx, const void* needle, uint32_t needle_len, uint32_t flags, uint64_t cap_hits,
+                         uint32_t* d_hit_items, uint64_t* d_hit_offsets, uint64_t* d_item_first_hit, uint64_t* d_need, int32_t* d_status,
+                         void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_find_async(c, idx, needle, needle_len, flags, cap_hits, d_hit_items, d_hit_offsets, d_item_first_hit, d_need, d_status, s))
+        return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "find");
 }
 
 // ---- gather into fixed-stride padded rows: the same ranges, row k at k * row_stride, the tails filled (tsq_rows.cuh) ----
