@@ -195,6 +195,8 @@ int tsqa_profile_read_rows(tsqa_ctx *ctx, double *pad_ms, uint32_t *pad_launches
 int tsqa_profile_read_records(tsqa_ctx *ctx, double *mark_ms, uint32_t *mark_launches, double *table_ms, uint32_t *table_calls);
 /* tsqa_find_async: its find decode (the decoder that compares with the needle) and, per call, its seam and table launches together. */
 int tsqa_profile_read_find(tsqa_ctx *ctx, double *find_ms, uint32_t *find_launches, double *table_ms, uint32_t *table_calls);
+/* tsqa_crc32_async: its CRC decode (the decoder that checksums) and, per call, its fold and close launches together. */
+int tsqa_profile_read_crc(tsqa_ctx *ctx, double *decode_ms, uint32_t *decode_launches, double *fold_ms, uint32_t *fold_calls);
 
 /* One step of a block-sharded job on one rank (block b of the job belongs to rank b % world; what bench.py --gpus N and
  * turbosqueeze_amd/sharding.py run).  The only exchange between ranks is the all-gather of the u32 stream sizes, made by the
@@ -1070,6 +1072,55 @@ int tsqa_find_async(tsqa_ctx *ctx, const tsqa_index *idx, const void *needle, ui
 int tsqa_find(tsqa_ctx *ctx, const tsqa_index *idx, const void *needle, uint32_t needle_len, uint32_t flags,
               uint64_t cap_hits, uint32_t *d_hit_items, uint64_t *d_hit_offsets,
               uint64_t *d_item_first_hit, uint64_t *d_need, int32_t *d_status, void *hip_stream);
+
+/*
+ * CRC-32 of every item: zlib's crc32 (polynomial 0xEDB88320, init and final xor 0xFFFFFFFF -- the value zlib, gzip, zip and png give)
+ * of the data behind an index, made on the device with NO decoded copy.  Every block is decoded and validated as in the whole-block
+ * decode, and its bytes are checksummed instead of being stored: the one thing written per block is a word of scratch (4 bytes
+ * per block, cleared by every call).  The CRC is linear, so the blocks' words combine into the items' whatever block_len, ext or
+ * route (join, cut, take, a transcode) made the container: equal data gives equal CRCs.  Any index but a batch index made on the
+ * device and not yet fetched.
+ *
+ * The rule.  The index has n_items items.  A container index has one item.  Item i has data D_i of T_i bytes.
+ *   - d_item_crc[i] is crc32(D_i).  It is 0 for an item of 0 bytes.
+ *   - d_item_status[i] is 0 for a healthy item; the index's own item status for an item the index refused, whose CRC is 0; and
+ *     TSQA_ERR_STREAM for an item one of whose blocks holds a malformed stream, whose CRC is 0.
+ *   - A malformed stream costs that item alone: every other item is delivered exactly (the decoders of an item's blocks share the
+ *     item's status word, as in tsqa_decompress_batch_items_async, and leave early on it).
+ *   - d_block_crc[b] (may be NULL) is crc32 of block b's own data: tsqa_crc32_combine folds an item's blocks into the item's CRC on
+ *     the host.  It is undefined for the blocks of an item whose status is nonzero.
+ *   - d_all_crc (may be NULL) is the CRC-32 of the index's whole data, the concatenation that tsqa_decompress_ranges* reads.  Refused
+ *     items contribute no bytes to it, as they contribute none to tsqa_index_total.  It is 0 when any item got TSQA_ERR_STREAM in
+ *     this call.
+ * Status: *d_status is TSQA_OK; TSQA_ERR_FORMAT for a sized index whose verdict is nonzero -- then no descriptor is read, every CRC
+ * is 0 and every item status is TSQA_ERR_FORMAT --; TSQA_ERR_STREAM when any item was raised to it.  An index of 0 blocks leaves
+ * every CRC 0 and the items' statuses the index's own.
+ * flags must be 0.
+ * Trust and alignment: as tsqa_records_async -- nothing in the container is trusted, nothing is written outside the stated
+ * extents (n_items entries of d_item_crc and d_item_status, n_blocks of d_block_crc, one of d_all_crc and d_status), the tables
+ * are aligned as their elements (4 bytes) and nothing wider than an element is stored.
+ * TSQA_ERR_ARG before anything is enqueued for: a NULL among idx, d_item_crc, d_item_status and d_status; nonzero flags; an index of
+ * another device; an index made on the device and not yet fetched.  Calls that share a context share its scratch: order them on
+ * one stream.
+ *
+ * tsqa_crc32: the same, then waits for hip_stream and returns *d_status.
+ *
+ * tsqa_plan_crc32: host only, the same rule on decoded bytes on the host, with tsqa_plan_records' shape: data is the concatenation,
+ *   item_at[n_items + 1] holds the items' starts in it, item_status may be NULL.  Fills item_crc[n_items] (0 for an empty or a
+ *   refused item) and *all_crc (may be NULL; the bytes of refused items are left out).  TSQA_ERR_ARG for NULL or unordered tables or
+ *   n_items == 0.
+ * tsqa_crc32_host: zlib's crc32(crc, buf, n) on the host (crc 0 starts a new checksum).
+ * tsqa_crc32_combine: zlib's crc32_combine -- crc32(A | B) from crc32(A), crc32(B) and B's length in bytes; the length is 64-bit
+ *   (8 * len_b passes 2^32 at 512 MiB).  Both are written here: libz is neither linked nor copied.
+ */
+int tsqa_plan_crc32(const void *data, const uint64_t *item_at, const int32_t *item_status, uint32_t n_items, uint32_t *item_crc,
+                    uint32_t *all_crc);
+uint32_t tsqa_crc32_host(uint32_t crc, const void *buf, size_t n);
+uint32_t tsqa_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int tsqa_crc32_async(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t flags, uint32_t *d_item_crc, int32_t *d_item_status,
+                     uint32_t *d_block_crc, uint32_t *d_all_crc, int32_t *d_status, void *hip_stream);
+int tsqa_crc32(tsqa_ctx *ctx, const tsqa_index *idx, uint32_t flags, uint32_t *d_item_crc, int32_t *d_item_status,
+               uint32_t *d_block_crc, uint32_t *d_all_crc, int32_t *d_status, void *hip_stream);
 
 /*
  * The index of a packed batch from its tables in DEVICE memory, with no host wait: the last step of packed compress -> index ->

@@ -16,6 +16,9 @@
 //   tsq_cli f <in.tsq> <needle>             find: the container goes to the device and the number of places at which the bytes
 //                                           of <needle> (1 .. 16) occur, and the first place's offset, are printed (tsqa_find
 //                                           with a table of one entry: nothing is decoded into memory).
+//   tsq_cli k <in.tsq>                      checksum: the container goes to the device and the data's size and its CRC-32 are printed,
+//                                           the value zlib.crc32 gives for the original file (tsqa_crc32: nothing is decoded
+//                                           into memory).
 // Unlike the reference's benchmark (clock() summed over threads, divided by 1e5) this reports
 // wall-clock MB/s.
 #include <chrono>
@@ -43,7 +46,8 @@ static int usage()
                     "       tsq_cli bf <in> <workdir> [--no-ext] [--reps N]   (file -> file -> file with warm contexts)\n"
                     "       tsq_cli x <in.tsq> <offset> <length> <out>       (uncompressed bytes [offset, offset + length))\n"
                     "       tsq_cli r <in.tsq> [delim]                       (record count and longest record for a delimiter byte, default 10)\n"
-                    "       tsq_cli f <in.tsq> <needle>                      (how often the needle's bytes, 1 .. 16, occur, and where first)\n");
+                    "       tsq_cli f <in.tsq> <needle>                      (how often the needle's bytes, 1 .. 16, occur, and where first)\n"
+                    "       tsq_cli k <in.tsq>                               (the data's size and its CRC-32, zlib's, in hex)\n");
     return 2;
 }
 
@@ -162,6 +166,42 @@ static int find_needle(const std::string& in, const std::string& needle)
     return 0;
 }
 
+// k: zlib's CRC-32 of a container's data, made on the device
+static int checksum(const std::string& in)
+{
+    FILE* f = fopen(in.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", in.c_str()); return 1; }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    std::vector<uint8_t> blob(sz > 0 ? (size_t)sz : 0);
+    const bool read_ok = fread(blob.data(), 1, blob.size(), f) == blob.size();
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "short read\n"); return 1; }
+    tsqa_ctx* ctx = nullptr;
+    if (tsqa_create(-1, &ctx) != TSQA_OK) { fprintf(stderr, "no usable MI355X (gfx950) device\n"); return 1; }
+    void *d_in = nullptr, *d_words = nullptr;                  // d_words: the item's CRC, its status, the whole data's CRC, the call's status
+    tsqa_index* idx = nullptr;
+    uint32_t words[4] = {0, 0, 0, 0};
+    int rc = TSQA_OK;
+    if (hipMalloc(&d_in, blob.size() ? blob.size() : 1) != hipSuccess || hipMalloc(&d_words, sizeof(words)) != hipSuccess ||
+        hipMemset(d_words, 0, sizeof(words)) != hipSuccess || hipMemcpy(d_in, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "device memory: %s\n", hipGetErrorString(hipGetLastError()));
+        rc = TSQA_ERR_HIP;
+    }
+    if (rc == TSQA_OK && (rc = tsqa_index_create(ctx, d_in, blob.size(), &idx)) == TSQA_OK) {
+        uint32_t* const w = static_cast<uint32_t*>(d_words);
+        rc = tsqa_crc32(ctx, idx, 0, w, reinterpret_cast<int32_t*>(w + 1), nullptr, w + 2, reinterpret_cast<int32_t*>(w + 3), nullptr);
+    }
+    if (rc != TSQA_OK && rc != TSQA_ERR_HIP) fprintf(stderr, "checksum failed (%d): %s\n", rc, tsqa_last_error(ctx));
+    if (rc == TSQA_OK && hipMemcpy(words, d_words, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess) rc = TSQA_ERR_HIP;
+    const uint64_t total = idx ? tsqa_index_total(idx) : 0;
+    tsqa_index_destroy(idx);
+    (void)hipFree(d_in); (void)hipFree(d_words);
+    tsqa_destroy(ctx);
+    if (rc != TSQA_OK) return 1;
+    printf("{\"bytes\": %llu, \"crc32\": \"0x%x\"}\n", (unsigned long long)total, words[2]);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return usage();
@@ -210,6 +250,10 @@ int main(int argc, char** argv)
         if (pos.size() != 2) return usage();
         if (pos[1].empty() || pos[1].size() > TSQA_FIND_MAX_NEEDLE) { fprintf(stderr, "the needle is 1 .. %u bytes\n", TSQA_FIND_MAX_NEEDLE); return 2; }
         return find_needle(pos[0], pos[1]);
+    }
+    if (mode == "k") {
+        if (pos.size() != 1) return usage();
+        return checksum(pos[0]);
     }
     if (mode == "bf") {
         // file -> .tsq file -> file through the _MT API's file modes with the contexts allocated once (as sample/main.cpp:71-95 keeps

@@ -254,6 +254,17 @@ def lib(ab=False) -> C.CDLL:
         f.argtypes = [vp, vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp]
     L.tsqa_profile_read_find.restype = C.c_int
     L.tsqa_profile_read_find.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.tsqa_plan_crc32.restype = C.c_int
+    L.tsqa_plan_crc32.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
+    for f in (L.tsqa_crc32_async, L.tsqa_crc32):
+        f.restype = C.c_int
+        f.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.tsqa_crc32_host.restype = C.c_uint32
+    L.tsqa_crc32_host.argtypes = [C.c_uint32, vp, C.c_size_t]
+    L.tsqa_crc32_combine.restype = C.c_uint32
+    L.tsqa_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    L.tsqa_profile_read_crc.restype = C.c_int
+    L.tsqa_profile_read_crc.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.tsqa_plan_split.restype = C.c_int
     L.tsqa_plan_split.argtypes = [C.c_size_t, C.c_uint32, u32p, szp]
     L.tsqa_compress_device_split_async.restype = C.c_int
@@ -634,6 +645,51 @@ class RangeIndex:
                 raise TsqError(st, "find: the device reported a refused index (4) or a malformed stream (5)")
         return table
 
+    def crc32(self, blocks: bool = False, all: bool = True, sync: bool = True) -> "CrcTable":
+        """zlib's CRC-32 of every item's data (DeviceCodec.crc32_async): the value zlib.crc32 gives for the bytes a decompress would
+        write.  The data is decoded and checksummed on the device; no decoded copy is made -- the scratch is 4 bytes per block.  all:
+        the CRC of the whole data too; blocks: one CRC per block too (they fold into the items' with crc32_combine).  -> a CrcTable.
+        One enqueue on the current stream with no host read; sync=True then waits and raises TsqError for a refused index (4), and
+        for a malformed stream (5) unless it cost only some of several items -- then the table's status says which."""
+        codec = self.codec
+        codec._join()
+        table = codec.crc32_async(self, blocks=blocks, all=all)
+        codec._join()
+        if sync:
+            table.check()
+        return table
+
+
+class CrcTable:
+    """What RangeIndex.crc32 gives: items (one CRC per item), all (the whole data's CRC, one entry, or None) and blocks (one per block,
+    or None) -- the uint32 values as int64 CUDA tensors, made on demand from d_items, d_all and d_blocks, the int32 tensors the
+    device wrote --; status (int32 per item: 0, the index's own status for an item it refused, 5 for an item with a malformed
+    stream; the CRC of both is 0) and d_status (int32, 1: 0, 4 a refused sized index, 5 when any item was raised to it).  All are
+    valid behind the stream the call was enqueued on."""
+
+    def __init__(self, index, d_items, status, d_blocks, d_all, d_status):
+        self.index, self.d_items, self.status, self.d_blocks, self.d_all, self.d_status = index, d_items, status, d_blocks, d_all, d_status
+
+    @property
+    def items(self):
+        return self.d_items.long() & 0xFFFFFFFF
+
+    @property
+    def blocks(self):
+        return None if self.d_blocks is None else self.d_blocks.long() & 0xFFFFFFFF
+
+    @property
+    def all(self):
+        return None if self.d_all is None else self.d_all.long() & 0xFFFFFFFF
+
+    def check(self) -> "CrcTable":
+        """Waits for the call.  Raises TsqError when the index was refused (4), or when a malformed stream (5) left no healthy
+        item; -> the table otherwise (with status 5 on the items it cost)."""
+        st = int(self.d_status.item())
+        if st == 4 or (st != 0 and not bool((self.status == 0).any().item())):
+            raise TsqError(st, "crc32: the device reported a refused index (4) or a malformed stream (5)")
+        return self
+
 
 class HitTable:
     """What RangeIndex.find gives: offsets (int64, each hit's first byte) and items (int32) of cap_hits entries, of which the first
@@ -711,6 +767,39 @@ class RecordTable:
 
 RECORDS_KEEP_DELIM, RECORDS_FLAT = 1, 2          # TSQA_RECORDS_KEEP_DELIM, TSQA_RECORDS_FLAT
 FIND_FLAT, FIND_MAX_NEEDLE = 2, 16               # TSQA_FIND_FLAT, TSQA_FIND_MAX_NEEDLE
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """tsqa_crc32_combine (host only): zlib's crc32_combine -- the CRC-32 of A | B from crc32(A), crc32(B) and B's length in bytes."""
+    return int(lib().tsqa_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
+
+
+def crc32_host(data, crc: int = 0) -> int:
+    """tsqa_crc32_host (host only): zlib.crc32(data, crc) by the library's own tables."""
+    import numpy as np
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    return int(lib().tsqa_crc32_host(int(crc) & 0xFFFFFFFF, buf.ctypes.data if buf.size else None, buf.size))
+
+
+def plan_crc32(data, item_at, item_status=None):
+    """tsqa_plan_crc32 (host only): the rule of RangeIndex.crc32 applied to decoded bytes on the host.  data, item_at, item_status: as
+    in plan_records.  -> (item_crc: uint32 numpy, 0 for an empty or refused item; the CRC of the whole data, refused items left
+    out).  Raises TsqError(3) when the arguments are refused."""
+    import numpy as np
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    at = np.ascontiguousarray(np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in item_at], dtype=np.uint64))
+    n_items = len(at) - 1
+    if n_items >= 1 and int(at[-1]) > buf.size:
+        raise TsqError(3, "tsqa_plan_crc32: the items end past the data")
+    st = None if item_status is None else np.ascontiguousarray(np.array([int(x) for x in item_status], dtype=np.int32))
+    if st is not None and len(st) != n_items:
+        raise TsqError(3, "tsqa_plan_crc32 takes one status per item")
+    crc, whole = np.zeros(max(n_items, 1), dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+    rc = lib().tsqa_plan_crc32(buf.ctypes.data if buf.size else None, at.ctypes.data, None if st is None else st.ctypes.data, max(n_items, 0),
+                               crc.ctypes.data, whole.ctypes.data)
+    if rc:
+        raise TsqError(rc, "tsqa_plan_crc32 refused the arguments")
+    return crc[:n_items], int(whole[0])
 
 
 def plan_find(data, item_at, needle, item_status=None, flat: bool = False, cap_hits=None):
@@ -1406,6 +1495,10 @@ class PackedBatch:
         return codec.index_packed_async(self.arena, self.d_offsets, self.d_sizes, n, max(int(cap_blocks), 1), self.block_len if sized else None,
                                         self.d_first_block if sized else None, self.d_block_sizes)
 
+    def crc32(self, blocks: bool = False, all: bool = True, sync: bool = True) -> "CrcTable":
+        """zlib's CRC-32 of every item of the batch, through its index (index().crc32): nothing is decoded into memory."""
+        return self.index().crc32(blocks=blocks, all=all, sync=sync)
+
     def take(self, d_items, align: int = 16, out=None, sync: bool = True) -> "PackedBatch":
         """The items d_items[k] of this batch (an int32 CUDA tensor, read as unsigned, or a list of ints; in any order, with
         repeats) as a new packed batch: BatchIndex.cut_items of whole items through the batch's device index, which is made on the
@@ -1550,6 +1643,13 @@ class DeviceCodec:
         fm, fn, tm, tn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
         self.L.tsqa_profile_read_find(self.h, C.byref(fm), C.byref(fn), C.byref(tm), C.byref(tn))
         return fm.value, fn.value, tm.value, tn.value
+
+    def profile_read_crc(self):
+        """-> (decode_ms_sum, launches, fold_ms_sum, calls): the CRC decode of crc32_async (the decoder that checksums) and its fold
+        and close launches since the last read."""
+        dm, dn, fm, fn = C.c_double(0), C.c_uint32(0), C.c_double(0), C.c_uint32(0)
+        self.L.tsqa_profile_read_crc(self.h, C.byref(dm), C.byref(dn), C.byref(fm), C.byref(fn))
+        return dm.value, dn.value, fm.value, fn.value
 
     def measure_copy(self, nbytes: int = 1 << 30, reps: int = 7):
         """-> (best, median) GB/s of a plain device copy kernel, bytes read + written."""
@@ -2094,6 +2194,30 @@ class DeviceCodec:
                                     (self._status if d_status is None else d_status).data_ptr(), self._stream())
         if rc:
             raise self._err(rc)
+
+    def crc32_async(self, index, blocks: bool = False, all: bool = True, stream=None, d_items=None, d_item_status=None, d_blocks=None,
+                    d_all=None, d_status=None) -> "CrcTable":
+        """tsqa_crc32_async on the current stream (or `stream`, a torch stream), nothing waited for: zlib's CRC-32 of every item of
+        `index` -> a CrcTable of CUDA tensors.  all / blocks: the whole data's CRC and one CRC per block are asked for too.  The
+        tensors are made here unless given (d_items, d_blocks, d_all: int32, whose bits are the uint32 values; d_item_status,
+        d_status: int32; a given d_blocks or d_all is asked for whatever the flags say)."""
+        torch = self.torch
+        i32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int32, device=self.device)
+        n_items = int(self.L.tsqa_index_items(index.h))
+        n_blocks = int(self.L.tsqa_index_blocks(index.h))
+        d_items = i32(n_items)[:n_items] if d_items is None else d_items
+        d_item_status = i32(n_items)[:n_items] if d_item_status is None else d_item_status
+        if d_blocks is None and blocks:
+            d_blocks = i32(n_blocks)[:n_blocks]
+        if d_all is None and all:
+            d_all = i32(1)
+        d_status = i32(1) if d_status is None else d_status
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        s = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        rc = self.L.tsqa_crc32_async(self.h, index.h, 0, d_items.data_ptr(), d_item_status.data_ptr(), ptr(d_blocks), ptr(d_all), d_status.data_ptr(), s)
+        if rc:
+            raise self._err(rc)
+        return CrcTable(index, d_items, d_item_status, d_blocks, d_all, d_status)
 
     def join(self, blobs, out=None, block_sizes: bool = False):
         """Join .tsq containers (1-D uint8 CUDA tensors; placement as in compress_batch: views of one storage are read in place)

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "tsq_common.cuh"
+#include "tsq_crc32.h"
 
 namespace tsq {
 
@@ -679,6 +680,62 @@ __device__ __forceinline__ void flush_find(const uint8_t* lds, uint32_t* map32, 
         const uint64_t g = g0 + ((uint64_t)w << 4), word = (g >> 6) + blk;
         if (ends != 0u && word < map_words) atomicOr(map32 + 2u * word + ((uint32_t)(g >> 5) & 1u), ends << ((uint32_t)g & 16u));
     }
+}
+
+// ---------------- P7 of a CRC (dec_crc_kernel): no byte of the image goes anywhere.  The image is walked as flush_mark walks it, by
+// the aligned 16-byte ring cells it touches (c0, skew, cells, the wrap at C::R, the bytes outside [lo, hi) of the first and last
+// cell masked to zero), and what leaves is ONE word per image, XORed into *word (LDS, zero before the flush):
+//     W = xor over the cells w of  R(cell w, masked) (x) x^(128 (cells - 1 - w))
+// which is R(image | z zero bytes), z = the bytes between the image's last byte and the END of its last cell.  Every exponent is
+// thus a whole number of cells, and one table of x^(128 k) serves the cells and the block's running fold alike; the partial last
+// cell costs nothing here -- the zeros behind the block's last byte are taken off once per block, with x^(-8 z) (crc_block_fold).
+// Zeros in FRONT of a cell's bytes do not count at all, which is why the first cell's mask is enough.
+// A cell's R: four rounds of four look-ups in slice[4][256] (tsq_crc32.h), the register XORed with the next four bytes in
+// between.  Its shift: one 32-step product (crc_mul, tsq_crc32.h) with pow[cells - 1 - w].  Both tables are in LDS at `tab` (slice, then pow).
+// The lanes' words are XORed across the wavefront by shuffles, and one lane of each wavefront that had a cell sends one LDS
+// atomic XOR.  No barrier inside.
+template <class L>
+__device__ __forceinline__ void flush_crc(const uint8_t* lds, const uint32_t* tab, uint32_t* word, const Image& im, uint32_t first_tid,
+                                          uint32_t n_threads)
+{
+    using C = SymCfg;
+    const uint32_t tid = threadIdx.x;
+    const uint8_t* const ring = lds + L::ring;
+    if (im.len == 0 || tid < first_tid) return;
+    const uint32_t skew = im.at & 15u, cells = (skew + im.len + 15u) >> 4;
+    const uint32_t c0 = im.at & ~15u;
+    if (((tid - first_tid) & ~63u) >= cells) return;                            // (a whole wavefront with no cell)
+    const uint32_t* const pow = tab + 1024;
+    uint32_t acc = 0;
+    for (uint32_t w = tid - first_tid; w < cells; w += n_threads) {
+        uint32_t a = c0 + (w << 4); a -= a >= C::R ? C::R : 0u;
+        const uint4 x = *reinterpret_cast<const uint4*>(ring + a);
+        const uint32_t lo = w == 0u ? skew : 0u, left = skew + im.len - (w << 4), hi = left < 16u ? left : 16u;   // the image's bytes [lo, hi) of the cell
+        const uint32_t keep = (0xFFFFu << lo) & (0xFFFFu >> (16u - hi));
+        const uint32_t v[4] = {x.x, x.y, x.z, x.w};
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            // the four bits of `keep` that belong to this word, one to a byte, then whole bytes
+            const uint32_t bytes = ((((keep >> (4u * i)) & 0xFu) * 0x00204081u) & 0x01010101u) * 0xFFu;
+            c ^= v[i] & bytes;
+            c = tab[768u + (c & 0xFFu)] ^ tab[512u + ((c >> 8) & 0xFFu)] ^ tab[256u + ((c >> 16) & 0xFFu)] ^ tab[c >> 24];
+        }
+        acc ^= crc_mul(c, pow[cells - 1u - w]);
+    }
+#pragma unroll
+    for (uint32_t d = 32u; d != 0u; d >>= 1) acc ^= (uint32_t)__shfl_xor((int)acc, (int)d);
+    if ((tid & 63u) == 0u && acc != 0u) atomicXor(word, acc);
+}
+
+// One image joins the block's running word: A is R(the block's bytes so far | the zeros up to the end of the last cell touched).
+// The image's first cell is the last image's last cell when it starts inside one (skew != 0), so the grid moves on by cells - 1
+// cells then, by `cells` otherwise.
+__device__ __forceinline__ uint32_t crc_image_fold(uint32_t acc, const uint32_t* tab, const Image& im, uint32_t word)
+{
+    const uint32_t skew = im.at & 15u, cells = (skew + im.len + 15u) >> 4;
+    const uint32_t moved = cells - (skew != 0u && cells != 0u ? 1u : 0u);
+    return crc_mul(acc, tab[1024u + moved]) ^ word;
 }
 
 }  // namespace tsq

@@ -46,7 +46,17 @@ struct BlockGroup {
     uint32_t block, first, count, hi;
 };
 
-enum DecMode : int { kDecWhole, kDecWindow, kDecGroup, kDecMark, kDecFind };
+enum DecMode : int { kDecWhole, kDecWindow, kDecGroup, kDecMark, kDecFind, kDecCrc };
+
+// LDS of dec_crc_kernel behind the decoder's own: the CRC tables of flush_crc (slice[4][256], then pow[kCrcCells + 1]: tsq_crc32.h)
+// and the two words into which the images' flushes XOR, by turns.  The other kernels ask for SymLds::total as before.
+struct CrcLds {
+    static constexpr uint32_t tab = (SymLds::total + 15u) & ~15u;                  // u32[kCrcLdsWords]
+    static constexpr uint32_t word = tab + 4u * ((kCrcLdsWords + 3u) & ~3u);        // u32[2]
+    static constexpr uint32_t total = word + 16u;
+};
+static_assert(CrcLds::total <= 160 * 1024, "LDS budget");
+static_assert(kCrcCells >= ((15u + SymCfg::OUTC + 15u) >> 4) + 1u, "a power for every cell count of an image");
 
 // ---------------- P7 of a record read: the image's bytes go to every item of the group that they meet (byte p of the block to
 // out[it.out_at + p - it.lo]).  The items are sorted by lo, so those that meet the image are a run of the list that only moves
@@ -178,7 +188,13 @@ __device__ __forceinline__ void flush_group(const uint8_t* lds, uint8_t* out, co
 // flush_mark, map_words long, and every chunk's image is compared with `delim` there.  Every use of that mode sits behind
 // `if constexpr`, so the other three are compiled as they were.  kDecFind (dec_find_kernel): kDecMark with a needle of up to 16
 // bytes in place of the delimiter (flush_find), and the block's first and last 15 bytes left in `edges`; it sits behind
-// `if constexpr` in the same places.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
+// `if constexpr` in the same places.  kDecCrc (dec_crc_kernel): like kDecMark no byte is written; every image leaves one word
+// (flush_crc), which one thread folds into the block's running word A = A (x) x^(128 cells moved) xor W, and `outbuf` is a table
+// of one u32 per block that takes R(block) at the end.  The fold of an image is made one chunk late, by the first thread of the
+// upper half in front of its next flush: the barrier that closes a P4 lies behind that P4's flush, so the word is complete then,
+// and the images' words take turns so that the flush under way XORs into the other one.  The last image is flushed by all lanes
+// behind the loop and ONE barrier, the only one this mode adds, stands between that flush and its fold.  It too sits behind
+// `if constexpr`.  (The pointers carry no __restrict__ here: the kernels' own parameters do, and restrict parameters of an
 // inlined function would give dec_sym_kernel other code than before.)
 template <DecMode kMode>
 __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const FrameInfo* frames, uint32_t n_frames, const RangeItem* items,
@@ -187,6 +203,7 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
                                                  [[maybe_unused]] FindNeedle needle = {0ull, 0ull, 0u}, [[maybe_unused]] uint8_t* edges = nullptr)
 {
     constexpr bool kWindow = kMode == kDecWindow, kGroup = kMode == kDecGroup, kMark = kMode == kDecMark, kFind = kMode == kDecFind;
+    constexpr bool kCrc = kMode == kDecCrc;
     using C = SymCfg;
     using L = SymLds;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -235,12 +252,14 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     // window: `out` is where byte lo goes; byte p of the block goes to out + (p - lo)
     // (group: every item has a destination of its own in outbuf; no skew of the ring can serve them all)
     // (mark: outbuf is the bit map, and no byte of the block has a destination)
-    uint8_t* const out = kGroup || kMark || kFind ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
+    // (crc: outbuf is the blocks' table of words)
+    uint8_t* const out = kGroup || kMark || kFind || kCrc ? outbuf : outbuf + (kWindow ? out_at : f.out_at);
     const uint32_t in_len = f.stream_len, size = f.out_len, ext = f.ext;
     // ring address of output position p: (p + oskew) mod R, so that 16-byte words of the ring are 16-byte words of HBM (window: of
     // the block's virtual base out - lo)
     // (mark: the 64-position grid of the concatenation falls on the ring's 64-byte grid, flush_mark)
-    const uint32_t oskew = kMark || kFind ? (uint32_t)(f.out_at & 63u) : kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
+    // (crc: no grid outside the block matters; the block starts on a cell)
+    const uint32_t oskew = kCrc ? 0u : kMark || kFind ? (uint32_t)(f.out_at & 63u) : kGroup ? 0u : (uint32_t)(((uintptr_t)out - lo) & 15u);
 
 #ifdef TSQ_STATS
     const uint32_t lane = tid & 63u, wid = tid >> 6;
@@ -249,6 +268,17 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
 #endif
     TSQD_T0();
     if (tid == 0) { misc[4] = 0; misc[9] = 0; misc[10] = 0; }
+    // crc: the tables come to LDS and the images' two words are cleared, under the barrier below; what the fold carries: the
+    // running word, the images made so far and the image in front of `prev`, whose word is still to be folded
+    [[maybe_unused]] const uint32_t* const ctab = reinterpret_cast<const uint32_t*>(lds + CrcLds::tab);
+    [[maybe_unused]] uint32_t* const cword = reinterpret_cast<uint32_t*>(lds + CrcLds::word);
+    [[maybe_unused]] uint32_t crc_acc = 0, n_img = 0;
+    [[maybe_unused]] Image prev2 = {0, 0, 0};
+    if constexpr (kCrc) {
+        const uint32_t* const src = reinterpret_cast<const uint32_t*>(&g_crc_tables);
+        for (uint32_t k = tid; k < kCrcLdsWords; k += C::T) reinterpret_cast<uint32_t*>(lds + CrcLds::tab)[k] = src[k];
+        if (tid < 2u) cword[tid] = 0u;
+    }
     uint32_t sp = 3, op = 0;
     uint32_t ring_op = oskew;            // ring address of position op
     Image prev = {0, 0, 0};              // what P7 still has to write out: the previous chunk's image
@@ -279,7 +309,13 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
         // HBM meanwhile (P7).  (measured in round 5: a build without this flush runs 4.558 against 4.553 ms, the flush beside P3's
         // chain instead 4.572 -- it hides completely)
         if (tid >= C::T / 2) {
-            if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, C::T / 2, C::T / 2);
+            if constexpr (kCrc) {
+                // image n_img - 2 joins the running word (its flush lies behind the last chunk's barriers), then image n_img - 1
+                // is flushed into the other word
+                if (tid == C::T / 2 && n_img >= 2u) { crc_acc = crc_image_fold(crc_acc, ctab, prev2, cword[n_img & 1u]); cword[n_img & 1u] = 0u; }
+                flush_crc<L>(lds, ctab, cword + ((n_img + 1u) & 1u), prev, C::T / 2, C::T / 2);
+            }
+            else if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, C::T / 2, C::T / 2);
             else if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, C::T / 2, C::T / 2);
             else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, C::T / 2, C::T / 2);
             else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, C::T / 2, C::T / 2);
@@ -333,6 +369,7 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
 #endif
 
         // ---------------- the image is complete: it goes to HBM during the next chunk's P4 (or right now, after the last chunk)
+        if constexpr (kCrc) { prev2 = prev; ++n_img; }
         prev = im;
         ring_op += im.len; ring_op -= ring_op >= C::R ? C::R : 0u;
         op = e.next_op;
@@ -345,7 +382,18 @@ __device__ __forceinline__ void sym_decode_block(const uint8_t* container, const
     if constexpr (kGroup) { if (tid == C::T / 2) misc[12] = gcur.cur; }
     __syncthreads();
     if constexpr (kGroup) { if (tid < C::T / 2) gcur.cur = misc[12]; }
-    if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, 0, C::T);
+    if constexpr (kCrc) {
+        if (tid == C::T / 2 && n_img >= 2u) { crc_acc = crc_image_fold(crc_acc, ctab, prev2, cword[n_img & 1u]); cword[n_img & 1u] = 0u; }
+        flush_crc<L>(lds, ctab, cword + ((n_img + 1u) & 1u), prev, 0, C::T);
+        __syncthreads();                                     // (the one barrier of this mode: the last image's word is complete behind it)
+        if (tid == C::T / 2) {
+            crc_acc = crc_image_fold(crc_acc, ctab, prev, cword[(n_img + 1u) & 1u]);
+            // the zeros between the block's last byte and the end of its last cell come off again: R(block)
+            const uint32_t pad = (16u - ((prev.at + prev.len) & 15u)) & 15u;
+            reinterpret_cast<uint32_t*>(out)[blk] = crc_mul(crc_acc, g_crc_tables.inv[pad]);
+        }
+    }
+    else if constexpr (kFind) flush_find<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, needle, size, edges, 0, C::T);
     else if constexpr (kMark) flush_mark<L>(lds, reinterpret_cast<uint32_t*>(out), map_words, f.out_at, blk, prev, delim, 0, C::T);
     else if constexpr (kGroup) flush_group<L>(lds, out, prev, gitems, gcount, gcur, 0, C::T);
     else if constexpr (kWindow) flush_window<L>(lds, out, prev, lo, hi, 0, C::T);
@@ -414,6 +462,30 @@ __global__ __launch_bounds__(1024) void dec_find_kernel(const uint8_t* __restric
     if (verdict && *verdict != 0) return;
     const FindNeedle needle = {((uint64_t)n1 << 32) | n0, ((uint64_t)n3 << 32) | n2, m};
     sym_decode_block<kDecFind>(container, frames, 0u, nullptr, reinterpret_cast<uint8_t*>(map), status, nullptr, 0u, 0u, map_words, needle, edges);
+}
+
+// The CRC (tsqa_crc32_async): one workgroup per block of the index, the block decoded whole and validated as in dec_sym_kernel, and
+// nothing of it written but block_r[block] = R(block) (tsq_crc32.h), which crc_fold_kernel (tsq_crc.cuh) carries to the items.  The
+// block's item is found here, by bisection in item_first (NULL: one item owns every block) as records_count_kernel finds it, and
+// the decoder reads and raises THAT item's status word, as dec_item_kernel does: a malformed stream ends the rest of its item
+// and nobody else's.  A workgroup that leaves with its item's word raised raises *any as well, for the call's status.
+__global__ __launch_bounds__(1024) void dec_crc_kernel(const uint8_t* __restrict__ container, const FrameInfo* __restrict__ frames,
+                                                       const int32_t* __restrict__ verdict, const uint64_t* __restrict__ item_first,
+                                                       uint32_t n_items, uint32_t* __restrict__ block_r, int32_t* __restrict__ item_status,
+                                                       int32_t* __restrict__ any)
+{
+    if (verdict && *verdict != 0) return;
+    uint32_t it = 0;
+    if (item_first) {
+        uint32_t lo = 0, hi = n_items;
+        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (item_first[mid] <= blockIdx.x) lo = mid; else hi = mid; }
+        it = lo;
+    }
+    sym_decode_block<kDecCrc>(container, frames, 0u, nullptr, reinterpret_cast<uint8_t*>(block_r), item_status + it);
+    if (threadIdx.x == 0u) {
+        const int32_t st = __hip_atomic_load(item_status + it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st != 0) atomicMax(any, st);
+    }
 }
 
 }  // namespace tsq

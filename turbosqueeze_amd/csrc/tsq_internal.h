@@ -154,6 +154,8 @@ struct tsqa_ctx {
     // -- and beside it 32 bytes per block for the blocks' first and last 15 bytes, and two words for the scan's count
     tsqa_scratch<uint8_t> find_edges;
     tsqa_scratch<uint64_t> find_need;
+    // tsqa_crc32_async (tsq_crc.cuh): the call's word, then one word per block, R of the block; cleared per call
+    tsqa_scratch<uint32_t> crc_blocks;
     char probe_shape[160] = {0};               // what tsqa_measure_copy chose (tsqa_copy_probe_shape)
     tsqa_scratch<uint32_t> duo_ring;           // two-workgroup decoder: chunk records handed from the PARSE to the COPY workgroup of a block
     tsqa_scratch<uint32_t> duo_flags;          // and their progress counters
@@ -168,8 +170,9 @@ struct tsqa_ctx {
     // 5 the cut's copy kernel (tsqa_cut_async and tsqa_cut_items_async), 6 the gather's planner (its launches in front of the decode), 7 the decode kernel of a record read
     // (tsqa_decompress_item_ranges_async, tsqa_gather_async and tsqa_gather_rows_async, whose planner is kind 6 too), 8 the pad kernel
     // of tsqa_gather_rows_async, 9 the mark decode of tsqa_records_async (dec_mark_kernel), 10 its table launches (tsq_records.cuh),
-    // 11 the find decode of tsqa_find_async (dec_find_kernel), 12 its seam and table launches (tsq_find.cuh).
-    static constexpr int kProfKinds = 13, kProfPairs = 256;
+    // 11 the find decode of tsqa_find_async (dec_find_kernel), 12 its seam and table launches (tsq_find.cuh),
+    // 13 the CRC decode of tsqa_crc32_async (dec_crc_kernel), 14 its fold and close launches (tsq_crc.cuh).
+    static constexpr int kProfKinds = 15, kProfPairs = 256;
     bool profiling = false;
     std::vector<hipEvent_t> prof_pool;                     // kProfKinds * kProfPairs * 2 events
     uint32_t prof_used[kProfKinds] = {0};
@@ -187,6 +190,7 @@ struct tsqa_ctx {
     int reserve_gather(size_t n_ranges, size_t cap_pieces, size_t cap_groups);
     int reserve_records(size_t map_words, size_t n_blocks);
     int reserve_find(size_t map_words, size_t n_blocks);
+    int reserve_crc(size_t n_blocks);
     // `readable` >= n: bytes of d_in that may be read (look-ahead halo); zeros are seen beyond it
     int launch_encode(const void* d_in, size_t n, size_t readable, uint32_t ext, int32_t* status, hipStream_t s);
     // general form: block b at d_in + b * stride, streams to slots_out[b * TSQ_OUTPUT_SZ], sizes to sizes_out[b]

@@ -23,6 +23,7 @@
 #include "tsq_rows.cuh"
 #include "tsq_records.cuh"
 #include "tsq_find.cuh"
+#include "tsq_crc.cuh"
 
 #include <algorithm>
 #include <cstdarg>
@@ -323,6 +324,15 @@ int tsqa_ctx::reserve_find(size_t map_words, size_t n_blocks)
     return find_edges.grow(this, edges) && find_need.grow(this, 2) ? TSQA_OK : TSQA_ERR_HIP;
 }
 
+// Scratch of the CRC: the call's word, then one word per block (R of the block); every call clears it.
+int tsqa_ctx::reserve_crc(size_t n_blocks)
+{
+    const size_t words = 1 + doubled(256, n_blocks);
+    if (!crc_blocks.needs(words)) return TSQA_OK;
+    (void)hipDeviceSynchronize();                        // (as in reserve_batch)
+    return crc_blocks.grow(this, words) ? TSQA_OK : TSQA_ERR_HIP;
+}
+
 // ---- kernel timing ----
 // One timed span of `kind` on `s`, where profiling is on and the kind has a pair left: the opening event is recorded here, the
 // closing one by end(); cancel() gives the pair back when what the span was to time was never enqueued.
@@ -450,6 +460,16 @@ extern "C" int tsqa_profile_read_find(tsqa_ctx* c, double* find_ms, uint32_t* fi
     if (c->prof_pool.empty()) { if (find_ms) *find_ms = 0; if (find_n) *find_n = 0; if (table_ms) *table_ms = 0; if (table_n) *table_n = 0; return TSQA_OK; }
     drain_events(c, 11, find_ms, find_n);
     drain_events(c, 12, table_ms, table_n);
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_profile_read_crc(tsqa_ctx* c, double* decode_ms, uint32_t* decode_n, double* fold_ms, uint32_t* fold_n)
+{
+    if (!c) return TSQA_ERR_ARG;
+    (void)hipSetDevice(c->device);
+    if (c->prof_pool.empty()) { if (decode_ms) *decode_ms = 0; if (decode_n) *decode_n = 0; if (fold_ms) *fold_ms = 0; if (fold_n) *fold_n = 0; return TSQA_OK; }
+    drain_events(c, 13, decode_ms, decode_n);
+    drain_events(c, 14, fold_ms, fold_n);
     return TSQA_OK;
 }
 
@@ -2537,6 +2557,104 @@ extern "C" int tsqa_find(tsqa_ctx* c, const tsqa_index* idx, const void* needle,
     TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
     TSQ_HIP(c, hipStreamSynchronize(s));
     return status_to_rc(c, st, "find");
+}
+
+// ---- zlib's CRC-32 of every item: a decode that keeps one word per block, a fold of the blocks' words into the items' and a
+// close (tsq_crc.cuh); the arithmetic and its host forms (tsq_crc32.h) ----
+
+static constexpr CrcTables kCrcHostTables = crc_make_tables();
+
+extern "C" uint32_t tsqa_crc32_host(uint32_t crc, const void* buf, size_t n)
+{
+    return buf ? crc_update_host(kCrcHostTables, crc, static_cast<const uint8_t*>(buf), n) : crc;
+}
+
+extern "C" uint32_t tsqa_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
+{
+    return crc_mul(crc_a, crc_xpow8(len_b)) ^ crc_b;
+}
+
+extern "C" int tsqa_plan_crc32(const void* data, const uint64_t* item_at, const int32_t* item_status, uint32_t n_items, uint32_t* item_crc,
+                               uint32_t* all_crc)
+{
+    if (!item_at || !item_crc || n_items == 0) return TSQA_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_at[i + 1] < item_at[i]) return TSQA_ERR_ARG;
+    if (!data && item_at[n_items] != item_at[0]) return TSQA_ERR_ARG;
+    const uint8_t* const bytes = static_cast<const uint8_t*>(data);
+    uint32_t all = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const uint64_t a = item_at[i], e = item_at[i + 1];
+        item_crc[i] = 0;
+        if (a == e || (item_status && item_status[i] != 0)) continue;       // (a refused item has no bytes in the whole data either)
+        all = crc_update_host(kCrcHostTables, all, bytes + a, (size_t)(e - a));
+        item_crc[i] = crc_update_host(kCrcHostTables, 0u, bytes + a, (size_t)(e - a));
+    }
+    if (all_crc) *all_crc = all;
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_crc32_async(tsqa_ctx* c, const tsqa_index* idx, uint32_t flags, uint32_t* d_item_crc, int32_t* d_item_status,
+                                uint32_t* d_block_crc, uint32_t* d_all_crc, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    if (!idx || !d_item_crc || !d_item_status || !d_status) { c->set_error("crc32: null pointer"); return TSQA_ERR_ARG; }
+    if (flags != 0u) { c->set_error("crc32: unknown flags 0x%x", flags); return TSQA_ERR_ARG; }
+    if (idx->device != c->device) { c->set_error("crc32: the index belongs to device %d, the context to %d", idx->device, c->device); return TSQA_ERR_ARG; }
+    // (the host sizes the blocks' table from the block count, which it does not have before the fetch)
+    if (idx->pending_items != 0u) { c->set_error("crc32: %s", kNeedsFetch); return TSQA_ERR_ARG; }
+    hipStream_t s = stream_of(c, hip_stream);
+    (void)hipSetDevice(c->device);
+    const uint32_t n_blocks = idx->n_blocks, n_items = tsqa_index_items(idx);
+    if (int rc = c->reserve_crc(n_blocks)) return rc;
+    int32_t* const any = reinterpret_cast<int32_t*>(static_cast<uint32_t*>(c->crc_blocks));
+    uint32_t* const block_r = c->crc_blocks + 1;
+    const FrameInfo* const frames = idx->frames;
+    const int32_t* const verdict = idx->verdict;
+    const uint64_t* const item_first = idx->d_item_first;
+    // the items' status words start as the index's own: zeros, but for the items it refused (which own no block)
+    bool refused = false;
+    for (size_t i = 0; i < idx->item_status.size() && i < n_items; ++i) refused = refused || idx->item_status[i] != 0;
+    if (refused) {
+        tsqa_uploads::Slot up;
+        if (int rc = c->range_up.acquire(c, (size_t)n_items * sizeof(int32_t), &up)) return rc;
+        for (uint32_t i = 0; i < n_items; ++i) up.host<int32_t>()[i] = i < idx->item_status.size() ? idx->item_status[i] : 0;
+        TSQ_HIP(c, hipMemcpyAsync(d_item_status, up.host<int32_t>(), (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        TSQ_HIP(c, up.commit(s));
+    } else {
+        TSQ_HIP(c, hipMemsetAsync(d_item_status, 0, (size_t)n_items * sizeof(int32_t), s));
+    }
+    TSQ_HIP(c, hipMemsetAsync(d_item_crc, 0, (size_t)n_items * sizeof(uint32_t), s));
+    if (d_all_crc) TSQ_HIP(c, hipMemsetAsync(d_all_crc, 0, sizeof(uint32_t), s));
+    TSQ_HIP(c, hipMemsetAsync(c->crc_blocks, 0, ((size_t)n_blocks + 1) * sizeof(uint32_t), s));
+    if (n_blocks != 0) {
+        ProfSpan decode(c, 13, s);
+        TSQ_RAISE_LDS(c, lds_need(dec_crc_kernel, CrcLds::total));
+        hipLaunchKernelGGL(dec_crc_kernel, dim3(n_blocks), dim3(SymCfg::T), CrcLds::total, s, idx->container, frames, verdict, item_first, n_items, block_r,
+                           d_item_status, any);
+        decode.end();
+    }
+    ProfSpan fold(c, 14, s);
+    const uint64_t lanes = std::max<uint64_t>(n_blocks, (uint64_t)n_items + 1u);
+    hipLaunchKernelGGL(crc_fold_kernel, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, s, frames, n_blocks, idx->total, verdict, item_first, n_items,
+                       static_cast<const uint32_t*>(block_r), static_cast<const int32_t*>(d_item_status), d_item_crc, d_block_crc, d_all_crc);
+    hipLaunchKernelGGL(crc_close_kernel, dim3(std::max(1u, (uint32_t)(((uint64_t)n_items + 255u) / 256u))), dim3(256), 0, s, verdict, static_cast<const int32_t*>(any), n_items, d_item_status,
+                       d_item_crc, d_all_crc, d_status);
+    fold.end();
+    TSQ_HIP(c, hipGetLastError());
+    return TSQA_OK;
+}
+
+extern "C" int tsqa_crc32(tsqa_ctx* c, const tsqa_index* idx, uint32_t flags, uint32_t* d_item_crc, int32_t* d_item_status, uint32_t* d_block_crc,
+                          uint32_t* d_all_crc, int32_t* d_status, void* hip_stream)
+{
+    if (!c) return TSQA_ERR_ARG;
+    hipStream_t s = stream_of(c, hip_stream);
+    if (int rc = tsqa_crc32_async(c, idx, flags, d_item_crc, d_item_status, d_block_crc, d_all_crc, d_status, s)) return rc;
+    int32_t st = 0;
+    TSQ_HIP(c, hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+    TSQ_HIP(c, hipStreamSynchronize(s));
+    return status_to_rc(c, st, "crc32");
 }
 
 // ---- gather into fixed-stride padded rows: the same ranges, row k at k * row_stride, the tails filled (tsq_rows.cuh) ----
